@@ -9,8 +9,11 @@ A "step" is one decoded token (one pass of the per-token hot path: L decoder lay
 The request is ALWAYS the headline one -- a 1024-token prompt prefilled through the real context path (KV cache resident
 in HBM) and --output-len (512) generated tokens -- whatever --steps / --warmup say: the K timed steps (preceded by W
 untimed ones) are a window of that request centred on output token 256, i.e. on the mean KV length 1280 of the whole
-request (K + W >= 512: the whole request is the window).  The steps before and after the window run untimed, then one
-complete ftcf_gptneox_forward of the same request gives the end-to-end latency.  return_cum_log_probs = 1 as in the
+request (K + W >= 512: the whole request is the window; K + W > --output-len lengthens the request to K + W tokens, so K is
+always the number of timed steps).  The steps before and after the window run untimed, then one complete
+ftcf_gptneox_forward of the same request gives the end-to-end latency.  --dump-outputs DIR writes what the measured
+request returned to its caller (output ids, sequence lengths, cumulative log-probs) as DIR/<name>.npy; the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.  return_cum_log_probs = 1 as in the
 reference harness (codefuse_example.py:745).  Weights are synthetic (random int8 + fp16 scales of CodeFuse-13B's shape,
 generated on the device); there is no network for checkpoints.  Rank 0 prints ONE JSON line.
 """
@@ -31,7 +34,7 @@ import torch  # noqa: E402
 def parse():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
-    p.add_argument("--steps", type=int, default=504)
+    p.add_argument("--steps", type=int, default=504, help="timed decode steps (>= 1)")
     p.add_argument("--warmup", type=int, default=8)
     p.add_argument("--dtype", default="int8", choices=["int8", "fp16"])
     p.add_argument("--prompt-len", type=int, default=1024)
@@ -54,7 +57,12 @@ def parse():
     p.add_argument("--fake-tp", type=int, default=0,
                    help="timing aid: run rank 0's shard of a TP=N model in ONE process over a 1-rank communicator "
                         "(no peers: outputs are meaningless, the JSON line is marked invalid)")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the measured request's outputs (what the caller receives) as DIR/<name>.npy (rank 0)")
+    a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def synth_weights(a, tp, dev):
@@ -243,11 +251,10 @@ def main():
     op = GptNeoXOp(group, rank, a.heads, a.head_dim, a.inter, a.layers, a.vocab, a.rotary, 0, end_id, tp, 1,
                    1 if a.dtype == "int8" else 0, 2048, True, weights, int8_w, scales)
     B, S = a.batch, a.prompt_len
-    out_len = a.output_len
+    out_len = max(a.output_len, a.steps + a.warmup)  # K timed steps + W warm-up steps always fit in the request
     # the timed window inside the request: K steps centred on output token out_len / 2 (KV length S + out_len / 2 = the
     # request's mean), W untimed steps right before it; the rest of the request runs untimed around the window
-    steps = min(a.steps, out_len)
-    warmup = min(a.warmup, out_len - steps)
+    steps, warmup = a.steps, a.warmup
     first = max(warmup, min(out_len - steps, out_len // 2 - steps // 2))  # output index of the first timed step
     pre, post = first - warmup, out_len - first - steps
     gi = torch.Generator().manual_seed(42)
@@ -331,6 +338,10 @@ def main():
         return pw, ta, tb
 
     prefill_wall_ms, t0, t1 = with_fallback(measured_request)
+    # what the measured request handed back (the requests below write the same buffers): ids as float64 (exact)
+    outputs = {"output_ids": out_ids.cpu().numpy().astype(np.float64),
+               "sequence_lengths": seq.cpu().numpy().astype(np.float64),
+               "cum_log_probs": cum.cpu().numpy().astype(np.float32)}
     elapsed = torch.tensor([t1 - t0], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
@@ -408,6 +419,10 @@ def main():
         if world > 1:
             dist.destroy_process_group()
         return
+    if a.dump_outputs:
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, arr in outputs.items():
+            np.save(os.path.join(a.dump_outputs, name + ".npy"), arr)
     tok_s = steps * B / elapsed
     t_mean = S + first + steps / 2.0  # mean KV length of the timed steps
     bpt = bytes_per_token(a, tp, t_mean)  # HBM bytes of ONE step (weights once, K/V rows of all B rows)
