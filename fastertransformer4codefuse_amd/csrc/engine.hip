@@ -230,17 +230,30 @@ extern "C" int ftcf_context_attention(const void* qkv, const void* qkv_bias, con
 // the engine
 // ---------------------------------------------------------------------------------------------------------------
 
-// transposeAxis01 for the TP logits all-gather: [tp][B][vl] -> [B][V] (GptNeoX.cc:913-924)
-__global__ void k_transpose_gathered_logits(float* out, const float* in, int tp, int B, int vl)
+// transposeAxis01 for the TP logits all-gather: [tp][B][vl] -> [B][V] (GptNeoX.cc:913-924); src >= 0 reads every slice
+// from slot [src] (fake peers: only the rank's own slot was written)
+__global__ void k_transpose_gathered_logits(float* out, const float* in, int tp, int B, int vl, int src)
 {
     const size_t total = (size_t)tp * B * vl;
+    const size_t slot  = (size_t)B * vl;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const int    j = (int)(i % vl);
         const size_t t = i / vl;
         const int    b = (int)(t % B), r = (int)(t / B);
-        out[(size_t)b * tp * vl + (size_t)r * vl + j] = in[i];
+        out[(size_t)b * tp * vl + (size_t)r * vl + j] = in[src < 0 ? i : (size_t)src * slot + (i % slot)];
     }
 }
+
+// the all-reduce of fake peers: TP identical partials sum to TP x the buffer (fp32 product, one rounding)
+template<typename T>
+__global__ void k_scale_by_tp(T* buf, size_t n, float tp)
+{
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        buf[i] = (T)((float)buf[i] * tp);
+    }
+}
+template __global__ void k_scale_by_tp<f16>(f16*, size_t, float);
+template __global__ void k_scale_by_tp<float>(float*, size_t, float);
 
 template<typename T>
 static std::vector<T> broadcast_arg(const T* p, int n, int B, T dflt, const char* name)
@@ -314,7 +327,8 @@ void ftcf_gptneox::begin(const ftcf_forward_args& a)
             FTCF_HIP_CHECK(hipMemsetAsync(tp_scratch, 0, 256, stream));
         }
         comm_barrier(cfg.comm, stream, tp_scratch);
-        FTCF_HIP_CHECK(hipMemsetAsync(cfg.comm->win[cfg.tensor_para_rank], 0, (size_t)2 * tpn * H * 8, stream));
+        // (this rank's own window: with fake peers it is the only one, whatever the rank)
+        FTCF_HIP_CHECK(hipMemsetAsync(cfg.comm->win[fake_peers() ? 0 : cfg.tensor_para_rank], 0, (size_t)2 * tpn * H * 8, stream));
         comm_barrier(cfg.comm, stream, tp_scratch);
     }
 

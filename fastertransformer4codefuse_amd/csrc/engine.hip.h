@@ -55,7 +55,9 @@ enum { KIND_LN_GEMV = 0, KIND_SPLITK = 1, KIND_LM_HEAD = 2, KIND_FUSED = 3, KIND
 
 }  // namespace
 
-__global__ void k_transpose_gathered_logits(float* out, const float* in, int tp, int B, int vl);  // (defined below)
+__global__ void k_transpose_gathered_logits(float* out, const float* in, int tp, int B, int vl, int src);  // (defined below)
+template<typename T>
+__global__ void k_scale_by_tp(T* buf, size_t n, float tp);  // (defined below)
 
 struct ftcf_gptneox {
     ftcf_gptneox_config       cfg{};
@@ -423,7 +425,17 @@ struct ftcf_gptneox {
                       &smallm_seq);
     }
 
-    void allreduce(f16* buf, size_t count, hipStream_t on = nullptr)
+    // fake peers (FTCF_FAKE_TP, bench.py --fake-tp N): a rank of a TP = N job alone on a one-rank RCCL communicator.  It
+    // plays every peer with its own shard, so an all-reduce is TP x its buffer and the gathered logits are TP copies of its
+    // slice: outputs are those of a TP = N job whose every rank holds shard `rank`.
+    bool fake_peers() const
+    {
+        return cfg.tensor_para_size > 1 && cfg.comm && cfg.comm->world == 1 && !cfg.comm->local && !cfg.comm->hx;
+    }
+    int fake_peers_mul() const { return fake_peers() ? cfg.tensor_para_size : 1; }
+
+    // (consumer_scales: the kernel that reads the result multiplies it by fake_peers_mul() itself -- no launch here)
+    void allreduce(f16* buf, size_t count, hipStream_t on = nullptr, bool consumer_scales = false)
     {
         if (cfg.tensor_para_size > 1) {
             Range r("ftcf.allreduce");
@@ -441,6 +453,13 @@ struct ftcf_gptneox {
                 hx_allreduce(cfg.comm, buf, count, true, st);
                 return;
             }
+            if (fake_peers()) {
+                if (consumer_scales) {
+                    return;
+                }
+                hipLaunchKernelGGL(k_scale_by_tp<f16>, dim3(256), dim3(256), 0, st, buf, count, (float)cfg.tensor_para_size);
+                return;  // TP identical partials
+            }
             FTCF_NCCL_CHECK(ncclAllReduce(buf, buf, count, ncclFloat16, ncclSum, cfg.comm->comm, st));
         }
     }
@@ -451,6 +470,12 @@ struct ftcf_gptneox {
     {
         const int tp = cfg.tensor_para_size;
         float*    mine = gath + (size_t)cfg.tensor_para_rank * B * vl;
+        if (fake_peers()) {
+            // every peer's slice is this rank's own: the transpose reads slot [rank] for all of them (no collective)
+            hipLaunchKernelGGL(k_transpose_gathered_logits, dim3(256), dim3(256), 0, st, out, gath, tp, B, vl,
+                               cfg.tensor_para_rank);
+            return;
+        }
         if (cfg.comm->local) {
             local_allgather(cfg.comm, gath, (size_t)B * vl, false, st);
         }
@@ -460,7 +485,7 @@ struct ftcf_gptneox {
         else {
             FTCF_NCCL_CHECK(ncclAllGather(mine, gath, (size_t)B * vl, ncclFloat32, cfg.comm->comm, st));
         }
-        hipLaunchKernelGGL(k_transpose_gathered_logits, dim3(256), dim3(256), 0, st, out, gath, tp, B, vl);
+        hipLaunchKernelGGL(k_transpose_gathered_logits, dim3(256), dim3(256), 0, st, out, gath, tp, B, vl, -1);
     }
 
     // ---------------------------------------------------------------------------------------------------------------
@@ -480,6 +505,10 @@ struct ftcf_gptneox {
             }
             if (cfg.comm->hx) {
                 hx_allreduce(cfg.comm, buf, count, false, stream);
+                return;
+            }
+            if (fake_peers()) {
+                hipLaunchKernelGGL(k_scale_by_tp<float>, dim3(256), dim3(256), 0, stream, buf, count, (float)cfg.tensor_para_size);
                 return;
             }
             FTCF_NCCL_CHECK(ncclAllReduce(buf, buf, count, ncclFloat32, ncclSum, cfg.comm->comm, stream));
@@ -783,10 +812,10 @@ struct ftcf_gptneox {
             pp.xw[r] = (cfg.tensor_para_size > 1 && cfg.comm && r < (int)cfg.comm->win.size())
                            ? static_cast<unsigned long long*>(cfg.comm->win[r]) : nullptr;
         }
-        if (cfg.tensor_para_size > 1 && cfg.comm && cfg.comm->world == 1 && !cfg.comm->win.empty()) {
-            // timing aid (bench.py --fake-tp N: ONE rank of a TP = N job without its peers): the rank plays every peer --
-            // "slot [rank] of rank r's window" is made to land in slot [r] of its own -- so that the kernel's exchange
-            // completes (the sums are meaningless, the work and the waits of a rank are all there)
+        if (fake_peers() && !cfg.comm->win.empty()) {
+            // fake peers (bench.py --fake-tp N: ONE rank of a TP = N job without its peers): the rank plays every peer --
+            // "slot [rank] of rank r's window" is made to land in slot [r] of its own -- so that the kernel's exchange adds
+            // TP copies of this rank's partial: outputs are those of a TP = N job whose every rank holds shard `rank`
             for (int r = 0; r < cfg.tensor_para_size && r < PERSIST_MAX_TP; r++) {
                 pp.xw[r] = static_cast<unsigned long long*>(cfg.comm->win[0])
                            + (ptrdiff_t)(r - cfg.tensor_para_rank) * ((ptrdiff_t)B * H / 2);
@@ -1020,11 +1049,11 @@ struct ftcf_gptneox {
                     // on a path that is bound by the latency of dependent launches.  Here attn | ffn (adjacent in the arena) travel
                     // as one message of twice the size and the residual -- x + attn + ffn + TP x (bias / TP) in fp32, rounded once
                     // -- runs inside the next layer's LayerNorm pass, as at TP = 1: two launches (FTCF_TP_PAIR_AR=0: the former).
-                    allreduce(att, (size_t)2 * B * H);
+                    allreduce(att, (size_t)2 * B * H, nullptr, true);
                     const LayerWeights* nx = l + 1 < L ? &layers[l + 1] : nullptr;
                     launch_residual_dual_ln(x, ffn, att, w.ffn2.bias, 1, 1, nx ? nx->ln1_g : nullptr, nx ? nx->ln1_b : nullptr,
                                             nx ? nx->ln2_g : nullptr, nx ? nx->ln2_b : nullptr, nrm, nrm2, B, H, 1e-5f, stream,
-                                            cfg.tensor_para_size);
+                                            cfg.tensor_para_size, fake_peers_mul());
                     continue;
                 }
                 if (dual && tp1) {
@@ -1150,7 +1179,7 @@ struct ftcf_gptneox {
                 }
                 FTCF_HIP_CHECK(hipEventRecord(dv_done[c], st));
                 FTCF_HIP_CHECK(hipStreamWaitEvent(side, dv_done[c], 0));
-                allreduce(tp_pair_ar ? attc : xr, (size_t)(tp_pair_ar ? 2 : 1) * M * H, side);
+                allreduce(tp_pair_ar ? attc : xr, (size_t)(tp_pair_ar ? 2 : 1) * M * H, side, tp_pair_ar);
                 FTCF_HIP_CHECK(hipEventRecord(dv_red[c], side));
                 if (tp_pair_ar) {
                     // the layer's residual inside the next layer's LayerNorm pass, behind the reduction (general loop below)
@@ -1158,7 +1187,7 @@ struct ftcf_gptneox {
                     FTCF_HIP_CHECK(hipStreamWaitEvent(st, dv_red[c], 0));
                     launch_residual_dual_ln(xr, ffnc, attc, w.ffn2.bias, 1, 1, nx ? nx->ln1_g : nullptr, nx ? nx->ln1_b : nullptr,
                                             nx ? nx->ln2_g : nullptr, nx ? nx->ln2_b : nullptr, nrm + o * H, nrm2 + o * H, M, H, 1e-5f,
-                                            st, cfg.tensor_para_size);
+                                            st, cfg.tensor_para_size, fake_peers_mul());
                 }
             }
         }

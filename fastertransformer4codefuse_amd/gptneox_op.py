@@ -54,8 +54,9 @@ def init_tensor_parallel_comm(group, rank, world_size, device):
         # two PROCESSES share one device, i.e. the inter-process path of the in-kernel all-reduce run on a single-GPU box.
         return _HostExchangeComm(group, rank, world_size, device).handle
     if os.environ.get("FTCF_FAKE_TP") == "1":
-        # timing aid (bench.py --fake-tp N): ONE process runs rank 0's shard of a TP=N model over a 1-rank communicator --
-        # the kernels and collectives of a rank are all launched, only the peers are missing (outputs are meaningless)
+        # fake peers (bench.py --fake-tp N): ONE process runs one rank's shard of a TP=N model over a 1-rank communicator --
+        # the kernels of a rank are all launched and the rank plays its own peers: outputs are those of a TP = N job whose
+        # every rank holds shard `rank` (an all-reduce is TP x the rank's partial, the gathered logits TP copies of its slice)
         capi.check(capi.lib().ftcf_comm_get_unique_id(ids.ctypes.data_as(C.POINTER(C.c_uint8))))
         comm = C.c_void_p()
         capi.check(capi.lib().ftcf_comm_init(ids.ctypes.data_as(C.POINTER(C.c_uint8)), 1, 0, device, C.byref(comm)))

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.gpu_helpers import _close, _run, _shard
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -29,15 +31,6 @@ def _op(full):
     a, weights, int8_w, scales = full
     return GptNeoXOp(None, 0, a.heads, a.head_dim, a.inter, a.layers, a.vocab, a.rotary, 0, 2, 1, 1, 1, 2048, True, weights,
                      int8_w, scales)
-
-
-def _run(op, ids, out, V):
-    B, S = ids.shape
-    lens = torch.full((B,), S, dtype=torch.int32, device="cuda")
-    dbg = torch.zeros((out, B, V), dtype=torch.float32, device="cuda")
-    o = op.forward(ids, lens, out, 1, torch.tensor([1], dtype=torch.int32), _debug_logits=dbg)
-    torch.cuda.synchronize()
-    return o[0][:, 0].cpu().numpy(), dbg.cpu().numpy()
 
 
 def test_full_size_properties(full, monkeypatch):
@@ -328,33 +321,6 @@ def test_13b_layer_shape_against_oracle(dtype, monkeypatch):
 # they hold exact shards of the TP = 1 model above (column / row slices of its tiled int8 images, the same scales), so the
 # TP engines must reproduce the TP = 1 engine up to the summation order of the row-split GEMMs.
 # ---------------------------------------------------------------------------------------------------------------------
-def _shard(full, tp, r):
-    a, weights, int8_w, scales = full
-    L, H, I = a.layers, a.heads * a.head_dim, a.inter
-    hl, il = H // tp, I // tp
-
-    def cols(t, N, lo, hi):  # tiled [N/16][K/64][1 KiB]: a column range is a range of the first axis
-        return t.view(N // 16, -1)[lo // 16:hi // 16]
-
-    def rows(t, N, K, lo, hi):  # a k range is a range of the second axis
-        return t.view(N // 16, K // 64, 1024)[:, lo // 64:hi // 64, :].contiguous().view(-1)
-
-    w = list(weights)
-    q8, sc = list(int8_w), list(scales)
-    for l in range(L):
-        w[3 * L + l] = torch.cat([weights[3 * L + l].view(3, H)[p, r * hl:(r + 1) * hl] for p in range(3)]).contiguous()
-        w[7 * L + l] = weights[7 * L + l][r * il:(r + 1) * il].contiguous()
-        w[9 * L + l] = (weights[9 * L + l].float() / tp).half()  # row-split GEMM biases are divided by TP (the converter)
-        q8[0 * L + l] = torch.cat([cols(int8_w[l], 3 * H, p * H + r * hl, p * H + (r + 1) * hl) for p in range(3)]
-                                  ).contiguous().view(-1)
-        sc[0 * L + l] = torch.cat([scales[l].view(3, H)[p, r * hl:(r + 1) * hl] for p in range(3)]).contiguous()
-        q8[1 * L + l] = rows(int8_w[L + l], H, H, r * hl, (r + 1) * hl)
-        q8[2 * L + l] = cols(int8_w[2 * L + l], I, r * il, (r + 1) * il).contiguous().view(-1)
-        sc[2 * L + l] = scales[2 * L + l][r * il:(r + 1) * il].contiguous()
-        q8[3 * L + l] = rows(int8_w[3 * L + l], H, I, r * il, (r + 1) * il)
-    return w, q8, sc
-
-
 def _run_tp(full, tp, ids, out, persist):
     import threading
     from fastertransformer4codefuse_amd.gptneox_op import GptNeoXOp, LocalTensorParallelGroup
@@ -387,18 +353,6 @@ def _run_tp(full, tp, ids, out, persist):
     return res
 
 
-def _close(ref_t, ref_l, t, l, S, frac, what):
-    scale = np.abs(ref_l).max()
-    for b in range(ref_t.shape[0]):
-        for s in range(ref_l.shape[0]):
-            e = np.abs(l[s, b] - ref_l[s, b]).max() / scale
-            assert e <= frac, (what, b, s, e)
-            if t[b, S + s] != ref_t[b, S + s]:
-                top2 = np.sort(ref_l[s, b])[-2:]
-                assert top2[1] - top2[0] <= 2 * frac * scale, (what, b, s, "token flip without a near tie")
-                break
-
-
 @pytest.mark.timeout(1800)
 @pytest.mark.parametrize("tp", [2, 4, 8])
 def test_full_size_tensor_parallel_one_row(full, tp):
@@ -412,8 +366,8 @@ def test_full_size_tensor_parallel_one_row(full, tp):
     for persist in (True, False):
         res = _run_tp(full, tp, ids, out, persist)
         # (the emulation gives a rank CUs / TP workgroups: at TP = 8 a rank's 32 workgroups cannot hold the 13B shard's
-        # run tables and the plan falls to the per-stage launches -- on 8 GPUs every rank has all 256; `bench.py --fake-tp 8`
-        # runs that kernel shape)
+        # run tables and the plan falls to the per-stage launches -- on 8 GPUs every rank has all 256; that kernel shape is
+        # checked against a TP = 1 reference in test_gpu_tp_product_grid.py)
         assert res[0][2] == (1 if persist and tp <= 4 else 0), res[0][2]
         for r in range(1, tp):  # every rank ends with the same tokens and bit-identical gathered logits
             assert np.array_equal(res[r][0], res[0][0]) and np.array_equal(res[r][1], res[0][1])
