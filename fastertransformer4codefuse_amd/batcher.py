@@ -5,6 +5,7 @@
     rid = cb.submit(prompt_ids, max_new_tokens=128)          # greedy; top_k / top_p / temperature / seed /
                                                              # repetition_penalty / stop_words optional
     bid = cb.submit_beam(prompt_ids, 128, beam_width=4)      # beam search: one event (bid, -1, True), then cb.beam_result(bid)
+    ContinuousBatcher(op, ..., prefix_cache=True)             # reuse the K/V pages of shared prompt prefixes (prefix_stats())
     while cb.busy():
         for request_id, token, finished in cb.step():
             ...
@@ -18,12 +19,18 @@ from . import capi
 
 
 class ContinuousBatcher:
-    def __init__(self, op, max_batch, page_tokens, num_pages, max_seq_len):
+    def __init__(self, op, max_batch, page_tokens, num_pages, max_seq_len, prefix_cache=False):
+        """prefix_cache=True: full prompt blocks of page_tokens tokens stay cached in the pool and later prompts that start with
+        them reuse their K/V (ftcf_batcher_create_ex); refused for tensor_para_size > 1 and fp32 engines."""
         self._op = op  # keeps the engine (and its weights) alive
         self.max_batch = int(max_batch)
         self._h = C.c_void_p()
-        capi.check(capi.lib().ftcf_batcher_create(op._h, int(max_batch), int(page_tokens), int(num_pages), int(max_seq_len),
-                                                  C.byref(self._h)))
+        if prefix_cache:
+            capi.check(capi.lib().ftcf_batcher_create_ex(op._h, int(max_batch), int(page_tokens), int(num_pages), int(max_seq_len), 1,
+                                                         C.byref(self._h)))
+        else:
+            capi.check(capi.lib().ftcf_batcher_create(op._h, int(max_batch), int(page_tokens), int(num_pages), int(max_seq_len),
+                                                      C.byref(self._h)))
         n = 2 * self.max_batch  # (a chunked admission can produce more events per iteration: the rest comes with the next call)
         self._ids = (C.c_long * n)()
         self._tok = (C.c_int * n)()
@@ -115,6 +122,20 @@ class ContinuousBatcher:
         w, r, f = C.c_int(0), C.c_int(0), C.c_int(0)
         capi.check(capi.lib().ftcf_batcher_status(self._h, C.byref(w), C.byref(r), C.byref(f)))
         return {"waiting": w.value, "running": r.value, "free_pages": f.value}
+
+    def prefix_stats(self):
+        """Counters of the prefix cache: enabled, cached_pages, evictable_pages, lookups, prompt_tokens, hit_tokens, computed_tokens,
+        evictions (all 0 without the cache)."""
+        en, cached, evictable = C.c_int(0), C.c_int(0), C.c_int(0)
+        lk, pt, ht, ct, ev = C.c_long(0), C.c_long(0), C.c_long(0), C.c_long(0), C.c_long(0)
+        capi.check(capi.lib().ftcf_batcher_prefix_stats(self._h, C.byref(en), C.byref(cached), C.byref(evictable), C.byref(lk),
+                                                        C.byref(pt), C.byref(ht), C.byref(ct), C.byref(ev)))
+        return {"enabled": en.value, "cached_pages": cached.value, "evictable_pages": evictable.value, "lookups": lk.value,
+                "prompt_tokens": pt.value, "hit_tokens": ht.value, "computed_tokens": ct.value, "evictions": ev.value}
+
+    def clear_prefix_cache(self):
+        """Drops every cached page that no request is using (they return to the free list)."""
+        capi.check(capi.lib().ftcf_batcher_clear_prefix_cache(self._h))
 
     def cancel(self, request_id):
         """Drops a waiting or running request; returns False when the id is unknown or already finished."""

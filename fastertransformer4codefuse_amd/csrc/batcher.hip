@@ -1,6 +1,7 @@
 // Continuous batching over a paged K/V cache (include/ftcf.h `ftcf_batcher_*`): split out of engine.hip in round 4.
 #include "engine.hip.h"
 #include "attn_device.hip.h"  // rotary_coef (the rows kernel's rotary table of a step)
+#include "prefix_index.h"
 
 #include <chrono>
 #include <set>
@@ -23,6 +24,10 @@
 // when it emits end_id or reaches max_new_tokens; its pages return to the free list at once.
 // Scope: parallel-residual models, any tensor_para_size (round 4: one batcher per rank), fp16 / int8 engines; top-k / top-p /
 // temperature sampling with repetition penalty, stop words and a token callback; beam search (round 4: BeamGroup below).
+// Prefix cache (ftcf_batcher_create_ex, off by default): the pages of finished prompt blocks stay in a PrefixIndex
+// (prefix_index.h); a request whose prompt starts with cached blocks takes those pages, k_gather_pages_to_kv copies them into
+// the engine's cache and the prompt phase runs from the first uncached token (context_decoder_chunked with prefill_begin).
+// Beam requests neither read nor populate it.
 // ---------------------------------------------------------------------------------------------------------------
 __global__ void k_batcher_embed(f16* out, const f16* table, const int* tok, int H)
 {
@@ -196,6 +201,12 @@ struct ftcf_batcher {
     std::vector<Slot>   slots;
     std::deque<Request> waiting;
     std::vector<int>    free_pages;
+    // prefix cache: the index holds one reference to each of its pages; `deferred` = slots of an admission whose
+    // request finished with its first token, released only after the admission's prompts have been inserted
+    bool             prefix_on = false;
+    PrefixIndex      pindex;
+    std::vector<int> deferred;
+    long             px_lookups = 0, px_prompt_tokens = 0, px_hit_tokens = 0, px_computed_tokens = 0, px_evictions = 0;
     long                next_id = 1;
     int                 max_prompt = 0;
 
@@ -217,9 +228,14 @@ struct ftcf_batcher {
         }
     }
 
-    void init(ftcf_gptneox* eng, int mb, int page_tokens, int pages, int max_seq_len)
+    void init(ftcf_gptneox* eng, int mb, int page_tokens, int pages, int max_seq_len, bool prefix_cache = false)
     {
         e = eng;
+        FTCF_CHECK_ARG(!prefix_cache
+                           || ftcf_gptneox::chunked_supported(e->fp32, e->cfg.tensor_para_size, e->cfg.use_gptj_residual, e->H),
+                       "the prefix cache needs an fp16 / int8 engine with tensor_para_size 1, parallel residual and a hidden size "
+                       "with the dual LayerNorm (a prompt phase from a token offset)");
+        prefix_on = prefix_cache;
         FTCF_CHECK_ARG(!e->fp32 && e->cfg.use_gptj_residual && (e->dh == 64 || e->dh == 128),
                        "the batcher serves fp16 / int8 engines with parallel residual and size_per_head 64 / 128");
         FTCF_CHECK_ARG(mb >= 1 && mb <= 64 && page_tokens >= 8 && pages >= 1 && max_seq_len >= 2, "bad batcher geometry");
@@ -349,9 +365,17 @@ struct ftcf_batcher {
             free_pages[i] = num_pages - 1 - i;
         }
         page_ref.assign(num_pages, 0);
+        pindex = PrefixIndex(P);
     }
     int take_page()
     {
+        if (free_pages.empty() && prefix_on) {  // a cached page only the index holds makes room (LRU, leaves first)
+            const int pg = pindex.evict_one(page_ref);
+            if (pg >= 0) {
+                px_evictions++;
+                drop_page(pg);
+            }
+        }
         if (free_pages.empty()) {
             throw Error(-2, "batcher: the page pool is exhausted (a reservation was wrong)");
         }
@@ -511,9 +535,11 @@ struct ftcf_batcher {
     }
 
     // prompts -> ONE ragged batch through the engine's context path (+ first tokens) -> pages of their slots
-    void admit(const std::vector<int>& sis, const std::vector<Request>& rs, std::vector<Event>& ev)
+    // hit (one request only): the cached pages of its first prompt blocks (pinned here: the slot's page list owns one reference)
+    void admit(const std::vector<int>& sis, const std::vector<Request>& rs, std::vector<Event>& ev, const std::vector<int>* hit = nullptr)
     {
         Range        rg("ftcf.batcher.admit");
+        deferred.clear();
         hipStream_t  st = e->stream;
         const int    n  = (int)sis.size();
         int          S  = 0;
@@ -549,7 +575,15 @@ struct ftcf_batcher {
             Slot&     s = slots[sis[i]];
             const int need = (lens[i] + r.max_new + P - 1) / P;
             s.pages.clear();
-            for (int k = 0; k < need; k++) {
+            if (hit) {
+                FTCF_CHECK_ARG(n == 1, "batcher: a prefix hit is admitted alone");
+                s.pages = *hit;
+                for (const int pg : *hit) {
+                    page_ref[pg]++;
+                }
+                pindex.touch(r.prompt.data(), (int)hit->size());
+            }
+            for (int k = (int)s.pages.size(); k < need; k++) {
                 s.pages.push_back(take_page());
             }
         }
@@ -579,7 +613,33 @@ struct ftcf_batcher {
         a.n_random_seed = n;
         a.output_ids = d_pout;
         a.sequence_lengths = d_pseq;
-        e->forward(a);  // host synchronous: K/V of row i, positions [0, len_i), are in the engine's cache [L][n][nh][S + 1][dh]
+        const int hit_tokens = hit ? (int)hit->size() * P : 0;
+        if (hit_tokens > 0) {
+            // the prompt phase starts at the first uncached token; first the cached pages go to cache row 0 (the engine's cache
+            // exists only inside forward(): the gather is its prefill_prefix hook)
+            const int        si = sis[0];
+            std::vector<int> row(max_pages, 0);
+            std::copy(slots[si].pages.begin(), slots[si].pages.end(), row.begin());
+            FTCF_HIP_CHECK(hipMemcpy(d_pt + (size_t)si * max_pages, row.data(), (size_t)max_pages * 4, hipMemcpyHostToDevice));
+            e->prefill_begin  = hit_tokens;
+            e->prefill_prefix = [this, si, S, hit_tokens] {
+                launch_gather_pages_to_kv(e->k_cache, e->v_cache, kpool, vpool, d_pt + (size_t)si * max_pages, e->L, e->nhl, e->dh, S + 1,
+                                          hit_tokens, P, pool_layer_elems, e->stream);
+            };
+            try {
+                e->forward(a);
+            }
+            catch (...) {
+                e->prefill_begin  = 0;
+                e->prefill_prefix = nullptr;
+                throw;
+            }
+            e->prefill_begin  = 0;
+            e->prefill_prefix = nullptr;
+        }
+        else {
+            e->forward(a);  // host synchronous: K/V of row i, positions [0, len_i), are in the engine's cache [L][n][nh][S + 1][dh]
+        }
         std::vector<int> out((size_t)n * (S + 1));
         FTCF_HIP_CHECK(hipMemcpy(out.data(), d_pout, out.size() * 4, hipMemcpyDeviceToHost));
         const size_t row_kv = (size_t)e->nhl * (S + 1) * e->dh;  // one row of one layer of the engine's cache
@@ -592,9 +652,11 @@ struct ftcf_batcher {
             std::vector<int> row(max_pages, 0);
             std::copy(s.pages.begin(), s.pages.end(), row.begin());
             FTCF_HIP_CHECK(hipMemcpyAsync(d_pt + (size_t)si * max_pages, row.data(), (size_t)max_pages * 4, hipMemcpyHostToDevice, st));
-            launch_scatter_kv_to_pages(e->k_cache + (size_t)i * row_kv, e->v_cache + (size_t)i * row_kv, kpool, vpool,
-                                       d_pt + (size_t)si * max_pages, e->L, e->nhl, e->dh, S + 1, len, P, pool_layer_elems, st,
-                                       (size_t)n * row_kv);
+            // (a hit: only the tail's pages; the cached ones are immutable)
+            launch_scatter_kv_to_pages(e->k_cache + (size_t)i * row_kv + (size_t)hit_tokens * e->dh,
+                                       e->v_cache + (size_t)i * row_kv + (size_t)hit_tokens * e->dh, kpool, vpool,
+                                       d_pt + (size_t)si * max_pages + hit_tokens / P, e->L, e->nhl, e->dh, S + 1, len - hit_tokens, P,
+                                       pool_layer_elems, st, (size_t)n * row_kv);
             // per-slot state of the decode steps
             const int      keff = (r.top_k == 0 && r.top_p == 0.f) ? 1 : std::min(r.top_k, 1024);  // BaseSamplingLayer: (0, 0) = greedy
             const float    ptk = (r.top_p == 0.f) ? 1.f : r.top_p;
@@ -630,8 +692,40 @@ struct ftcf_batcher {
             if (done) {
                 const uint8_t one8 = 1;
                 FTCF_HIP_CHECK(hipMemcpy(d_fin + si, &one8, 1, hipMemcpyHostToDevice));
-                release(s);
+                if (prefix_on) {
+                    deferred.push_back(si);  // (its prompt pages are inserted first: commit())
+                }
+                else {
+                    release(s);
+                }
             }
+        }
+    }
+    // a successful admission of ordinary requests: their full prompt blocks enter the index (first writer wins), then the slots
+    // whose request ended with its first token are released
+    void commit(const std::vector<int>& sis, const std::vector<Request>& rs, int hit_tokens = 0)
+    {
+        if (!prefix_on) {
+            return;
+        }
+        for (size_t i = 0; i < sis.size(); i++) {
+            const Request& r = rs[i];
+            const int      S = (int)r.prompt.size();
+            pindex.insert(r.prompt.data(), S / P, slots[sis[i]].pages, page_ref);
+            px_lookups++;
+            px_prompt_tokens += S;
+            px_hit_tokens += hit_tokens;
+            px_computed_tokens += S - hit_tokens;
+        }
+        for (const int si : deferred) {
+            release(slots[si]);
+        }
+        deferred.clear();
+    }
+    void clear_prefix_cache()
+    {
+        for (int pg; (pg = pindex.evict_one(page_ref)) >= 0;) {
+            drop_page(pg);
         }
     }
 
@@ -1360,7 +1454,9 @@ struct ftcf_batcher {
         // admissions: as many of the queue's head requests as there are free slots and pages, prefilled as ONE ragged batch
         std::vector<int>     sis;
         std::vector<Request> rs;
-        int                  pages_left = (int)free_pages.size() - reserved_pages();
+        // (prefix cache: the cached pages nobody else holds count as free -- take_page evicts them when the free list runs dry)
+        int                  pages_left = (int)free_pages.size() - reserved_pages() + (prefix_on ? pindex.evictable(page_ref) : 0);
+        std::vector<int>     hit;  // a request with a prefix hit: its cached pages (it is admitted alone)
         if (!waiting.empty() && waiting.front().beam_width > 1) {
             // a beam request at the head of the queue: K consecutive free slots and the group's whole page budget, admitted alone
             const Request& r    = waiting.front();
@@ -1432,7 +1528,37 @@ struct ftcf_batcher {
             if (r.beam_width > 1) {
                 break;  // (admitted alone, by the next iteration)
             }
-            const int      need = ((int)r.prompt.size() + r.max_new + P - 1) / P;
+            int            need = ((int)r.prompt.size() + r.max_new + P - 1) / P;
+            if (prefix_on) {
+                // at most floor((S - 1) / P) blocks: the last prompt token is always computed (its logits give the first token)
+                // and decode never writes into a cached page
+                std::vector<int> h = pindex.lookup(r.prompt.data(), ((int)r.prompt.size() - 1) / P);
+                if (!h.empty()) {
+                    if (!sis.empty()) {
+                        break;  // (admitted alone, by the next iteration)
+                    }
+                    // the budget without the pages this hit pins: they are in use, not evictable
+                    for (const int pg : h) {
+                        page_ref[pg]++;
+                    }
+                    const int avail = (int)free_pages.size() - reserved_pages() + pindex.evictable(page_ref);
+                    for (const int pg : h) {
+                        page_ref[pg]--;
+                    }
+                    need -= (int)h.size();
+                    if (avail < need) {
+                        break;
+                    }
+                    const int keff = (r.top_k == 0 && r.top_p == 0.f) ? 1 : std::min(r.top_k, 1024);
+                    slot_topk[si]  = keff;
+                    slot_temp[si]  = r.temperature;
+                    sis.push_back(si);
+                    rs.push_back(std::move(waiting.front()));
+                    waiting.pop_front();
+                    hit = std::move(h);
+                    break;
+                }
+            }
             if (pages_left < need) {
                 break;  // FIFO: nobody overtakes the head of the queue
             }
@@ -1443,6 +1569,50 @@ struct ftcf_batcher {
             sis.push_back(si);
             rs.push_back(std::move(waiting.front()));
             waiting.pop_front();
+        }
+        if (!hit.empty()) {
+            // a prefix hit, alone: the tail's prompt phase from the hit offset, in chunks with decode steps of the running slots
+            // between them when it is long (as a chunked admission below)
+            const int          hit_tokens = (int)hit.size() * P;
+            std::vector<Event> own, between;
+            try {
+                if (any && prefill_chunk > 0 && (int)rs[0].prompt.size() - hit_tokens > prefill_chunk) {
+                    hook_ev          = &between;
+                    e->prefill_chunk = prefill_chunk;
+                    e->prefill_hook  = [this] {
+                        bool live = false;
+                        for (const Slot& s : slots) {
+                            live |= s.active;
+                        }
+                        if (live) {
+                            refresh_host_flags();
+                            decode(*hook_ev);
+                        }
+                    };
+                }
+                admit(sis, rs, own, &hit);
+                e->prefill_hook = nullptr;
+                hook_ev         = nullptr;
+            }
+            catch (...) {
+                // the hit's references go with the slot's page list; nothing is inserted
+                e->prefill_hook = nullptr;
+                hook_ev         = nullptr;
+                (void)hipDeviceSynchronize();
+                (void)hipGetLastError();
+                ev.insert(ev.end(), between.begin(), between.end());
+                release(slots[sis[0]]);
+                const uint8_t one8 = 1;
+                (void)hipMemcpy(d_fin + sis[0], &one8, 1, hipMemcpyHostToDevice);
+                waiting.push_front(std::move(rs[0]));
+                throw;
+            }
+            commit(sis, rs, hit_tokens);
+            ev.insert(ev.end(), between.begin(), between.end());
+            ev.insert(ev.end(), own.begin(), own.end());
+            fire(own, 0);
+            refresh_host_flags();
+            return;
         }
         bool any_long = false;
         for (const Request& r : rs) {
@@ -1494,6 +1664,7 @@ struct ftcf_batcher {
                     }
                     throw;
                 }
+                commit(one_si, one_r);
                 ev.insert(ev.end(), between.begin(), between.end());
                 ev.insert(ev.end(), own.begin(), own.end());
                 fire(own, 0);
@@ -1522,6 +1693,7 @@ struct ftcf_batcher {
                 ev.resize(ev0);
                 throw;
             }
+            commit(sis, rs);
             fire(ev, ev0);
         }
         refresh_host_flags();
@@ -1554,6 +1726,55 @@ extern "C" int ftcf_batcher_create(ftcf_gptneox_t engine, int max_batch, int pag
         auto b = std::make_unique<ftcf_batcher>();
         b->init(engine, max_batch, page_tokens, num_pages, max_seq_len);
         *out = b.release();
+    });
+}
+extern "C" int ftcf_batcher_create_ex(ftcf_gptneox_t engine, int max_batch, int page_tokens, int num_pages, int max_seq_len,
+                                      int prefix_cache, ftcf_batcher_t* out)
+{
+    return guarded([&] {
+        FTCF_CHECK_ARG(engine && out, "NULL argument");
+        require_device();
+        auto b = std::make_unique<ftcf_batcher>();
+        b->init(engine, max_batch, page_tokens, num_pages, max_seq_len, prefix_cache != 0);
+        *out = b.release();
+    });
+}
+extern "C" int ftcf_batcher_prefix_stats(ftcf_batcher_t b, int* enabled, int* cached_pages, int* evictable_pages, long* lookups,
+                                         long* prompt_tokens, long* hit_tokens, long* computed_tokens, long* evictions)
+{
+    return guarded([&] {
+        FTCF_CHECK_ARG(b, "NULL argument");
+        if (enabled) {
+            *enabled = b->prefix_on ? 1 : 0;
+        }
+        if (cached_pages) {
+            *cached_pages = b->pindex.n_cached;
+        }
+        if (evictable_pages) {
+            *evictable_pages = b->pindex.evictable(b->page_ref);
+        }
+        if (lookups) {
+            *lookups = b->px_lookups;
+        }
+        if (prompt_tokens) {
+            *prompt_tokens = b->px_prompt_tokens;
+        }
+        if (hit_tokens) {
+            *hit_tokens = b->px_hit_tokens;
+        }
+        if (computed_tokens) {
+            *computed_tokens = b->px_computed_tokens;
+        }
+        if (evictions) {
+            *evictions = b->px_evictions;
+        }
+    });
+}
+extern "C" int ftcf_batcher_clear_prefix_cache(ftcf_batcher_t b)
+{
+    return guarded([&] {
+        FTCF_CHECK_ARG(b, "NULL argument");
+        b->clear_prefix_cache();
     });
 }
 extern "C" int ftcf_batcher_submit(ftcf_batcher_t b, const int* prompt_ids, int prompt_len, int max_new_tokens, int top_k,

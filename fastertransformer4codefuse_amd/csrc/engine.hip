@@ -284,6 +284,8 @@ void ftcf_gptneox::begin(const ftcf_forward_args& a)
     FTCF_CHECK_ARG(a.input_ids && a.input_lengths && a.output_ids && a.sequence_lengths, "NULL tensor");
     const int K = a.beam_width, batch = a.batch_size;
     FTCF_CHECK_ARG(K >= 1 && K <= BEAM_MAX_K, "beam_width must be in [1, 64]");
+    FTCF_CHECK_ARG(prefill_begin == 0 || (!fp32 && K == 1 && batch == 1 && prefill_begin < S),
+                   "a prompt phase from a token offset needs one fp16 / int8 sequence without beams, longer than the offset");
     FTCF_HIP_CHECK(hipSetDevice(cfg.device));
     abandon_session();  // (a request left open -- begin / step without finish, or a step that threw -- must not leak its graph)
     stats.window_allreduces = 0;

@@ -610,19 +610,35 @@ struct ftcf_gptneox {
     // of its running slots there: an admission delays them by one chunk, not by the whole prompt).  The row-wise arithmetic is
     // that of context_decoder; the split-K form of the GEMMs depends on the row count, so results agree to fp16 rounding of
     // the GEMM outputs, not bit for bit.
+    // The same from token `prefill_begin` on (the batcher's prefix cache): `prefill_prefix` runs first and puts the K/V of tokens
+    // [0, prefill_begin) into cache row 0, the prompt phase computes the tail only -- in one piece without a hook, in chunks of
+    // `prefill_chunk` with one.  The batcher sets these members before the request and resets them after it.
     int                   prefill_chunk = 0;
     std::function<void()> prefill_hook;
+    int                   prefill_begin = 0;
+    std::function<void()> prefill_prefix;
+    static bool chunked_supported(bool fp32_, int tp, bool gptj, int H_) { return !fp32_ && tp == 1 && gptj && residual_dual_ln_supported(H_); }
     bool context_decoder_chunked(int S, const int* input_lengths, int s_max, int tile = 1)
     {
-        if (!prefill_hook || prefill_chunk <= 0 || S <= prefill_chunk || fp32 || cfg.tensor_para_size != 1 || !cfg.use_gptj_residual
-            || !residual_dual_ln_supported(H)) {
+        const int sb = prefill_begin;
+        if (sb > 0) {
+            FTCF_CHECK_ARG(chunked_supported(fp32, cfg.tensor_para_size, cfg.use_gptj_residual, H) && tile == 1 && sb < S,
+                           "a prompt phase from a token offset needs one sequence, no beams, tensor_para_size 1, parallel residual "
+                           "and the dual LayerNorm");
+        }
+        else if (!prefill_hook || prefill_chunk <= 0 || S <= prefill_chunk
+                 || !chunked_supported(fp32, cfg.tensor_para_size, cfg.use_gptj_residual, H)) {
             return false;
         }
         Range r("ftcf.GptNeoXContextDecoder.chunked");
         bind_layers();
         const size_t cache_l = (size_t)tile * nhl * s_max * dh;  // (tile = beam_width: the sequence's K/V go to cache row 0 of tile rows)
-        for (int s0 = 0; s0 < S; s0 += prefill_chunk) {
-            const int s1 = std::min(S, s0 + prefill_chunk), m = s1 - s0;
+        const int    chunk   = (prefill_hook && prefill_chunk > 0) ? prefill_chunk : S;
+        if (sb > 0 && prefill_prefix) {
+            prefill_prefix();
+        }
+        for (int s0 = sb; s0 < S; s0 += chunk) {
+            const int s1 = std::min(S, s0 + chunk), m = s1 - s0;
             f16*      X  = px + (size_t)s0 * H;
             for (int l = 0; l < L; l++) {
                 const LayerWeights& w = layers[l];
@@ -733,6 +749,7 @@ struct ftcf_gptneox {
         if (B == 1 && context_decoder_chunked(S, input_lengths, s_max, tile)) {  // (tile > 1: a beam request's prompt)
             return;
         }
+        FTCF_CHECK_ARG(prefill_begin == 0, "a prompt phase from a token offset needs a batch of one sequence");
         if (tile == 1 && context_decoder_overlapped(B, S, input_lengths, s_max)) {
             return;
         }

@@ -812,4 +812,44 @@ void launch_scatter_kv_to_pages(const f16* kc, const f16* vc, f16* kpool, f16* v
     FTCF_HIP_CHECK(hipGetLastError());
 }
 
+
+// the exact inverse of k_scatter_kv_to_pages (the batcher's prefix cache): tokens [0, T) of a sequence, T a
+// multiple of P, from its pages of every layer -> one row of the engine cache [L][rows][nh][s_max][dh] (kc / vc point at the
+// row in layer 0), where the prompt phase reads the K/V of earlier tokens.  One 16-byte piece of K and one of V per thread
+// and iteration; a bit-exact copy.
+__global__ void k_gather_pages_to_kv(f16* __restrict__ kc, f16* __restrict__ vc, const f16* __restrict__ kpool,
+                                     const f16* __restrict__ vpool, const int* __restrict__ pages, int nh, int dh, int s_max, int T,
+                                     int P, size_t pool_layer_elems, size_t dst_layer_elems, size_t total)
+{
+    const int ppr = dh / 8;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int pc = (int)(i % ppr);
+        size_t    r  = i / ppr;
+        const int t  = (int)(r % T);
+        r /= T;
+        const int    h = (int)(r % nh), l = (int)(r / nh);
+        const size_t src = (size_t)l * pool_layer_elems + ((size_t)pages[t / P] * nh + h) * P * dh + (size_t)(t % P) * dh + pc * 8;
+        const size_t dst = (size_t)l * dst_layer_elems + ((size_t)h * s_max + t) * dh + pc * 8;
+        *reinterpret_cast<u32x4*>(kc + dst) = *reinterpret_cast<const u32x4*>(kpool + src);
+        *reinterpret_cast<u32x4*>(vc + dst) = *reinterpret_cast<const u32x4*>(vpool + src);
+    }
+}
+void launch_gather_pages_to_kv(f16* kc, f16* vc, const f16* kpool, const f16* vpool, const int* pages, int L, int nh, int dh, int s_max,
+                               int T, int P, size_t pool_layer_elems, hipStream_t s, size_t dst_layer_elems)
+{
+    FTCF_CHECK_ARG(T >= 0 && T % P == 0 && T <= s_max && dh % 8 == 0, "gather_pages_to_kv: bad geometry");
+    if (dst_layer_elems == 0) {
+        dst_layer_elems = (size_t)nh * s_max * dh;  // a one-row cache
+    }
+    const size_t total = (size_t)L * nh * T * (dh / 8);
+    if (total == 0) {
+        return;
+    }
+    // grid-stride over the pieces: at most 16 workgroups of 256 threads per CU of the 256 (enough loads in flight to stream
+    // at HBM rate; a small prefix takes fewer)
+    hipLaunchKernelGGL(k_gather_pages_to_kv, dim3((unsigned)std::min<size_t>((total + 255) / 256, 256 * 16)), dim3(256), 0, s, kc, vc,
+                       kpool, vpool, pages, nh, dh, s_max, T, P, pool_layer_elems, dst_layer_elems, total);
+    FTCF_HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace ftcf

@@ -250,6 +250,24 @@ int ftcf_gptneox_destroy(ftcf_gptneox_t h);
 typedef struct ftcf_batcher* ftcf_batcher_t;
 int ftcf_batcher_create(ftcf_gptneox_t engine, int max_batch, int page_tokens, int num_pages, int max_seq_len,
                         ftcf_batcher_t* out);
+/* The same with a PREFIX CACHE (prefix_cache = 1; 0 is ftcf_batcher_create): the pages that hold a finished admission's full
+ * prompt blocks (page_tokens tokens each) stay cached, keyed by their tokens; a later request whose prompt starts with
+ * cached blocks reuses their K/V -- at most floor((prompt_len - 1) / page_tokens) of them, the last prompt token is always
+ * computed -- and its prompt phase computes only the rest.  Cached pages nobody uses are evicted, least recently used and
+ * leaves first, only when an allocation cannot be served from the free list; ftcf_batcher_status's free_pages counts the
+ * free list only.  Streams equal those of a cold admission up to fp16 rounding of the prompt phase (token exact unless a
+ * near tie).  Requests admitted in the same batch do not share with each other; beam requests neither read nor populate
+ * the cache.  Refused (an error, not a silent no-op) for tensor_para_size > 1, fp32 engines, sequential residual and
+ * hidden sizes without the dual LayerNorm. */
+int ftcf_batcher_create_ex(ftcf_gptneox_t engine, int max_batch, int page_tokens, int num_pages, int max_seq_len, int prefix_cache,
+                           ftcf_batcher_t* out);
+/* Prefix-cache counters (any pointer may be NULL): enabled, cached pages, cached pages eviction could free now, admissions
+ * looked up, their prompt tokens, the tokens served from the cache, the prompt tokens actually computed, pages evicted to make
+ * room.  A batcher without the cache reports enabled = 0 and zeros. */
+int ftcf_batcher_prefix_stats(ftcf_batcher_t b, int* enabled, int* cached_pages, int* evictable_pages, long* lookups,
+                              long* prompt_tokens, long* hit_tokens, long* computed_tokens, long* evictions);
+/* drops every cached page no request is using */
+int ftcf_batcher_clear_prefix_cache(ftcf_batcher_t b);
 /* prompt_ids: HOST array.  (top_k, top_p) = (0, 0) is greedy, as in the reference's sampling layer. */
 int ftcf_batcher_submit(ftcf_batcher_t b, const int* prompt_ids, int prompt_len, int max_new_tokens, int top_k, float top_p,
                         float temperature, unsigned long long seed, long* request_id);

@@ -1,6 +1,8 @@
 """Throughput of the continuous-batching front end on the CodeFuse-13B-shaped int8 model: N requests of `--prompt-len` tokens
 asking for `--new` tokens each, submitted at once to a batcher with `--slots` slots.  Prints one JSON line.  For comparison the
-static batch of the same shape through GptNeoXOp.forward (bench.py --batch N) decodes in lockstep from one prefill."""
+static batch of the same shape through GptNeoXOp.forward (bench.py --batch N) decodes in lockstep from one prefill.
+--shared-prefix P: N requests whose prompts share a P-token prefix and differ in a `--tail`-token private tail, run once with
+the batcher's prefix cache off and once on; reports time to first token and generated tokens/s of both."""
 import argparse
 import json
 import os
@@ -28,12 +30,18 @@ def main():
                     help="latency mode: `--slots` - 1 requests decode; after 10 iterations one request with a prompt of this many "
                          "tokens arrives; prints the longest gap between two tokens of a running request (token callback "
                          "timestamps) -- compare FTCF_BATCHER_PREFILL_CHUNK=0 (whole prompts) with the default 512")
+    ap.add_argument("--shared-prefix", type=int, default=0,
+                    help="prefix-cache mode: every prompt = one shared prefix of this many tokens + a private --tail; cache off vs on")
+    ap.add_argument("--tail", type=int, default=64)
     a = ap.parse_args()
     m = argparse.Namespace(layers=a.layers, heads=40, head_dim=128, inter=20480, vocab=100864, rotary=32, dtype="int8")
     dev = torch.device("cuda", 0)
     weights, int8_w, scales = bench.synth_weights(m, 1, dev)
     op = GptNeoXOp(None, 0, m.heads, m.head_dim, m.inter, m.layers, m.vocab, m.rotary, 0, 2, 1, 1, 1, 2048, True, weights,
                    int8_w, scales)
+    if a.shared_prefix:
+        shared_prefix(a, m, op)
+        return
     per_seq = (max(a.prompt_len, a.late_prompt) + a.new + a.page - 1) // a.page
     cb = ContinuousBatcher(op, a.slots, a.page, per_seq * a.slots, max(a.prompt_len, a.late_prompt) + a.new)
     rng = np.random.RandomState(0)
@@ -75,6 +83,52 @@ def main():
     print(json.dumps({"workload": f"13B-shaped int8 (L={a.layers}), {a.requests} requests x {a.prompt_len}-in / {a.new // 2}..{a.new}-out, "
                                   f"{a.slots} slots, {a.page}-token pages", "generated_tokens": toks, "seconds": round(dt, 3),
                       "tokens_per_sec": round(toks / dt, 1), "iterations": iters, "ms_per_iteration": round(dt / iters * 1e3, 3)}))
+
+
+def shared_prefix(a, m, op):
+    """One request with the prefix is served first (the system prompt a server has seen before), then the N requests arrive at
+    once; time to first token = submission -> the token callback's first event of the request."""
+    rng = np.random.RandomState(0)
+    prefix = rng.randint(3, m.vocab, size=a.shared_prefix).tolist()
+    reqs = [prefix + rng.randint(3, m.vocab, size=a.tail).tolist() for _ in range(a.requests)]
+    S = a.shared_prefix + a.tail
+    per_seq = (S + a.new + a.page - 1) // a.page
+    num_pages = per_seq * a.slots + 2 * (S // a.page) + 8
+    res = {"workload": f"13B-shaped int8 (L={a.layers}), {a.requests} requests x ({a.shared_prefix} shared + {a.tail} private)-in / "
+                       f"{a.new}-out, {a.slots} slots, {a.page}-token pages"}
+    for on in (False, True):
+        cb = ContinuousBatcher(op, a.slots, a.page, num_pages, S + a.new, prefix_cache=on)
+        stamps = {}
+        cb.set_token_callback(lambda rid, tok, fin: stamps.setdefault(rid, []).append(time.perf_counter()))
+        # warm-up: every kernel shape of both admission forms, and the prefix served once
+        cb.submit(prefix + rng.randint(3, m.vocab, size=a.tail).tolist(), 4)
+        cb.run_all()
+        cb.submit(reqs[0], 4)
+        cb.run_all()
+        # one request alone on an idle batcher: its time to first token is its admission
+        t = time.perf_counter()
+        one = cb.submit(reqs[1], 1)
+        cb.run_all()
+        single = stamps[one][0] - t
+        stamps.clear()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        sub = {cb.submit(p, a.new): time.perf_counter() for p in reqs}
+        toks = 0
+        while cb.busy():
+            toks += len(cb.step())
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        ttft = sorted((stamps[r][0] - ts) * 1e3 for r, ts in sub.items())
+        st = cb.prefix_stats()
+        res["cache_on" if on else "cache_off"] = {
+            "single_request_ttft_ms": round(single * 1e3, 2), "ttft_ms_median": round(ttft[len(ttft) // 2], 2),
+            "ttft_ms_p90": round(ttft[int(len(ttft) * 0.9)], 2), "ttft_ms_max": round(ttft[-1], 2), "generated_tokens": toks,
+            "seconds": round(dt, 3), "tokens_per_sec": round(toks / dt, 1), "hit_tokens": st["hit_tokens"],
+            "computed_tokens": st["computed_tokens"], "evictions": st["evictions"]}
+        cb.set_token_callback(None)
+        del cb
+    print(json.dumps(res))
 
 
 if __name__ == "__main__":
