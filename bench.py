@@ -3,6 +3,7 @@
 1024-token prompt + 512 generated tokens, tensor parallel over --gpus ranks (one process per GPU, RCCL).
 
   python bench.py --gpus 1 --steps 504 --warmup 8            # N = 1
+  python bench.py --gpus 1 --steps 504 --warmup 8 --full     # + end-to-end request, roofline, CPU baseline
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" is one decoded token (one pass of the per-token hot path: L decoder layers + LM head + dynamic decode).
@@ -10,8 +11,10 @@ The request is ALWAYS the headline one -- a 1024-token prompt prefilled through 
 in HBM) and --output-len (512) generated tokens -- whatever --steps / --warmup say: the K timed steps (preceded by W
 untimed ones) are a window of that request centred on output token 256, i.e. on the mean KV length 1280 of the whole
 request (K + W >= 512: the whole request is the window; K + W > --output-len lengthens the request to K + W tokens, so K is
-always the number of timed steps).  The steps before and after the window run untimed, then one complete
-ftcf_gptneox_forward of the same request gives the end-to-end latency.  --dump-outputs DIR writes what the measured
+always the number of timed steps).  The steps before and after the window run untimed.  That is all a plain run does
+besides one short warm-up request; --full adds the legs that the headline figure does not need: one complete
+ftcf_gptneox_forward of the same request (end-to-end latency), a profiled run of the window's KV lengths (roofline, with a
+rocprofv3 PMC child process at N = 1) and the whole-model CPU baseline.  --dump-outputs DIR writes what the measured
 request returned to its caller (output ids, sequence lengths, cumulative log-probs) as DIR/<name>.npy; the inputs are
 seeded, so two builds run with the same arguments can be compared output for output.  return_cum_log_probs = 1 as in the
 reference harness (codefuse_example.py:745).  Weights are synthetic (random int8 + fp16 scales of CodeFuse-13B's shape,
@@ -49,6 +52,9 @@ def parse():
     p.add_argument("--top-k", type=int, default=1, help="sampling top_k (1 = greedy, the headline; the reference harness "
                                                          "defaults to 50)")
     p.add_argument("--top-p", type=float, default=0.0, help="sampling top_p (with --top-k 0: the top-p layer)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the end-to-end request, the profiled roofline run and the CPU baseline (the four options "
+                        "below trim a --full run; a plain run does none of these)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-e2e", action="store_true")
     p.add_argument("--profile-steps", type=int, default=48)
@@ -62,6 +68,9 @@ def parse():
     a = p.parse_args()
     if a.steps < 1 or a.warmup < 0:
         p.error("--steps must be >= 1 and --warmup >= 0")
+    if not a.full:
+        a.no_cpu_baseline = a.no_e2e = a.no_pmc = True
+        a.profile_steps = 0
     return a
 
 

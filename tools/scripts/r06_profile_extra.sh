@@ -9,10 +9,10 @@ for own in 1 0; do
   grep -h persistent $O/pmc_sq_own$own.txt | cut -c1-400
 done
 for tp in 2 4; do
-  timeout 600 rocprofv3 --kernel-trace --stats -d $O/trace_tp$tp -o r -- python $R/bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-e2e --no-pmc --fake-tp $tp > /dev/null 2> $O/trace_tp$tp.err
+  timeout 600 rocprofv3 --kernel-trace --stats -d $O/trace_tp$tp -o r -- python $R/bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-e2e --no-pmc --fake-tp $tp > /dev/null 2> $O/trace_tp$tp.err
   python $R/tools/prof_summary.py $(find $O/trace_tp$tp -name "*results.db" | head -1) $O/kernel_stats_faketp$tp.txt | head -6
 done
-timeout 900 rocprofv3 --kernel-trace --stats -d $O/trace16 -o r -- python $R/bench.py --batch 16 --prompt-len 256 --output-len 128 --steps 40 --warmup 5 --no-cpu-baseline --no-e2e --no-pmc > /dev/null 2> $O/trace16.err
+timeout 900 rocprofv3 --kernel-trace --stats -d $O/trace16 -o r -- python $R/bench.py --full --batch 16 --prompt-len 256 --output-len 128 --steps 40 --warmup 5 --no-cpu-baseline --no-e2e --no-pmc > /dev/null 2> $O/trace16.err
 python $R/tools/prof_summary.py $(find $O/trace16 -name "*results.db" | head -1) $O/kernel_stats_bs16.txt | head -6
 find $O -name "*.db" -delete
 ls $O
