@@ -35,6 +35,7 @@ class ContinuousBatcher:
         self._ids = (C.c_long * n)()
         self._tok = (C.c_int * n)()
         self._fin = (C.c_int * n)()
+        self._lp = (C.c_float * n)()
         self._cb = None
 
     def __del__(self):
@@ -117,6 +118,15 @@ class ContinuousBatcher:
         n = C.c_int(0)
         capi.check(capi.lib().ftcf_batcher_step(self._h, self._ids, self._tok, self._fin, 2 * self.max_batch, C.byref(n)))
         return [(int(self._ids[i]), int(self._tok[i]), bool(self._fin[i])) for i in range(n.value)]
+
+    def step_ex(self):
+        """The same iteration with each token's log-probability: [(request_id, token, finished, log_prob), ...].  log_prob is
+        the value the token adds to the request's cumulative log-probability (the engine's output_log_probs), NaN for a beam
+        request's event."""
+        n = C.c_int(0)
+        capi.check(capi.lib().ftcf_batcher_step_ex(self._h, self._ids, self._tok, self._fin, self._lp, 2 * self.max_batch,
+                                                   C.byref(n)))
+        return [(int(self._ids[i]), int(self._tok[i]), bool(self._fin[i]), float(self._lp[i])) for i in range(n.value)]
 
     def status(self):
         w, r, f = C.c_int(0), C.c_int(0), C.c_int(0)

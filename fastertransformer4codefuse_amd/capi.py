@@ -52,7 +52,8 @@ class ForwardArgs(C.Structure):
         ("return_cum_log_probs", C.c_int),
         ("callback", TOKEN_CALLBACK), ("callback_user", C.c_void_p),
         ("output_ids", C.c_void_p), ("sequence_lengths", C.c_void_p), ("cum_log_probs", C.c_void_p),
-        ("debug_logits", C.c_void_p)]
+        ("debug_logits", C.c_void_p),
+        ("output_log_probs", C.c_void_p), ("context_log_probs", C.c_void_p)]
 
 
 class ForwardStats(C.Structure):
@@ -69,14 +70,14 @@ EXPORTED = [
     "ftcf_last_error", "ftcf_version", "ftcf_device_count", "ftcf_symmetric_quantize_int8",
     "ftcf_int8_rowmajor_to_tiled", "ftcf_int8_tiled_to_rowmajor", "ftcf_int8_cuda_sm80_to_rowmajor",
     "ftcf_int8_rowmajor_to_cuda_sm80", "ftcf_fp16_rowmajor_to_tiled",
-    "ftcf_fpA_intB_gemm", "ftcf_fp16_gemm", "ftcf_lm_head", "ftcf_layernorm", "ftcf_add_bias_attn_ffn_residual",
+    "ftcf_fpA_intB_gemm", "ftcf_fp16_gemm", "ftcf_lm_head", "ftcf_lm_head_log_probs", "ftcf_layernorm", "ftcf_add_bias_attn_ffn_residual",
     "ftcf_masked_multihead_attention", "ftcf_masked_multihead_attention_workspace", "ftcf_context_attention",
     "ftcf_comm_get_unique_id", "ftcf_comm_init", "ftcf_comm_destroy", "ftcf_comm_local_unique_id",
     "ftcf_comm_init_local", "ftcf_comm_init_host_exchange", "ftcf_comm_allreduce_sum",
     "ftcf_comm_allgather", "ftcf_gptneox_create", "ftcf_gptneox_forward", "ftcf_gptneox_begin", "ftcf_gptneox_step", "ftcf_gptneox_finish",
     "ftcf_gptneox_get_stats",
     "ftcf_gptneox_set_profiling", "ftcf_gptneox_destroy",
-    "ftcf_batcher_create", "ftcf_batcher_create_ex", "ftcf_batcher_prefix_stats", "ftcf_batcher_clear_prefix_cache", "ftcf_batcher_submit", "ftcf_batcher_submit_ex", "ftcf_batcher_submit_beam", "ftcf_batcher_submit_beam_ex", "ftcf_batcher_beam_result", "ftcf_batcher_step", "ftcf_batcher_set_token_callback", "ftcf_batcher_status", "ftcf_batcher_cancel", "ftcf_batcher_destroy"]
+    "ftcf_batcher_create", "ftcf_batcher_create_ex", "ftcf_batcher_prefix_stats", "ftcf_batcher_clear_prefix_cache", "ftcf_batcher_submit", "ftcf_batcher_submit_ex", "ftcf_batcher_submit_beam", "ftcf_batcher_submit_beam_ex", "ftcf_batcher_beam_result", "ftcf_batcher_step", "ftcf_batcher_step_ex", "ftcf_batcher_set_token_callback", "ftcf_batcher_status", "ftcf_batcher_cancel", "ftcf_batcher_destroy"]
 
 _lib = None
 

@@ -174,6 +174,7 @@ struct ftcf_batcher {
     DecodeState* d_bstate = nullptr;
     void*        beam_ws = nullptr;
     float *      d_ptopk = nullptr, *d_ptopp = nullptr, *d_temp = nullptr, *d_cum = nullptr, *d_rep = nullptr;
+    float *      d_olp = nullptr, *d_polp = nullptr;  // log-probability of each slot's token of a decode step / of an admission's first
     int*         d_hist = nullptr;  // [max_len + 1][max_batch] time-major token history of the slots (repetition penalty)
     int *        d_sw = nullptr;    // admission: stop words of the ragged batch, the reference's [n][2][Lw] layout
     uint64_t *   d_seed = nullptr, *d_draws = nullptr;
@@ -294,6 +295,8 @@ struct ftcf_batcher {
         d_ptopp = dmalloc<float>(B);
         d_temp = dmalloc<float>(B);
         d_cum = dmalloc<float>(B);
+        d_olp = dmalloc<float>(B);
+        d_polp = dmalloc<float>(B);
         d_rep = dmalloc<float>(B);
         d_hist = dmalloc<int>((size_t)(max_len + 2) * B);
         d_sw = dmalloc<int>(B * 2 * STOP_LW);
@@ -489,9 +492,11 @@ struct ftcf_batcher {
     }
 
     struct Event {
-        long id;
-        int  token, finished;
+        long  id;
+        int   token, finished;
+        float log_prob = NAN;  // ftcf_batcher_step_ex: the token's log-probability (NaN: a beam request's event)
     };
+    bool want_log_probs = false;  // inside ftcf_batcher_step_ex: admissions compute their first token's log-probability too
     std::vector<Event>* hook_ev = nullptr;  // where the decode steps inside a chunked admission put their events
     std::deque<Event>   outbox;             // events of an iteration that did not fit the caller's arrays
     ftcf_token_callback_fn on_token = nullptr;  // called for every event the moment it exists (inside step())
@@ -613,6 +618,9 @@ struct ftcf_batcher {
         a.n_random_seed = n;
         a.output_ids = d_pout;
         a.sequence_lengths = d_pseq;
+        if (want_log_probs) {  // (the engine then runs the soft-max statistics as return_cum_log_probs = 1 does: the decode steps' setting)
+            a.output_log_probs = d_polp;
+        }
         const int hit_tokens = hit ? (int)hit->size() * P : 0;
         if (hit_tokens > 0) {
             // the prompt phase starts at the first uncached token; first the cached pages go to cache row 0 (the engine's cache
@@ -642,6 +650,10 @@ struct ftcf_batcher {
         }
         std::vector<int> out((size_t)n * (S + 1));
         FTCF_HIP_CHECK(hipMemcpy(out.data(), d_pout, out.size() * 4, hipMemcpyDeviceToHost));
+        std::vector<float> first_lp((size_t)n, NAN);
+        if (want_log_probs) {
+            FTCF_HIP_CHECK(hipMemcpy(first_lp.data(), d_polp, (size_t)n * 4, hipMemcpyDeviceToHost));
+        }
         const size_t row_kv = (size_t)e->nhl * (S + 1) * e->dh;  // one row of one layer of the engine's cache
         for (int i = 0; i < n; i++) {
             const Request& r  = rs[i];
@@ -688,7 +700,7 @@ struct ftcf_batcher {
             s.generated = 1;
             s.max_new = r.max_new;
             const int done = (first == e->cfg.end_id || s.generated >= s.max_new || hits_stop_word(s)) ? 1 : 0;
-            ev.push_back(Event{r.id, first, done});  // (the token callback fires when the admission has succeeded: step())
+            ev.push_back(Event{r.id, first, done, first_lp[i]});  // (the token callback fires when the admission has succeeded: step())
             if (done) {
                 const uint8_t one8 = 1;
                 FTCF_HIP_CHECK(hipMemcpy(d_fin + si, &one8, 1, hipMemcpyHostToDevice));
@@ -1345,6 +1357,7 @@ struct ftcf_batcher {
         sp.finished = d_fin;
         sp.seq_len = d_len;     // + 1 per sampled token: the slot's length
         sp.cum_log_probs = d_cum;
+        sp.output_log_probs = d_olp;  // (row_len: one value per slot, written where cum_log_probs is)
         sp.pad_count = d_zero;
         sp.state = d_state;     // step stays 0
         sp.ws = samp_ws;
@@ -1363,8 +1376,10 @@ struct ftcf_batcher {
         }
         std::vector<int>     tok(B);
         std::vector<uint8_t> fin(B);
+        std::vector<float>   lp(B);
         int                  gemm_err = 0;
         FTCF_HIP_CHECK(hipMemcpyAsync(tok.data(), d_tok, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+        FTCF_HIP_CHECK(hipMemcpyAsync(lp.data(), d_olp, (size_t)B * 4, hipMemcpyDeviceToHost, st));
         FTCF_HIP_CHECK(hipMemcpyAsync(fin.data(), d_fin, (size_t)B, hipMemcpyDeviceToHost, st));
         if (smallm_ws) {  // sticky flag of the burst GEMMs' in-launch split-K reduction (the engine's finish() reads its own)
             FTCF_HIP_CHECK(hipMemcpyAsync(&gemm_err, reinterpret_cast<char*>(smallm_ws) + smallm_partial, sizeof(int),
@@ -1417,7 +1432,7 @@ struct ftcf_batcher {
             s.generated += 1;
             s.hist.push_back(tok[si]);
             const int done = (fin[si] || s.generated >= s.max_new || hits_stop_word(s)) ? 1 : 0;
-            emit(ev, Event{s.id, tok[si], done});
+            emit(ev, Event{s.id, tok[si], done, lp[si]});
             if (done) {
                 if (!fin[si]) {
                     const uint8_t one8 = 1;
@@ -1840,20 +1855,23 @@ extern "C" int ftcf_batcher_beam_result(ftcf_batcher_t b, long request_id, int* 
         b->beam_results.erase(it);
     });
 }
-extern "C" int ftcf_batcher_step(ftcf_batcher_t b, long* request_ids, int* tokens, int* finished, int capacity, int* n_events)
+static int batcher_step(ftcf_batcher_t b, long* request_ids, int* tokens, int* finished, float* log_probs, int capacity, int* n_events)
 {
     return guarded([&] {
         FTCF_CHECK_ARG(b && request_ids && tokens && finished && n_events, "NULL argument");
         FTCF_CHECK_ARG(capacity >= 2 * b->max_batch, "event arrays must hold 2 * max_batch entries");
         if (b->outbox.empty()) {  // (else: the rest of the previous iteration's events first)
             std::vector<ftcf_batcher::Event> ev;
+            b->want_log_probs = log_probs != nullptr;
             try {
                 b->step(ev);
             }
             catch (...) {
+                b->want_log_probs = false;
                 b->outbox.insert(b->outbox.end(), ev.begin(), ev.end());  // tokens of decode steps that did run are not lost
                 throw;
             }
+            b->want_log_probs = false;
             b->outbox.insert(b->outbox.end(), ev.begin(), ev.end());
         }
         int n = 0;
@@ -1861,10 +1879,25 @@ extern "C" int ftcf_batcher_step(ftcf_batcher_t b, long* request_ids, int* token
             request_ids[n] = b->outbox.front().id;
             tokens[n]      = b->outbox.front().token;
             finished[n]    = b->outbox.front().finished;
+            if (log_probs) {
+                log_probs[n] = b->outbox.front().log_prob;
+            }
             b->outbox.pop_front();
         }
         *n_events = n;
     });
+}
+extern "C" int ftcf_batcher_step(ftcf_batcher_t b, long* request_ids, int* tokens, int* finished, int capacity, int* n_events)
+{
+    return batcher_step(b, request_ids, tokens, finished, nullptr, capacity, n_events);
+}
+extern "C" int ftcf_batcher_step_ex(ftcf_batcher_t b, long* request_ids, int* tokens, int* finished, float* log_probs, int capacity,
+                                    int* n_events)
+{
+    if (!log_probs) {
+        return guarded([&] { FTCF_CHECK_ARG(false, "NULL argument"); });
+    }
+    return batcher_step(b, request_ids, tokens, finished, log_probs, capacity, n_events);
 }
 extern "C" int ftcf_batcher_set_token_callback(ftcf_batcher_t b, ftcf_token_callback_fn fn, void* user)
 {

@@ -159,6 +159,16 @@ extern "C" int ftcf_lm_head(const void* A, const void* W, float* logits, int m, 
         lm_head_dispatch((const f16*)A, (const f16*)W, logits, m, n, k, ldc, (hipStream_t)stream);
     });
 }
+extern "C" int ftcf_lm_head_log_probs(const void* A, const void* W, const int* targets, float* log_probs, float* row_logsumexp, int m,
+                                      int n, int k, void* stream)
+{
+    return guarded([&] {
+        require_device();
+        FTCF_CHECK_ARG(A && W && targets && log_probs, "NULL tensor");
+        launch_lm_head_log_probs((const f16*)A, (const f16*)W, targets, log_probs, row_logsumexp, m, n, k,
+                                 lm_head_log_probs_workspace(m, n, (hipStream_t)stream), (hipStream_t)stream);
+    });
+}
 extern "C" int ftcf_layernorm(const void* x, const void* gamma, const void* beta, void* out, int m, int n, float eps,
                               ftcf_dtype dtype, void* stream)
 {
@@ -286,6 +296,10 @@ void ftcf_gptneox::begin(const ftcf_forward_args& a)
     FTCF_CHECK_ARG(K >= 1 && K <= BEAM_MAX_K, "beam_width must be in [1, 64]");
     FTCF_CHECK_ARG(prefill_begin == 0 || (!fp32 && K == 1 && batch == 1 && prefill_begin < S),
                    "a prompt phase from a token offset needs one fp16 / int8 sequence without beams, longer than the offset");
+    FTCF_CHECK_ARG(!a.output_log_probs || K == 1,
+                   "output_log_probs is not supported with beam_width > 1 (the values would have to follow the beams' parents)");
+    FTCF_CHECK_ARG(!a.context_log_probs || !fp32, "context_log_probs needs an fp16 / int8 engine");
+    FTCF_CHECK_ARG(!a.context_log_probs || prefill_begin == 0, "context_log_probs needs the whole prompt phase");
     FTCF_HIP_CHECK(hipSetDevice(cfg.device));
     abandon_session();  // (a request left open -- begin / step without finish, or a step that threw -- must not leak its graph)
     stats.window_allreduces = 0;
@@ -475,6 +489,21 @@ void ftcf_gptneox::begin(const ftcf_forward_args& a)
     else {
         FTCF_HIP_CHECK(hipMemcpyAsync(step_ids, in_ids, (size_t)B * 4, hipMemcpyDeviceToDevice, stream));
     }
+    if (a.context_log_probs) {
+        // (ParallelGpt.cc:403-470) px holds the last layer's output of every prompt row, once per request (beams included, tensor
+        // parallel ranks alike: the head is replicated): the final LayerNorm, then the fused LM head -> log-prob kernel
+        if (S > 1) {
+            launch_layernorm(px, final_g, final_b, pnrm, batch * S, H, 1e-5f, true, stream);
+            launch_context_log_probs(a.context_log_probs, pnrm, lm_head, a.input_ids, a.input_lengths, ctx_tgt, ctx_lp, batch, S, V, H,
+                                     stream);
+        }
+        else {
+            FTCF_HIP_CHECK(hipMemsetAsync(a.context_log_probs, 0, (size_t)batch * S * 4, stream));
+        }
+    }
+    if (a.output_log_probs) {
+        FTCF_HIP_CHECK(hipMemsetAsync(olp, 0, (size_t)out_len * B * 4, stream));  // (steps after a row finished hold 0)
+    }
     FTCF_HIP_CHECK(hipEventRecord(e1, stream));
 
     SamplingParams sp{};
@@ -505,11 +534,13 @@ void ftcf_gptneox::begin(const ftcf_forward_args& a)
     sp.stop_len = a.stop_words_len;
     sp.optional_last_tokens = a.optional_last_tokens;
     sp.optional_count = a.optional_last_tokens_count;
-    sp.return_cum_log_probs = a.return_cum_log_probs ? 1 : 0;
+    // (output_log_probs needs the soft-max statistics: sampling_topk_kernels.cu:273 switches them on for either output)
+    sp.return_cum_log_probs = (a.return_cum_log_probs || a.output_log_probs) ? 1 : 0;
     sp.output_ids = step_ids;
     sp.finished = finished;
     sp.seq_len = seq_len;
     sp.cum_log_probs = cum;
+    sp.output_log_probs = a.output_log_probs ? olp : nullptr;
     sp.pad_count = pad_count;
     sp.state = state;
     sp.h_flags = h_flags;
@@ -778,6 +809,9 @@ void ftcf_gptneox::finish()
     }
     if (a.cum_log_probs) {
         FTCF_HIP_CHECK(hipMemcpyAsync(a.cum_log_probs, cum, (size_t)ses.B * 4, hipMemcpyDeviceToDevice, stream));
+    }
+    if (a.output_log_probs) {
+        launch_transpose_log_probs(a.output_log_probs, olp, ses.total - ses.S, ses.B, stream);
     }
     int ps_error = 0, smallm_error = 0;
     if (pplan.ok) {

@@ -100,6 +100,9 @@ struct ftcf_gptneox {
     uint8_t *    finished = nullptr, *masked = nullptr;
     int *        seq_len = nullptr, *pad_count = nullptr, *step_ids = nullptr, *d_top_k = nullptr,
         *d_min_length = nullptr;
+    float *   olp = nullptr;  // output_log_probs of the token loop, time-major [output_len, B]
+    int*      ctx_tgt = nullptr;  // context_log_probs scratch: targets [B*S] ...
+    float*    ctx_lp  = nullptr;  // ... and the log-probability of each hidden row's target [B*S]
     float *   cum = nullptr, *d_p_topk = nullptr, *d_p_topp = nullptr, *d_temp = nullptr, *d_rep = nullptr;
     uint64_t *draws = nullptr, *d_seed = nullptr;
     float*    smallm_ws = nullptr;  // split-K partials + tickets of the batched decode GEMM (5..16 rows)
@@ -351,6 +354,7 @@ struct ftcf_gptneox {
             d_top_k            = c.take<int>(B);
             d_min_length       = c.take<int>(B);
             cum                = c.take<float>(B);
+            olp                = c.take<float>((size_t)(total - S) * B);
             d_p_topk           = c.take<float>(B);
             d_p_topp           = c.take<float>(B);
             d_temp             = c.take<float>(B);
@@ -376,6 +380,8 @@ struct ftcf_gptneox {
                 patt           = c.take<f16>(M * H * (fp32 ? 2 : 1));
                 pmid           = c.take<f16>(M * il * (fp32 ? 2 : 1));
                 pffn           = c.take<f16>(M * H * (fp32 ? 2 : 1));
+                ctx_tgt        = c.take<int>(M);
+                ctx_lp         = c.take<float>(M);
             }
             if (pass == 0) {
                 arena.reserve(c.off + 4096);

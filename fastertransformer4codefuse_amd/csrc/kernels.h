@@ -351,6 +351,20 @@ void launch32_context_attention(float* qkv, const float* qkv_bias, const int* in
                                 int cache_row_mult = 1);
 void launch32_mmha(const Mmha32Params& p, hipStream_t s);
 
+// ---- fused LM head -> per-row log-probability of a target token : kernels_logprob.hip ----
+// log_probs[r] = l[r, targets[r]] - logsumexp_j l[r, j], l = A[m,k] (fp16) x W[n,k]^T (fp16, fp32 accumulation); targets[r] < 0
+// (or >= n) gives 0; row_lse [m] or NULL.  k % 8 == 0.  ws: lm_head_log_probs_workspace_bytes(m, n) bytes, no zeroing needed.
+size_t lm_head_log_probs_workspace_bytes(int m, int n);
+void   launch_lm_head_log_probs(const f16* A, const f16* W_nk, const int* targets, float* log_probs, float* row_lse, int m, int n,
+                                int k, void* ws, hipStream_t s);
+// a grow-only workspace of at least that size per (device, stream), kept for the life of the process
+void*  lm_head_log_probs_workspace(int m, int n, hipStream_t s);
+// the engine's context_log_probs [B, S] from the final-LayerNorm'd prompt rows hidden_nrm [B*S, H]: targets / lp are [B*S] scratch
+void   launch_context_log_probs(float* out, const f16* hidden_nrm, const f16* W_nk, const int* ids, const int* lengths, int* targets,
+                                float* lp, int B, int S, int V, int H, hipStream_t s);
+// output_log_probs: the time-major [T, B] buffer of the token loop -> [B, T]
+void   launch_transpose_log_probs(float* out, const float* in, int T, int B, hipStream_t s);
+
 // ---- dynamic decode : kernels_sampling.hip ----
 struct DecodeState {  // device resident, one per engine
     int step;         // current step (max_input_len .. total-1)
@@ -382,6 +396,9 @@ struct SamplingParams {
     uint8_t*        finished;
     int*            seq_len;
     float*          cum_log_probs;
+    // the log-probability each step adds to cum_log_probs, time-major [total_len - max_input_len, B] at row (step - max_input_len)
+    // (row 0 with row_len: one step per launch), or NULL.  Needs return_cum_log_probs.
+    float*          output_log_probs;
     int*            pad_count;
     DecodeState*    state;
     int*            h_flags;  // pinned host mirror: [0] = all_finished, [1] = step that produced it

@@ -80,6 +80,17 @@ __device__ __forceinline__ VI block_best(VI x, float* redv, int* redi)
     return r;
 }
 
+// the log-probability a step adds to cum_log_probs, kept per token (GptNeoX.cc:967-987 output_log_probs): row (step -
+// max_input_len) of the time-major buffer, indexed by the DEVICE step so that a captured step replays correctly (row 0 in the
+// continuous batcher, whose rows each have their own step and which launches one step at a time)
+__device__ __forceinline__ void store_output_log_prob(const SamplingParams& p, const int step, const int row, const float lp)
+{
+    if (p.output_log_probs) {
+        const size_t t = p.row_len ? 0 : (size_t)(step - p.max_input_len);
+        p.output_log_probs[t * p.B + row] = lp;
+    }
+}
+
 // ---- step 1: penalties, masks, softmax (one block per row) -----------------------------------------------------
 __global__ __launch_bounds__(1024) void k_decode_prep(const SamplingParams p)
 {
@@ -834,8 +845,12 @@ __global__ __launch_bounds__(256) void k_sample(const SamplingParams p, float* c
                 id = 0;
             }
             *out_id = id;
-            if (p.return_cum_log_probs && p.cum_log_probs) {
-                p.cum_log_probs[b] += logf(sv[pick]);
+            if (p.return_cum_log_probs) {
+                const float lp = logf(sv[pick]);
+                if (p.cum_log_probs) {
+                    p.cum_log_probs[b] += lp;
+                }
+                store_output_log_prob(p, step, b, lp);
             }
             p.seq_len[b] += 1;  // :305-308
             p.finished[b] = (id == p.end_id);
@@ -952,8 +967,12 @@ __global__ __launch_bounds__(256) void k_sample(const SamplingParams p, float* c
         }
         if (threadIdx.x == 0) {
             *out_id = id;
-            if (p.return_cum_log_probs && p.cum_log_probs) {
-                p.cum_log_probs[b] += logf(pr);
+            if (p.return_cum_log_probs) {
+                const float lp = logf(pr);
+                if (p.cum_log_probs) {
+                    p.cum_log_probs[b] += lp;
+                }
+                store_output_log_prob(p, step, b, lp);
             }
             p.seq_len[b] += 1;
             p.finished[b] = (id == p.end_id);
@@ -1176,8 +1195,12 @@ __device__ __forceinline__ void greedy_finish(const SamplingParams& p, const flo
                     id = 0;
                 }
                 *out_id = id;
-                if (p.return_cum_log_probs && p.cum_log_probs) {
-                    p.cum_log_probs[row] = cum + logf(prob);
+                if (p.return_cum_log_probs) {
+                    const float lp = logf(prob);
+                    if (p.cum_log_probs) {
+                        p.cum_log_probs[row] = cum + lp;
+                    }
+                    store_output_log_prob(p, step, row, lp);
                 }
                 p.seq_len[row]  = slen + 1;
                 p.finished[row] = (id == p.end_id);
@@ -1308,8 +1331,12 @@ __device__ __forceinline__ void greedy_finish(const SamplingParams& p, const flo
                 id = 0;
             }
             *out_id = id;
-            if (p.return_cum_log_probs && p.cum_log_probs) {
-                p.cum_log_probs[row] = cum + logf(prob);
+            if (p.return_cum_log_probs) {
+                const float lp = logf(prob);
+                if (p.cum_log_probs) {
+                    p.cum_log_probs[row] = cum + lp;
+                }
+                store_output_log_prob(p, step, row, lp);
             }
             p.seq_len[row]  = slen + 1;  // :305-308
             p.finished[row] = (id == p.end_id);
@@ -1670,8 +1697,12 @@ __global__ __launch_bounds__(256) void k_topk_decode(const SamplingParams p, flo
                 id = 0;
             }
             *out_id = id;
-            if (p.return_cum_log_probs && p.cum_log_probs) {
-                p.cum_log_probs[row] += logf(sv[pick]);
+            if (p.return_cum_log_probs) {
+                const float lp = logf(sv[pick]);
+                if (p.cum_log_probs) {
+                    p.cum_log_probs[row] += lp;
+                }
+                store_output_log_prob(p, step0, row, lp);
             }
             p.seq_len[row] += 1;  // :305-308
             p.finished[row] = (id == p.end_id);

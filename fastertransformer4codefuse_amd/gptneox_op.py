@@ -168,7 +168,11 @@ class GptNeoXOp:
     def forward(self, input_ids, input_lengths, output_len, beam_width=None, top_k=None, top_p=None,
                 beam_search_diversity_rate=None, temperature=None, len_penalty=None, repetition_penalty=None,
                 random_seed=None, stop_words_list=None, optional_last_tokens=None, return_cum_log_probs=None,
-                callback=None, _debug_logits=None):
+                callback=None, _debug_logits=None, return_output_log_probs=None, return_context_log_probs=None):
+        """Returns [output_ids, sequence_lengths], then cum_log_probs [B, beam], output_log_probs [B, beam, output_len]
+        (GptNeoX.cc:967-987: each generated token's log-probability, 0 after a row has finished) and context_log_probs
+        [B, max_input_len] (log P(input_ids[b, t] | input_ids[b, < t]) at t >= 1, 0 at t = 0 and in the padding), each
+        only when it was asked for."""
         _check_input(input_ids, "input_ids", torch.int32)
         if input_ids.dim() != 2:
             raise RuntimeError("input_ids must be a matrix")
@@ -186,6 +190,9 @@ class GptNeoXOp:
         output_ids = torch.empty((B, beam_width, total), dtype=torch.int32, device=dev)
         sequence_lengths = torch.empty((B, beam_width), dtype=torch.int32, device=dev)
         cum_log_probs = torch.empty((B, beam_width), dtype=torch.float32, device=dev) if return_cum_log_probs else None
+        output_log_probs = (torch.empty((B, beam_width, int(output_len)), dtype=torch.float32, device=dev)
+                            if return_output_log_probs else None)
+        context_log_probs = torch.empty((B, S), dtype=torch.float32, device=dev) if return_context_log_probs else None
 
         keep = []
 
@@ -230,10 +237,16 @@ class GptNeoXOp:
         a.cum_log_probs = cum_log_probs.data_ptr() if cum_log_probs is not None else None
         if _debug_logits is not None:
             a.debug_logits = _debug_logits.data_ptr()
+        if output_log_probs is not None:
+            a.output_log_probs = output_log_probs.data_ptr()
+        if context_log_probs is not None:
+            a.context_log_probs = context_log_probs.data_ptr()
         capi.check(capi.lib().ftcf_gptneox_forward(self._h, C.byref(a)))
-        if return_cum_log_probs:
-            return [output_ids, sequence_lengths, cum_log_probs]
-        return [output_ids, sequence_lengths]
+        out = [output_ids, sequence_lengths]
+        for t in (cum_log_probs, output_log_probs, context_log_probs):
+            if t is not None:
+                out.append(t)
+        return out
 
     # --- extras (not part of the reference surface) ---
     def stats(self):

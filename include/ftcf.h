@@ -79,6 +79,13 @@ int ftcf_fp16_gemm(const void* A, const void* W_tiled, const void* bias, ftcf_ac
                    void* stream);
 /* LM head (models/gptneox/GptNeoX.cc:866-912): logits_f32[m, n] = A[m,k] (fp16) x W[n,k]^T (fp16, row major [V,H]) */
 int ftcf_lm_head(const void* A, const void* W_nk, float* logits, int m, int n, int k, int ldc, void* stream);
+/* Fused LM head -> log-probability of a target token (the prompt-scoring kernel behind context_log_probs; the reference writes
+ * the logits and runs kernels/logprob_kernels.cu:36-100 over them).  For each row r, l_j = sum_k A[r,k] W[j,k] (fp16 products,
+ * fp32 accumulation, as ftcf_lm_head), log_probs[r] = l[targets[r]] - logsumexp_j l_j; targets[r] < 0 (or >= n) gives 0.
+ * row_logsumexp [m] or NULL.  A [m, k] fp16, W [n, k] fp16 row major (the engine's lm_head), targets [m] int32, k % 8 == 0;
+ * all device pointers.  Deterministic: two calls give identical bits.  Workspace is internal (kept per device and stream). */
+int ftcf_lm_head_log_probs(const void* A, const void* W_nk, const int* targets, float* log_probs, float* row_logsumexp, int m, int n,
+                           int k, void* stream);
 /* invokeGeneralLayerNorm (kernels/layernorm_kernels.cu:1652-1735), fp16 half2 path numerics (:157-286) */
 int ftcf_layernorm(const void* x, const void* gamma, const void* beta, void* out, int m, int n, float eps,
                    ftcf_dtype dtype, void* stream);
@@ -195,6 +202,22 @@ typedef struct {
     float* cum_log_probs;    /* [B, beam] or NULL */
     /* optional debug taps (device, may be NULL): raw fp32 logits of every step [output_len, B, V] */
     float* debug_logits;
+    /* per-token log-probabilities (device, may be NULL; appended last so that zero-initialised callers are unchanged).
+     * output_log_probs [B, beam, output_len] (GptNeoX.cc:418, 967-987): [b, 0, i] is the log-probability of the i-th generated
+     *   token, exactly the value that step adds to cum_log_probs -- logf(prob) under the row's soft-max after temperature,
+     *   penalties and the min-length / optional-token masks, before top-k / top-p truncation (the reference's top-p definition).
+     *   Deliberate difference: the reference's TOP-K kernel stores log P(i | i in top-k) (sampling_topk_kernels.cu:289-301),
+     *   which is always 0 for greedy; here top-k rows store the full-soft-max value as top-p rows do.  Steps after a row has
+     *   finished hold 0, so a sequential fp32 sum over i reproduces cum_log_probs bit for bit.  Asking for it switches the
+     *   soft-max statistics on exactly as return_cum_log_probs = 1 does: tokens are those of that request.  beam_width > 1 is
+     *   refused (FTCF_ERR_INVALID_ARG).
+     * context_log_probs [B, max_input_len] (ParallelGpt.cc:403-470 is_return_context_cum_log_probs): [b, t] for
+     *   1 <= t < input_lengths[b] is log P(input_ids[b, t] | input_ids[b, < t]); [b, 0] and the padding hold 0.  The index is the
+     *   token's own position (FT's log_probs[t] holds token t + 1).  Computed once per request by a fused LM-head kernel (the
+     *   logits never reach memory; ftcf_lm_head_log_probs); beam requests score the prompt once, the values equal beam_width 1's.
+     *   fp32 engines are refused. */
+    float* output_log_probs;
+    float* context_log_probs;
 } ftcf_forward_args;
 
 typedef struct {
@@ -305,6 +328,13 @@ int ftcf_batcher_beam_result(ftcf_batcher_t b, long request_id, int* output_ids,
  * iteration then produces several tokens per running sequence.  Events that do not fit `capacity` are returned by the next
  * calls, before a new iteration runs (`running` of ftcf_batcher_status counts 1 for them). */
 int ftcf_batcher_step(ftcf_batcher_t b, long* request_ids, int* tokens, int* finished, int capacity, int* n_events);
+/* The same with each event's log-probability: log_probs[i] is the event token's log-probability as output_log_probs of
+ * ftcf_forward_args defines it (the value the step adds to the request's cumulative log-probability), NaN for a beam request's
+ * token = -1 event.  An admission inside this call scores its first token too (the engine's prompt phase then runs the soft-max
+ * statistics, as every decode step of the batcher does); events of admissions made by ftcf_batcher_step and fetched here carry
+ * NaN.  log_probs holds `capacity` floats. */
+int ftcf_batcher_step_ex(ftcf_batcher_t b, long* request_ids, int* tokens, int* finished, float* log_probs, int capacity,
+                         int* n_events);
 /* Streaming (the reference's token callback, GptNeoX.cc:362-375, 1023 `token_generated_cb_`, per request here): `fn` is called
  * from inside ftcf_batcher_step, on the calling thread, for every event the moment its token is on the host -- i.e. between
  * the chunks of a long admission as well -- and the same events are returned by the step call afterwards.  NULL unsets. */
