@@ -235,6 +235,58 @@ extern "C" int ftcf_context_attention(const void* qkv, const void* qkv_bias, con
                                  S, nh, dh, rot, s_max, (f16*)ctx, (hipStream_t)stream);
     });
 }
+// the batcher's paged kernels, one call each (the batcher itself launches them through the same launchers)
+extern "C" int ftcf_paged_attention(const void* qkv, const void* qkv_bias, void* k_pool, void* v_pool, const int* page_table,
+                                    const int* lengths, const uint8_t* finished, int B, int nh, int dh, int rot, int page_tokens,
+                                    int max_pages, int max_len, void* ctx, void* stream)
+{
+    return guarded([&] {
+        require_device();
+        FTCF_CHECK_ARG(qkv && qkv_bias && k_pool && v_pool && page_table && lengths && finished && ctx, "NULL tensor");
+        FTCF_CHECK_ARG(B >= 1 && nh >= 1 && page_tokens >= 1 && max_pages >= 1 && max_len >= 1 && max_len <= max_pages * page_tokens,
+                       "paged attention: bad geometry");
+        MmhaPagedParams p{};
+        p.qkv = (const f16*)qkv;
+        p.qkv_bias = (const f16*)qkv_bias;
+        p.kpool = (f16*)k_pool;
+        p.vpool = (f16*)v_pool;
+        p.page_table = page_table;
+        p.len = lengths;
+        p.finished = finished;
+        p.B = B;
+        p.nh = nh;
+        p.dh = dh;
+        p.rot = rot;
+        p.P = page_tokens;
+        p.max_pages = max_pages;
+        p.ctx = (f16*)ctx;
+        launch_mmha_paged(p, max_len, (hipStream_t)stream);
+    });
+}
+extern "C" int ftcf_scatter_kv_to_pages(const void* k_cache, const void* v_cache, void* k_pool, void* v_pool, const int* pages, int L,
+                                        int nh, int dh, int s_max, int S, int page_tokens, size_t pool_layer_elems,
+                                        size_t src_layer_elems, void* stream)
+{
+    return guarded([&] {
+        require_device();
+        FTCF_CHECK_ARG(k_cache && v_cache && k_pool && v_pool && pages, "NULL tensor");
+        FTCF_CHECK_ARG(L >= 1 && nh >= 1 && page_tokens >= 1 && S >= 0 && S <= s_max && dh % 8 == 0, "scatter_kv_to_pages: bad geometry");
+        launch_scatter_kv_to_pages((const f16*)k_cache, (const f16*)v_cache, (f16*)k_pool, (f16*)v_pool, pages, L, nh, dh, s_max, S,
+                                   page_tokens, pool_layer_elems, (hipStream_t)stream, src_layer_elems);
+    });
+}
+extern "C" int ftcf_gather_pages_to_kv(void* k_cache, void* v_cache, const void* k_pool, const void* v_pool, const int* pages, int L,
+                                       int nh, int dh, int s_max, int T, int page_tokens, size_t pool_layer_elems,
+                                       size_t dst_layer_elems, void* stream)
+{
+    return guarded([&] {
+        require_device();
+        FTCF_CHECK_ARG(k_cache && v_cache && k_pool && v_pool && pages, "NULL tensor");
+        FTCF_CHECK_ARG(L >= 1 && nh >= 1 && page_tokens >= 1, "gather_pages_to_kv: bad geometry");
+        launch_gather_pages_to_kv((f16*)k_cache, (f16*)v_cache, (const f16*)k_pool, (const f16*)v_pool, pages, L, nh, dh, s_max, T,
+                                  page_tokens, pool_layer_elems, (hipStream_t)stream, dst_layer_elems);
+    });
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // the engine

@@ -105,6 +105,27 @@ size_t ftcf_masked_multihead_attention_workspace(int B, int nh, int dh, int s_ma
  * qkv [B*S, 3*Hl] fp16 (row = b*S+s), ctx [B*S, Hl] fp16. */
 int ftcf_context_attention(const void* qkv, const void* qkv_bias, const int* input_lengths, void* k_cache,
                            void* v_cache, int B, int S, int nh, int dh, int rot, int s_max, void* ctx, void* stream);
+/* The continuous batcher's decode attention over paged K/V (one layer): the arithmetic of ftcf_masked_multihead_attention for
+ * slot b at position lengths[b] (NeoX rotary at that position), the keys of positions [0, lengths[b]) read through
+ * page_table[b][t / page_tokens] at row t % page_tokens, the new key / value row appended there.  qkv [B, 3*nh*dh] fp16,
+ * qkv_bias [3*nh*dh], k_pool / v_pool [num_pages][nh][page_tokens][dh] fp16, page_table [B][max_pages] int32, lengths [B]
+ * int32 (< max_len), finished [B] uint8 (1: slot skipped, nothing read or written), ctx [B, nh*dh] fp16.  dh 64 / 128; a
+ * slot's scores stay in LDS, so max_len (= max_pages * page_tokens in the batcher) is bounded (~15000 tokens at dh 128). */
+int ftcf_paged_attention(const void* qkv, const void* qkv_bias, void* k_pool, void* v_pool, const int* page_table,
+                         const int* lengths, const uint8_t* finished, int B, int nh, int dh, int rot, int page_tokens,
+                         int max_pages, int max_len, void* ctx, void* stream);
+/* K/V of tokens [0, S) of one sequence, dense -> paged, for L layers: k_cache / v_cache point at the sequence's row of layer 0
+ * of a cache [L][rows][nh][s_max][dh] (src_layer_elems = rows * nh * s_max * dh apart; 0: a one-row cache), the pools are
+ * [L][num_pages][nh][page_tokens][dh] (pool_layer_elems = num_pages * nh * page_tokens * dh apart), pages [S / page_tokens
+ * rounded up] the sequence's page ids.  A bit-exact copy; nothing beyond token S - 1 is written. */
+int ftcf_scatter_kv_to_pages(const void* k_cache, const void* v_cache, void* k_pool, void* v_pool, const int* pages, int L, int nh,
+                             int dh, int s_max, int S, int page_tokens, size_t pool_layer_elems, size_t src_layer_elems,
+                             void* stream);
+/* The inverse (the batcher's prefix cache): tokens [0, T) of a sequence's pages -> its row of the dense cache, T a multiple of
+ * page_tokens and <= s_max; same layouts and strides as ftcf_scatter_kv_to_pages.  A bit-exact copy. */
+int ftcf_gather_pages_to_kv(void* k_cache, void* v_cache, const void* k_pool, const void* v_pool, const int* pages, int L, int nh,
+                            int dh, int s_max, int T, int page_tokens, size_t pool_layer_elems, size_t dst_layer_elems,
+                            void* stream);
 
 /* ================================================================================================
  * libth_gptneox counterpart -- the engine behind GptNeoXOp

@@ -109,3 +109,20 @@ def shard_weights(cfg, w, tp, rank):
             out.append(np.ascontiguousarray(a, dtype=np.float32))
     out += [w[12 * L], w[12 * L + 1], w[12 * L + 2], w[12 * L + 3]]
     return out
+
+
+# ---- the continuous batcher's paged geometry: k_mmha_paged keeps a slot's scores in LDS, so max_seq_len is bounded ----
+PAGED_LDS = 64 * 1024
+
+
+def paged_smem_bytes(dh, max_pages, max_len):
+    """mmha_paged_smem_bytes (csrc/kernels_attn.hip): q / k / v, the wave partials, the page table, the scores."""
+    return 3 * dh * 2 + 4 * dh * 4 + max_pages * 4 + (max_len + 2) * 4
+
+
+def longest_paged_len(dh, P):
+    """max_len (= max_pages * P) of the longest max_seq_len the batcher accepts for (dh, P) (batcher.hip: the LDS rule)."""
+    mp = 1
+    while paged_smem_bytes(dh, mp + 1, (mp + 1) * P) <= PAGED_LDS:
+        mp += 1
+    return mp * P
