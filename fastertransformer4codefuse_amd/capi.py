@@ -53,7 +53,8 @@ class ForwardArgs(C.Structure):
         ("callback", TOKEN_CALLBACK), ("callback_user", C.c_void_p),
         ("output_ids", C.c_void_p), ("sequence_lengths", C.c_void_p), ("cum_log_probs", C.c_void_p),
         ("debug_logits", C.c_void_p),
-        ("output_log_probs", C.c_void_p), ("context_log_probs", C.c_void_p)]
+        ("output_log_probs", C.c_void_p), ("context_log_probs", C.c_void_p),
+        ("speculative_tokens", C.c_int), ("speculative_ngram", C.c_int), ("draft_ids", C.c_void_p)]
 
 
 class ForwardStats(C.Structure):
@@ -62,7 +63,8 @@ class ForwardStats(C.Structure):
                 ("gemv_kind", C.c_int), ("decode_path", C.c_int), ("prefill_overlap", C.c_int),
                 ("prefill_ms_plain", C.c_float), ("prefill_ms_overlapped", C.c_float), ("window_allreduces", C.c_int),
                 ("decode_overlap", C.c_int), ("decode_step_ms_plain", C.c_float), ("decode_step_ms_overlapped", C.c_float),
-                ("persist_layout", C.c_int)]
+                ("persist_layout", C.c_int),
+                ("spec_active", C.c_int), ("spec_steps", C.c_int), ("spec_drafted", C.c_int), ("spec_accepted", C.c_int)]
 
 
 # every symbol include/ftcf.h declares (tests/test_capi_host.py checks the list against the header and the library)
@@ -72,6 +74,7 @@ EXPORTED = [
     "ftcf_int8_rowmajor_to_cuda_sm80", "ftcf_fp16_rowmajor_to_tiled",
     "ftcf_fpA_intB_gemm", "ftcf_fp16_gemm", "ftcf_lm_head", "ftcf_lm_head_log_probs", "ftcf_layernorm", "ftcf_add_bias_attn_ffn_residual",
     "ftcf_masked_multihead_attention", "ftcf_masked_multihead_attention_workspace", "ftcf_context_attention",
+    "ftcf_verify_attention", "ftcf_verify_attention_workspace", "ftcf_ngram_draft",
     "ftcf_paged_attention", "ftcf_scatter_kv_to_pages", "ftcf_gather_pages_to_kv",
     "ftcf_comm_get_unique_id", "ftcf_comm_init", "ftcf_comm_destroy", "ftcf_comm_local_unique_id",
     "ftcf_comm_init_local", "ftcf_comm_init_host_exchange", "ftcf_comm_allreduce_sum",
@@ -93,6 +96,8 @@ def lib():
         _lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
         _lib.ftcf_last_error.restype = C.c_char_p
         _lib.ftcf_masked_multihead_attention_workspace.restype = C.c_size_t
+        if hasattr(_lib, "ftcf_verify_attention_workspace"):  # (FTCF_LIB_NAME may name an older build: the call itself then fails)
+            _lib.ftcf_verify_attention_workspace.restype = C.c_size_t
     return _lib
 
 

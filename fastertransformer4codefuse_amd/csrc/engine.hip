@@ -225,6 +225,46 @@ extern "C" int ftcf_masked_multihead_attention(const void* qkv, const void* qkv_
         launch_mmha(p, (hipStream_t)stream);
     });
 }
+// speculative decoding's kernels, one call each (the engine launches them through the same launchers)
+extern "C" size_t ftcf_verify_attention_workspace(int R, int nh, int dh, int s_max)
+{
+    return verify_attention_workspace_bytes(R, nh, dh, s_max);
+}
+extern "C" int ftcf_verify_attention(const void* qkv, const void* qkv_bias, void* k_cache, void* v_cache, int cache_row, int len,
+                                     int R, int nh, int dh, int rot, int s_max, void* ctx, void* workspace, size_t workspace_bytes,
+                                     void* stream)
+{
+    return guarded([&] {
+        require_device();
+        FTCF_CHECK_ARG(qkv && k_cache && v_cache && ctx && workspace, "NULL tensor");
+        FTCF_CHECK_ARG(cache_row >= 0 && R >= 1 && R <= VERIFY_MAX_ROWS && verify_attention_supported(nh, dh, s_max),
+                       "verify attention: bad geometry (size_per_head 64 / 128, at most ~32000 positions)");
+        FTCF_CHECK_ARG(workspace_bytes >= verify_attention_workspace_bytes(R, nh, dh, s_max), "verify attention workspace too small");
+        VerifyAttnParams p{};
+        p.qkv      = (const f16*)qkv;
+        p.qkv_bias = (const f16*)qkv_bias;
+        p.k_cache  = (f16*)k_cache + (size_t)cache_row * nh * s_max * dh;
+        p.v_cache  = (f16*)v_cache + (size_t)cache_row * nh * s_max * dh;
+        p.ctx      = (f16*)ctx;
+        p.ws       = (float*)workspace;
+        p.len      = len;
+        p.R        = R;
+        p.nh       = nh;
+        p.dh       = dh;
+        p.rot      = rot;
+        p.s_max    = s_max;
+        FTCF_HIP_CHECK(hipMemsetAsync(workspace, 0, verify_attention_ticket_bytes(nh), (hipStream_t)stream));
+        launch_verify_attention(p, (hipStream_t)stream);
+    });
+}
+extern "C" int ftcf_ngram_draft(const int* tokens, int n, int K, int N, int* draft, int* n_draft, void* stream)
+{
+    return guarded([&] {
+        require_device();
+        FTCF_CHECK_ARG(tokens && n >= 1, "draft: tokens [n], n >= 1");
+        launch_ngram_draft(tokens, n, nullptr, K, N, nullptr, 0, 0, draft, n_draft, nullptr, nullptr, (hipStream_t)stream);
+    });
+}
 extern "C" int ftcf_context_attention(const void* qkv, const void* qkv_bias, const int* input_lengths, void* k_cache,
                                       void* v_cache, int B, int S, int nh, int dh, int rot, int s_max, void* ctx,
                                       void* stream)
@@ -386,6 +426,22 @@ void ftcf_gptneox::begin(const ftcf_forward_args& a)
             }
         }
     }
+    // speculative greedy decoding: a hint that cannot change a result -- a request it does not cover
+    // runs as it always has, and the stats say so
+    FTCF_CHECK_ARG(a.speculative_tokens >= 0 && a.speculative_tokens <= VERIFY_MAX_ROWS - 1, "speculative_tokens must be in [0, 15]");
+    FTCF_CHECK_ARG(a.speculative_ngram >= 0 && a.speculative_ngram <= 8, "speculative_ngram must be in [0, 8]");
+    bool spec = a.speculative_tokens > 0 && batch == 1 && K == 1 && !fp32 && tpn == 1 && cfg.use_gptj_residual && prefill_begin == 0
+                && verify_attention_supported(nhl, dh, total) && H % 64 == 0 && hl % 64 == 0 && il % 64 == 0 && !a.callback && !a.return_cum_log_probs
+                && !a.output_log_probs && !a.debug_logits && !a.stop_words_list && !a.optional_last_tokens && a.n_min_length == 0
+                && (a.n_top_k == 0 || (a.top_k && a.top_k[0] <= 1)) && (a.n_top_p == 0 || (a.top_p && a.top_p[0] == 0.f))
+                && (a.n_repetition_penalty == 0 || (a.repetition_penalty && a.repetition_penalty[0] == 1.f));
+    if (spec) {  // (the token history must be dense from position 0: a prompt as long as its row)
+        int h_len = 0;
+        FTCF_HIP_CHECK(hipMemcpyAsync(&h_len, a.input_lengths, sizeof(int), hipMemcpyDeviceToHost, stream));
+        comm_stream_sync(cfg.comm, stream);
+        spec = h_len == S;
+    }
+    spec_plan = spec;
     plan(B, S, total, K);
     if (want_tp && pplan.ok) {
         // granule tags repeat from request to request: every rank's window is zeroed between two barriers -- nobody is
@@ -455,6 +511,11 @@ void ftcf_gptneox::begin(const ftcf_forward_args& a)
     if (smallm_ws) {
         // granules of the batched-decode GEMMs' in-launch reduction: their tags repeat from request to request
         FTCF_HIP_CHECK(hipMemsetAsync(smallm_ws, 0, smallm_partial + gemm_smallm_ticket_bytes(), stream));
+    }
+    if (spec_plan) {  // tickets of the verify attention, granules and tickets of the verify pass's burst GEMMs
+        FTCF_HIP_CHECK(hipMemsetAsync(spec_aws, 0, verify_attention_ticket_bytes(nhl), stream));
+        FTCF_HIP_CHECK(hipMemsetAsync(spec_gws, 0, spec_partial + gemm_smallm_ticket_bytes(), stream));
+        FTCF_HIP_CHECK(hipMemsetAsync(spec_ndraft, 0, 4 * sizeof(int), stream));
     }
     if (pplan.ok || rplan.ok) {
         const size_t cache_l = (size_t)B * nhl * s_max * dh;
@@ -651,6 +712,10 @@ void ftcf_gptneox::begin(const ftcf_forward_args& a)
     ses.all_finished = false;
     ses.e0 = e0;
     ses.e1 = e1;
+    ses.spec   = spec_plan;
+    ses.spec_K = a.speculative_tokens;
+    ses.spec_N = a.speculative_ngram > 0 ? a.speculative_ngram : 3;
+    ses.spec_nd = ses.spec_steps = ses.spec_drafted = ses.spec_accepted = 0;
     stats.decode_ms = 0.f;
     dv_ran = dv_eligible = false;
 }
@@ -726,6 +791,9 @@ int ftcf_gptneox::step(int max_steps)
     Range r("ftcf.step");
     FTCF_CHECK_ARG(ses.active, "no request in flight: call ftcf_gptneox_begin first");
     FTCF_HIP_CHECK(hipSetDevice(cfg.device));
+    if (ses.spec) {
+        return step_speculative(max_steps);
+    }
     const ftcf_forward_args& a = ses.a;
     const int B = ses.B, S = ses.S, total = ses.total;
     const int tp = cfg.tensor_para_size;
@@ -845,6 +913,152 @@ int ftcf_gptneox::step(int max_steps)
     return done;
 }
 
+// One verify pass: the token of position step - 1 and `drafts` drafted tokens as R = drafts + 1 rows of the
+// one sequence through the general path's layer loop for <= 16 rows (decoder(): the burst GEMM pairs [QKV, FFN1] -> attention ->
+// [out-proj, FFN2], residual + both LayerNorms in one pass) with the verify attention where launch_mmha stands, then the final
+// LayerNorm, the LM head on R rows and the acceptance kernel, which closes the step as the greedy kernels do.  The K / V rows of
+// rejected drafts stay in the cache beyond the sequence's length; the next step overwrites them.
+void ftcf_gptneox::verify_pass(int st, int drafts)
+{
+    Range r("ftcf.verify_pass");
+    const int    R = drafts + 1, len = st - 1, s_max = ses.s_max, rot = cfg.rotary_embedding_dim;
+    const size_t cache_l = (size_t)ses.B * nhl * s_max * dh;
+    const double wbytes  = int8 ? 1.0 : 2.0;
+    const bool   dual    = residual_dual_ln_supported(H);
+    launch_verify_embed(vx, wte, step_ids, spec_draft, st, R, H, stream);
+    launch_verify_rotary(vrot, len, R, rot, stream);
+    for (int l = 0; l < L; l++) {
+        const LayerWeights& w       = layers[l];
+        const int           inplace = (l > 0 && l < L - 1) ? 1 : 0;
+        if (!dual) {
+            launch_layernorm(vx, w.ln1_g, w.ln1_b, vnrm, R, H, 1e-5f, true, stream);
+            launch_layernorm(vx, w.ln2_g, w.ln2_b, vnrm2, R, H, 1e-5f, true, stream);
+        }
+        else if (l == 0) {
+            launch_residual_dual_ln(vx, nullptr, nullptr, nullptr, 1, 0, w.ln1_g, w.ln1_b, w.ln2_g, w.ln2_b, vnrm, vnrm2, R, H, 1e-5f,
+                                    stream);
+        }
+        const SmallmDesc p1[2] = {{vnrm, w.qkv.kernel, w.qkv.scale, nullptr, 0, vqkv, 3 * hl, H},
+                                  {vnrm2, w.ffn1.kernel, w.ffn1.scale, w.ffn1.bias, 1, vmid, il, H}};
+        timed(KIND_SMALLM, wbytes * H * (3.0 * hl + il),
+              [&] { launch_gemm_smallm_group(p1, 2, spec_gws, spec_partial, R, int8, stream, &state->step, &smallm_seq); });
+        VerifyAttnParams ap{};
+        ap.qkv       = vqkv;
+        ap.qkv_bias  = w.qkv.bias;
+        ap.k_cache   = k_cache + l * cache_l;
+        ap.v_cache   = v_cache + l * cache_l;
+        ap.rot_table = rot > 0 ? vrot : nullptr;
+        ap.ctx       = vctx;
+        ap.ws        = spec_aws;
+        ap.len       = len;
+        ap.R         = R;
+        ap.nh        = nhl;
+        ap.dh        = dh;
+        ap.rot       = rot;
+        ap.s_max     = s_max;
+        launch_verify_attention(ap, stream);
+        const SmallmDesc p3[2] = {{vctx, w.attn_out.kernel, w.attn_out.scale, nullptr, 0, vatt, H, hl},
+                                  {vmid, w.ffn2.kernel, w.ffn2.scale, nullptr, 0, vffn, H, il}};
+        timed(KIND_SMALLM, wbytes * H * ((double)hl + il),
+              [&] { launch_gemm_smallm_group(p3, 2, spec_gws, spec_partial, R, int8, stream, &state->step, &smallm_seq); });
+        if (dual) {
+            const LayerWeights* nx = l + 1 < L ? &layers[l + 1] : nullptr;
+            launch_residual_dual_ln(vx, vffn, vatt, w.ffn2.bias, 1, inplace, nx ? nx->ln1_g : nullptr, nx ? nx->ln1_b : nullptr,
+                                    nx ? nx->ln2_g : nullptr, nx ? nx->ln2_b : nullptr, vnrm, vnrm2, R, H, 1e-5f, stream);
+        }
+        else {
+            launch_add_bias_attn_ffn_residual(vx, vffn, vatt, vx, w.ffn2.bias, R, H, 1, inplace, true, stream);
+        }
+    }
+    launch_layernorm(vx, final_g, final_b, vnrm, R, H, 1e-5f, true, stream);
+    timed(KIND_LM_HEAD, 2.0 * V * H, [&] { lm_head_dispatch(vnrm, lm_head, vlogits, R, V, H, V, stream); });
+    VerifyAcceptParams vp{};
+    vp.logits     = vlogits;
+    vp.R          = R;
+    vp.V          = V;
+    vp.step       = st;
+    vp.end_id     = cfg.end_id;
+    vp.draft      = spec_draft;
+    vp.output_ids = step_ids;
+    vp.finished   = finished;
+    vp.seq_len    = seq_len;
+    vp.state      = state;
+    vp.h_flags    = h_flags;
+    vp.argmax_ws  = spec_argmax;
+    launch_verify_accept(vp, stream);
+    // what the next plain step expects of the step before it (k_greedy_decode's tail): the embedding row of the last token emitted
+    // and the rotary table of its position
+    launch_step_prologue(x, wte, step_ids, &state->step, rot_table, pad_count, 1, H, rot, stream, &state->all_finished);
+}
+
+// The token loop of a request that speculates.  Every iteration ends with the draft kernel for the NEXT step and one host
+// synchronisation, which tells the host the tokens emitted, the end of the request and whether the next step has drafts: a
+// verify pass then, the plain decode step (its captured graph) otherwise.  Never more than max_steps tokens per call and never
+// past output_len: a pass is cut to what is left.
+int ftcf_gptneox::step_speculative(int max_steps)
+{
+    const ftcf_forward_args& a = ses.a;
+    const int  S = ses.S, total = ses.total;
+    hipEvent_t ea = get_event(), eb = get_event();
+    FTCF_HIP_CHECK(hipEventRecord(ea, stream));
+    int done = 0;
+    while (done < max_steps && ses.next_step < total && !ses.all_finished) {
+        const int  st           = ses.next_step;
+        const bool with_decoder = !(S > 1 && st == S);
+        const int  nd = with_decoder ? std::min(std::min(ses.spec_nd, ses.spec_K), std::min(total - st - 1, max_steps - done - 1)) : 0;
+        if (nd > 0) {
+            verify_pass(st, nd);
+        }
+        else if (use_graph && with_decoder && !profiling) {
+            if (!ses.graph_exec) {
+                hipGraph_t g = nullptr;
+                FTCF_HIP_CHECK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
+                try {
+                    enqueue_step(true);
+                }
+                catch (...) {
+                    (void)hipStreamEndCapture(stream, &g);
+                    if (g) {
+                        (void)hipGraphDestroy(g);
+                    }
+                    throw;
+                }
+                FTCF_HIP_CHECK(hipStreamEndCapture(stream, &g));
+                FTCF_HIP_CHECK(hipGraphInstantiate(&ses.graph_exec, g, nullptr, nullptr, 0));
+                FTCF_HIP_CHECK(hipGraphDestroy(g));
+            }
+            FTCF_HIP_CHECK(hipGraphLaunch(ses.graph_exec, stream));
+        }
+        else {
+            enqueue_step(with_decoder);
+        }
+        // the next step's drafts: the caller's (draft_ids from the generated index of the device's step on) or the n-gram lookup
+        // over the tokens so far
+        launch_ngram_draft(step_ids, 0, &state->step, ses.spec_K, ses.spec_N, a.draft_ids, S, total - S, spec_draft, spec_ndraft,
+                           h_flags + 4, &state->all_finished, stream);
+        comm_stream_sync(cfg.comm, stream);
+        const int emitted = nd > 0 ? h_flags[3] : 1;
+        if (nd > 0) {
+            ses.spec_steps++;
+            ses.spec_drafted += nd;
+            ses.spec_accepted += h_flags[5];
+        }
+        ses.steps += emitted;
+        ses.next_step += emitted;
+        done += emitted;
+        ses.all_finished = h_flags[0] != 0;
+        ses.spec_nd      = h_flags[4];
+    }
+    FTCF_HIP_CHECK(hipEventRecord(eb, stream));
+    comm_event_sync(cfg.comm, eb, "the token loop");
+    float ms = 0.f;
+    FTCF_HIP_CHECK(hipEventElapsedTime(&ms, ea, eb));
+    stats.decode_ms += ms;
+    event_pool.push_back(ea);
+    event_pool.push_back(eb);
+    return done;
+}
+
 void ftcf_gptneox::finish()
 {
     Range r("ftcf.finish");
@@ -882,6 +1096,10 @@ void ftcf_gptneox::finish()
     FTCF_HIP_CHECK(hipEventElapsedTime(&ms, ses.e0, ses.e1));
     stats.prefill_ms   = ms;
     stats.decode_steps = ses.steps;
+    stats.spec_active   = ses.spec ? 1 : 0;
+    stats.spec_steps    = ses.spec_steps;
+    stats.spec_drafted  = ses.spec_drafted;
+    stats.spec_accepted = ses.spec_accepted;
     if (ov_eligible && ov_trial < 2) {  // a trial of the auto mode: every rank keeps the slowest rank's time
         const int us   = comm_max(cfg.comm, (int)(ms * 1000.f), stream, tp_scratch);
         ov_ms[ov_trial] = us * 1e-3f;

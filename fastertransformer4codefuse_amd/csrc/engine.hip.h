@@ -136,6 +136,14 @@ struct ftcf_gptneox {
     long long*          rows_ts = nullptr;
     std::string         ps_ts_file;
 
+    // speculative greedy decoding: the buffers of a verify pass over <= 16 rows of the one sequence, carved
+    // only for a request that speculates (spec_plan, set by begin() before plan())
+    bool   spec_plan = false;
+    f16 *  vx = nullptr, *vnrm = nullptr, *vnrm2 = nullptr, *vqkv = nullptr, *vctx = nullptr, *vatt = nullptr, *vffn = nullptr, *vmid = nullptr;
+    float *vlogits = nullptr, *vrot = nullptr, *spec_aws = nullptr, *spec_gws = nullptr;
+    size_t spec_partial = 0;  // split-K partials of the pass's burst GEMMs (a workspace of their own: [partials][tickets])
+    int *  spec_draft = nullptr, *spec_ndraft = nullptr, *spec_argmax = nullptr;
+
     // profiling
     bool               profiling = false;
     ftcf_forward_stats stats{};
@@ -382,6 +390,26 @@ struct ftcf_gptneox {
                 pffn           = c.take<f16>(M * H * (fp32 ? 2 : 1));
                 ctx_tgt        = c.take<int>(M);
                 ctx_lp         = c.take<float>(M);
+            }
+            if (spec_plan) {  // (behind everything else: the views of a request that does not speculate are where they were)
+                const int R  = VERIFY_MAX_ROWS;
+                vx           = c.take<f16>((size_t)R * H);
+                vnrm         = c.take<f16>((size_t)R * H);
+                vnrm2        = c.take<f16>((size_t)R * H);
+                vqkv         = c.take<f16>((size_t)R * 3 * hl);
+                vctx         = c.take<f16>((size_t)R * hl);
+                vatt         = c.take<f16>((size_t)R * H);
+                vffn         = c.take<f16>((size_t)R * H);
+                vmid         = c.take<f16>((size_t)R * il);
+                vlogits      = c.take<float>((size_t)R * V);
+                vrot         = c.take<float>((size_t)R * 256);
+                spec_aws     = c.take<float>(verify_attention_workspace_bytes(R, nhl, dh, s_max) / 4);
+                spec_partial = gemm_smallm_workspace_bytes(R, 3 * hl, H, int8) + gemm_smallm_workspace_bytes(R, il, H, int8)
+                               + gemm_smallm_workspace_bytes(R, H, hl, int8) + gemm_smallm_workspace_bytes(R, H, il, int8);
+                spec_gws     = c.take<float>((spec_partial + gemm_smallm_ticket_bytes()) / 4);
+                spec_draft   = c.take<int>(R);
+                spec_ndraft  = c.take<int>(4);
+                spec_argmax  = c.take<int>(2 * R);
             }
             if (pass == 0) {
                 arena.reserve(c.off + 4096);
@@ -1387,6 +1415,11 @@ struct ftcf_gptneox {
         hipGraphExec_t    graph_exec = nullptr;
         bool              path_logged = false;  // the decoder of this request has been named in the log (FT_LOG_LEVEL=DEBUG)
         hipGraphExec_t    graph_exec_n = nullptr;  // graph_tokens consecutive tokens in one graph (persistent path, no callback)
+        // speculative decoding: on for this request; K, N; the draft count the last step's draft kernel left for the next one;
+        // verify passes, drafts proposed / accepted so far
+        bool              spec = false;
+        int               spec_K = 0, spec_N = 0, spec_nd = 0;
+        int               spec_steps = 0, spec_drafted = 0, spec_accepted = 0;
     } ses;
     bool use_graph = true;
     // drops whatever an unfinished request left behind: the captured graph holds the OLD arena pointers, shapes and sampling
@@ -1419,6 +1452,8 @@ struct ftcf_gptneox {
     void begin(const ftcf_forward_args& a);
     void enqueue_step(bool with_decoder);
     int  step(int max_steps);
+    int  step_speculative(int max_steps);
+    void verify_pass(int step, int drafts);
     void finish();
     bool persist_failed = false;  // the persistent kernel gave up on a hand-off during the last request
     bool winar_failed = false;    // ... or the exchange-window all-reduce of the prompt phase did

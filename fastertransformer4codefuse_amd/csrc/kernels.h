@@ -463,4 +463,51 @@ void   launch_decode_init(uint8_t* finished, int* seq_len, float* cum_log_probs,
 void   launch_gather_tree(int* output_ids, int* sequence_lengths, const int* step_ids, const int* seq_len,
                           const int* input_lengths, int B, int max_input_len, int total, int end_id, hipStream_t s);
 
+// ---- speculative greedy decoding : kernels_verify.hip ----
+// Decode attention for R <= 16 consecutive new tokens of ONE sequence: qkv [R, 3 * nh * dh], the sequence's cache row
+// k_cache / v_cache [nh, s_max, dh] holds positions [0, len).  Row i: bias, NeoX rotary at len + i, K / V stored at len + i,
+// ctx[i] = soft-max attention over positions [0, len + i] with mmha_partial's arithmetic.  The cached keys are read once for
+// all rows.  rot_table: [R, rot / 2, 2] {cos, sin} of positions len .. len + R - 1 (launch_verify_rotary) or NULL (computed
+// in the kernel, the same values).  ws: verify_attention_workspace_bytes, its ticket words (the first
+// verify_attention_ticket_bytes) zero before the first launch; a launch leaves them zero.
+constexpr int VERIFY_MAX_ROWS = 16;
+struct VerifyAttnParams {
+    const f16*   qkv;
+    const f16*   qkv_bias;
+    f16 *        k_cache, *v_cache;  // the sequence's cache row
+    const float* rot_table;
+    f16*         ctx;  // [R, nh * dh]
+    float*       ws;
+    int          len, R, nh, dh, rot, s_max;
+};
+bool   verify_attention_supported(int nh, int dh, int s_max);  // head size 64 / 128, a context the merger's split table holds
+size_t verify_attention_workspace_bytes(int R, int nh, int dh, int s_max);
+size_t verify_attention_ticket_bytes(int nh);
+void   launch_verify_attention(const VerifyAttnParams& p, hipStream_t s);
+void   launch_verify_rotary(float* table, int len, int R, int rot, hipStream_t s);
+// prompt-lookup drafting (one workgroup).  tokens t[0, n), n = *d_n when d_n is given: for g = min(N, n - 1) .. 1 the LARGEST
+// s <= n - g - 1 with t[s, s + g) == t[n - g, n); the first g that has one wins: draft = t[s + g, min(s + g + K, n)).
+// ext (a caller's own drafts, [ext_len]): draft = ext[n - ext_base, ...) instead, cut at K, at ext_len and at the first negative id.
+// *n_draft (device) and, when given, *h_n_draft (pinned host) receive the count; d_stop set: nothing is drafted (count 0).
+void launch_ngram_draft(const int* tokens, int n, const int* d_n, int K, int N, const int* ext, int ext_base, int ext_len,
+                        int* draft, int* n_draft, int* h_n_draft, const int* d_stop, hipStream_t s);
+// the input rows of a verify pass: x[0] = wte[tokens[step - 1]], x[i] = wte[draft[i - 1]]
+void launch_verify_embed(f16* x, const f16* wte, const int* tokens, const int* draft, int step, int R, int H, hipStream_t s);
+// acceptance: a[i] = argmax of logits row i (value descending, index ascending on ties); m = longest prefix with
+// draft[i] == a[i]; emits a[0 .. m] cut after the first end_id, appends them at output_ids[step ...], advances seq_len[0] and
+// the device step, sets finished / all_finished, and leaves all_finished, the last step written, the tokens emitted and the
+// drafts accepted in h_flags[0], [1], [3], [5] (pinned; [4] is the draft kernel's count).  argmax_ws: 2 * R words.
+struct VerifyAcceptParams {
+    const float* logits;  // [R, V]
+    int          R, V, step, end_id;
+    const int*   draft;  // [R - 1]
+    int*         output_ids;
+    uint8_t*     finished;
+    int*         seq_len;
+    DecodeState* state;
+    int*         h_flags;
+    int*         argmax_ws;
+};
+void launch_verify_accept(const VerifyAcceptParams& p, hipStream_t s);
+
 }  // namespace ftcf

@@ -1,0 +1,567 @@
+// Speculative greedy decoding: the kernels of a verify pass over R = drafts + 1 rows of ONE sequence.
+//
+//  * k_verify_attention : decode attention for R <= 16 consecutive new tokens of one sequence.  launch_mmha treats its rows as
+//      different sequences and would stream the same `len` cached keys R times; here a (head, key-split) workgroup reads its
+//      K / V rows ONCE into registers and scores them against all R rotated queries (staged once in LDS, held in registers by
+//      every lane).  The R new keys are a causal R x R tail served from LDS by the last split's workgroup (row i never reads
+//      row j's key from the cache: another workgroup may not have written it yet).  Arithmetic and rounding points are
+//      mmha_partial's (attn_device.hip.h): half q / k / v + bias, NeoX rotary with the fp32 angle, packed dot2 scores in fp32,
+//      exp against the split's row maximum, fp32 P.V, the split partials merged in split order by the workgroup that draws
+//      the head's last ticket (the ORDER is fixed whoever merges: two launches give the same bits), one normalisation with
+//      the reference's + 1e-6, the context rounded once.
+//  * k_ngram_draft      : prompt-lookup drafting, one workgroup.
+//  * k_verify_embed / k_verify_argmax / k_verify_accept : the pass's input rows and the greedy acceptance rule.
+//
+// Roofline: HBM (4 * len * dh * nh bytes per layer, once for all rows); the VALU work grows with R (R * dh fused
+// multiply-adds per key and head, twice).
+#include "attn_device.hip.h"
+
+namespace ftcf {
+
+constexpr int VA_MAX_CHUNK = 256;                                  // cached keys of a workgroup
+constexpr int VA_LDP       = VA_MAX_CHUNK + VERIFY_MAX_ROWS + 4;   // row stride of the score tile (floats)
+constexpr int VA_MAX_SPLIT = 128;                                  // the merger keeps {max, sum} of every split in a score row
+constexpr int VA_WGS       = 512;                                  // workgroups a launch aims for
+
+typedef __attribute__((address_space(1))) unsigned va_gu32;
+
+// keys per workgroup: a multiple of 32 (one round of the four waves at either head size) in [64, 256]
+static int verify_chunk(int len, int nh)
+{
+    const long want = ((long)len * nh + VA_WGS - 1) / VA_WGS;
+    const int  c    = (int)((want + 31) / 32 * 32);
+    return std::max(64, std::min(VA_MAX_CHUNK, c));
+}
+// the most splits any len <= s_max gets: 64-key chunks never exceed s_max / 64 splits, a chunk of len * nh / VA_WGS keys or more
+// never VA_WGS / nh, 256-key chunks never s_max / 256 (all rounded up)
+static int verify_max_split(int nh, int s_max)
+{
+    nh = std::max(nh, 1);
+    return std::max(1, std::min((s_max + 63) / 64, std::max((VA_WGS + nh - 1) / nh, (s_max + VA_MAX_CHUNK - 1) / VA_MAX_CHUNK)));
+}
+bool verify_attention_supported(int nh, int dh, int s_max)
+{
+    return (dh == 64 || dh == 128) && nh >= 1 && s_max >= 1 && verify_max_split(nh, s_max) <= VA_MAX_SPLIT;
+}
+size_t verify_attention_ticket_bytes(int nh)
+{
+    return ((size_t)nh * sizeof(unsigned) + 255) & ~(size_t)255;
+}
+size_t verify_attention_workspace_bytes(int R, int nh, int dh, int s_max)
+{
+    return verify_attention_ticket_bytes(nh) + (size_t)nh * verify_max_split(nh, s_max) * R * (dh + 2) * sizeof(float);
+}
+
+template<int DH>
+__global__ __launch_bounds__(256) void k_verify_attention(const VerifyAttnParams p, const int chunk, const int nsplit)
+{
+    constexpr int LPK = DH / 8;    // lanes per key / value row (16 B each)
+    constexpr int KPI = 64 / LPK;  // rows per wave-load
+    constexpr int RM  = VERIFY_MAX_ROWS;
+    constexpr int U   = 4;         // rows per lane and round; two rounds in flight
+    constexpr int STEP = 4 * KPI;  // keys of one wave-load of the four waves
+    __shared__ __attribute__((aligned(16))) f16 s_q[RM * DH];
+    __shared__ __attribute__((aligned(16))) f16 s_k[RM * DH];
+    __shared__ __attribute__((aligned(16))) f16 s_v[RM * DH];
+    __shared__ float s_p[RM * VA_LDP];
+    __shared__ float s_o[RM * DH];
+    __shared__ float s_m[RM], s_l[RM];
+    __shared__ int   s_last;
+
+    const int  h = blockIdx.x, sp = blockIdx.y;
+    const int  lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int  sub = lane % LPK, grp = lane / LPK;
+    const int  R = p.R, len = p.len, hl = p.nh * DH;
+    const int  t_beg = sp * chunk;
+    const int  nk    = min(len - t_beg, chunk);  // cached keys of this split (0 only when len == 0)
+    const bool owner = sp == nsplit - 1;         // serves the R new keys
+    const int  n_loc = nk + (owner ? R : 0);
+    f16*       kc = p.k_cache + (size_t)h * p.s_max * DH;
+    f16*       vc = p.v_cache + (size_t)h * p.s_max * DH;
+
+    for (int i = threadIdx.x; i < R * DH; i += 256) {
+        const int    r = i / DH, d = i % DH;
+        const size_t base = (size_t)r * 3 * hl + h * DH + d;
+        s_q[i] = p.qkv[base] + (p.qkv_bias ? p.qkv_bias[h * DH + d] : (f16)0.f);
+        if (owner) {
+            s_k[i] = p.qkv[base + hl] + (p.qkv_bias ? p.qkv_bias[hl + h * DH + d] : (f16)0.f);
+            s_v[i] = p.qkv[base + 2 * hl] + (p.qkv_bias ? p.qkv_bias[2 * hl + h * DH + d] : (f16)0.f);
+        }
+    }
+    __syncthreads();
+    const int half = p.rot / 2;
+    for (int i = threadIdx.x; i < R * half; i += 256) {
+        const int r = i / half, j = i % half;
+        float     cs, sn;
+        if (p.rot_table) {
+            cs = p.rot_table[(size_t)i * 2];
+            sn = p.rot_table[(size_t)i * 2 + 1];
+        }
+        else {
+            rotary_coef(j, p.rot, len + r, cs, sn);
+        }
+        f16 a = s_q[r * DH + j], c = s_q[r * DH + j + half];
+        rotary_apply(a, c, cs, sn);
+        s_q[r * DH + j]        = a;
+        s_q[r * DH + j + half] = c;
+        if (owner) {
+            f16 ka = s_k[r * DH + j], kc2 = s_k[r * DH + j + half];
+            rotary_apply(ka, kc2, cs, sn);
+            s_k[r * DH + j]        = ka;
+            s_k[r * DH + j + half] = kc2;
+        }
+    }
+    __syncthreads();
+    if (owner) {  // append rows [len, len + R) to the cache
+        for (int i = threadIdx.x; i < R * DH / 8; i += 256) {
+            *reinterpret_cast<u32x4*>(kc + (size_t)len * DH + i * 8) = *reinterpret_cast<const u32x4*>(s_k + i * 8);
+            *reinterpret_cast<u32x4*>(vc + (size_t)len * DH + i * 8) = *reinterpret_cast<const u32x4*>(s_v + i * 8);
+        }
+    }
+
+    // the split's cached rows of `base`, U per lane and round, the next round requested before this one is consumed (clamped,
+    // never conditional: consume() gets `valid`)
+    auto stream_rows = [&](const f16* base, auto&& consume) {
+        if (nk <= 0) {
+            return;
+        }
+        u32x4 ra[U], rb[U];
+        auto  ld = [&](u32x4 (&r)[U], const int l0) {
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                int li = l0 + u * STEP + wid * KPI + grp;
+                li     = li < nk ? li : nk - 1;
+                r[u]   = *reinterpret_cast<const u32x4*>(base + (size_t)(t_beg + li) * DH + sub * 8);
+            }
+        };
+        auto use = [&](const u32x4 (&r)[U], const int l0) {
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const int li = l0 + u * STEP + wid * KPI + grp;
+                consume(__builtin_bit_cast(f16x8, r[u]), li, li < nk);
+            }
+        };
+        int l0 = 0;
+        ld(ra, 0);
+        for (;;) {
+            ld(rb, l0 + U * STEP);
+            use(ra, l0);
+            l0 += U * STEP;
+            if (l0 >= nk) {
+                break;
+            }
+            ld(ra, l0 + U * STEP);
+            use(rb, l0);
+            l0 += U * STEP;
+            if (l0 >= nk) {
+                break;
+            }
+        }
+    };
+
+    // ---- phase 1: scores of every key of the split against all rows ----
+    const float inv_sqrt_dh = rsqrtf((float)DH);
+    {
+        f16x8 qv[RM];
+#pragma unroll
+        for (int r = 0; r < RM; r++) {
+            qv[r] = r < R ? *reinterpret_cast<const f16x8*>(s_q + r * DH + sub * 8) : f16x8{0, 0, 0, 0, 0, 0, 0, 0};
+        }
+        // jnew: the key is new key jnew (masked for the rows before it), -1: a cached key
+        auto score = [&](const f16x8 kv, const int li, const bool valid, const int jnew) {
+#pragma unroll
+            for (int r = 0; r < RM; r++) {
+                if (r < R) {
+                    float a = 0.f;
+                    a       = dot2(f16x2{qv[r][0], qv[r][1]}, f16x2{kv[0], kv[1]}, a);
+                    a       = dot2(f16x2{qv[r][2], qv[r][3]}, f16x2{kv[2], kv[3]}, a);
+                    a       = dot2(f16x2{qv[r][4], qv[r][5]}, f16x2{kv[4], kv[5]}, a);
+                    a       = dot2(f16x2{qv[r][6], qv[r][7]}, f16x2{kv[6], kv[7]}, a);
+                    a       = group_sum_dpp<LPK>(a) * inv_sqrt_dh;
+                    if (valid && sub == 0) {
+                        s_p[r * VA_LDP + li] = jnew > r ? -INFINITY : a;
+                    }
+                }
+            }
+        };
+        stream_rows(kc, [&](const f16x8 kv, const int li, const bool valid) { score(kv, li, valid, -1); });
+        if (owner) {
+            for (int j0 = 0; j0 < R; j0 += STEP) {
+                const int   j  = j0 + wid * KPI + grp;
+                const int   jc = j < R ? j : R - 1;
+                const f16x8 kv = *reinterpret_cast<const f16x8*>(s_k + jc * DH + sub * 8);
+                score(kv, nk + j, j < R, jc);
+            }
+        }
+    }
+    __syncthreads();
+    // ---- phase 2: per row, exp against the split's maximum and the local sum (a wave per row) ----
+    for (int r = wid; r < R; r += 4) {
+        float mx = -INFINITY;
+        for (int i = lane; i < n_loc; i += 64) {
+            mx = fmaxf(mx, s_p[r * VA_LDP + i]);
+        }
+        mx        = wave_max_dpp(mx);
+        float sum = 0.f;
+        for (int i = lane; i < n_loc; i += 64) {
+            const float v = s_p[r * VA_LDP + i];
+            const float e = (v == -INFINITY || mx == -INFINITY) ? 0.f : __expf(v - mx);
+            s_p[r * VA_LDP + i] = e;
+            sum += e;
+        }
+        sum = wave_sum_dpp(sum);
+        if (lane == 0) {
+            s_m[r] = mx;
+            s_l[r] = sum;
+        }
+    }
+    __syncthreads();
+    // ---- phase 3: P.V (fp32 accumulate), every value row once for all rows ----
+    float acc[RM][8];
+#pragma unroll
+    for (int r = 0; r < RM; r++) {
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            acc[r][j] = 0.f;
+        }
+    }
+    auto pv = [&](const f16x8 vv, const int li, const bool valid) {
+        if (valid) {
+#pragma unroll
+            for (int r = 0; r < RM; r++) {
+                if (r < R) {
+                    const float pt = s_p[r * VA_LDP + li];
+#pragma unroll
+                    for (int j = 0; j < 8; j++) {
+                        acc[r][j] = fmaf(pt, (float)vv[j], acc[r][j]);
+                    }
+                }
+            }
+        }
+    };
+    stream_rows(vc, pv);
+    if (owner) {
+        for (int j0 = 0; j0 < R; j0 += STEP) {
+            const int   j  = j0 + wid * KPI + grp;
+            const int   jc = j < R ? j : R - 1;
+            const f16x8 vv = *reinterpret_cast<const f16x8*>(s_v + jc * DH + sub * 8);
+            pv(vv, nk + jc, j < R);  // (a masked pair holds probability 0)
+        }
+    }
+    // fold the key groups of a wave (every lane gets the sum), then the four waves in wave order
+#pragma unroll
+    for (int r = 0; r < RM; r++) {
+        if (r < R) {
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                acc[r][j] = across_groups_sum<LPK>(acc[r][j]);
+            }
+        }
+    }
+    for (int w = 0; w < 4; w++) {
+        if (wid == w && grp == 0) {
+#pragma unroll
+            for (int r = 0; r < RM; r++) {
+                if (r < R) {
+#pragma unroll
+                    for (int j = 0; j < 8; j++) {
+                        float* o = &s_o[r * DH + sub * 8 + j];
+                        *o       = (w == 0 ? 0.f : *o) + acc[r][j];
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (nsplit == 1) {
+        for (int i = threadIdx.x; i < R * DH; i += 256) {
+            const int   r = i / DH, d = i % DH;
+            const float inv = 1.f / (s_l[r] + 1.e-6f);
+            p.ctx[(size_t)r * hl + h * DH + d] = (f16)(s_o[i] * inv);
+        }
+        return;
+    }
+    // ---- publish the partial {o[R][DH], max, sum} (write-through: the merger may sit on another XCD), then a ticket ----
+    constexpr int NE      = DH + 2;
+    unsigned*     tickets = reinterpret_cast<unsigned*>(p.ws);
+    float*        parts   = reinterpret_cast<float*>(reinterpret_cast<char*>(p.ws) + (((size_t)p.nh * 4 + 255) & ~(size_t)255))
+                   + (size_t)h * nsplit * R * NE;
+    {
+        va_gu32* mine = (va_gu32*)(parts + (size_t)sp * R * NE);
+        for (int i = threadIdx.x; i < R * DH; i += 256) {
+            const int r = i / DH, d = i % DH;
+            __hip_atomic_store(mine + (size_t)r * NE + d, __float_as_uint(s_o[i]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if ((int)threadIdx.x < R) {
+            __hip_atomic_store(mine + (size_t)threadIdx.x * NE + DH, __float_as_uint(s_m[threadIdx.x]), __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(mine + (size_t)threadIdx.x * NE + DH + 1, __float_as_uint(s_l[threadIdx.x]), __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's stores have been acknowledged
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned t = __hip_atomic_fetch_add((va_gu32*)(tickets + h), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_last           = t == (unsigned)(nsplit - 1) ? 1 : 0;
+        if (s_last) {
+            __hip_atomic_store((va_gu32*)(tickets + h), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-armed
+        }
+    }
+    __syncthreads();
+    if (!s_last) {
+        return;
+    }
+    // ---- merger: every split's {max, sum} -> weights and the denominator per row, in split order ----
+    const va_gu32* all = (const va_gu32*)parts;
+    for (int i = threadIdx.x; i < R * nsplit; i += 256) {
+        const int r = i / nsplit, s2 = i % nsplit;
+        s_p[r * VA_LDP + s2]                = __uint_as_float(__hip_atomic_load(all + ((size_t)s2 * R + r) * NE + DH, __ATOMIC_RELAXED,
+                                                                 __HIP_MEMORY_SCOPE_AGENT));
+        s_p[r * VA_LDP + VA_MAX_SPLIT + s2] = __uint_as_float(__hip_atomic_load(all + ((size_t)s2 * R + r) * NE + DH + 1,
+                                                                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < R) {
+        const int r = threadIdx.x;
+        float     m = -INFINITY;
+        for (int s2 = 0; s2 < nsplit; s2++) {
+            m = fmaxf(m, s_p[r * VA_LDP + s2]);
+        }
+        float L = 0.f;  // fixed-order sum over splits
+        for (int s2 = 0; s2 < nsplit; s2++) {
+            const float ms = s_p[r * VA_LDP + s2];
+            const float w  = (ms == -INFINITY) ? 0.f : __expf(ms - m);
+            L += w * s_p[r * VA_LDP + VA_MAX_SPLIT + s2];
+            s_p[r * VA_LDP + s2] = w;
+        }
+        s_l[r] = L;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < R * DH; i += 256) {
+        const int r = i / DH, d = i % DH;
+        float     o = 0.f;
+        for (int s2 = 0; s2 < nsplit; s2++) {
+            o += s_p[r * VA_LDP + s2]
+                 * __uint_as_float(__hip_atomic_load(all + ((size_t)s2 * R + r) * NE + d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        }
+        const float inv = 1.f / (s_l[r] + 1.e-6f);
+        p.ctx[(size_t)r * hl + h * DH + d] = (f16)(o * inv);
+    }
+}
+
+void launch_verify_attention(const VerifyAttnParams& p, hipStream_t s)
+{
+    FTCF_CHECK_ARG(p.dh == 64 || p.dh == 128, "verify attention: size_per_head must be 64 or 128");
+    FTCF_CHECK_ARG(p.R >= 1 && p.R <= VERIFY_MAX_ROWS, "verify attention: 1 <= rows <= 16");
+    FTCF_CHECK_ARG(p.nh >= 1 && p.len >= 0 && p.len + p.R <= p.s_max, "verify attention: the rows do not fit the cache");
+    FTCF_CHECK_ARG(p.rot >= 0 && p.rot % 2 == 0 && p.rot <= p.dh, "rotary_embedding_dim must be even and <= size_per_head");
+    const int chunk  = verify_chunk(p.len, p.nh);
+    const int nsplit = std::max(1, (p.len + chunk - 1) / chunk);
+    FTCF_CHECK_ARG(nsplit <= VA_MAX_SPLIT && nsplit <= verify_max_split(p.nh, p.s_max), "verify attention: context too long");
+    FTCF_CHECK_ARG(nsplit == 1 || p.ws != nullptr, "verify attention: no workspace");
+    dim3 grid(p.nh, nsplit);
+    if (p.dh == 128) {
+        hipLaunchKernelGGL((k_verify_attention<128>), grid, dim3(256), 0, s, p, chunk, nsplit);
+    }
+    else {
+        hipLaunchKernelGGL((k_verify_attention<64>), grid, dim3(256), 0, s, p, chunk, nsplit);
+    }
+    FTCF_HIP_CHECK(hipGetLastError());
+}
+
+__global__ void k_verify_rotary(float* table, int len, int rot)
+{
+    const int r = blockIdx.x, half = rot / 2;
+    for (int j = threadIdx.x; j < half; j += blockDim.x) {
+        float cs, sn;
+        rotary_coef(j, rot, len + r, cs, sn);
+        table[((size_t)r * half + j) * 2]     = cs;
+        table[((size_t)r * half + j) * 2 + 1] = sn;
+    }
+}
+void launch_verify_rotary(float* table, int len, int R, int rot, hipStream_t s)
+{
+    if (rot <= 0) {
+        return;
+    }
+    hipLaunchKernelGGL(k_verify_rotary, dim3(R), dim3(64), 0, s, table, len, rot);
+    FTCF_HIP_CHECK(hipGetLastError());
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// drafting
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_ngram_draft(const int* __restrict__ tokens, int n, const int* d_n, int K, int N,
+                                                     const int* __restrict__ ext, int ext_base, int ext_len, int* draft, int* n_draft,
+                                                     int* h_n_draft, const int* d_stop)
+{
+    __shared__ int s_best;
+    if (d_n) {
+        n = *d_n;
+    }
+    int cnt = 0;
+    if (d_stop && *d_stop) {
+        // every row has finished: nothing to draft
+    }
+    else if (ext) {
+        if (threadIdx.x == 0) {
+            const int j = n - ext_base;
+            while (j >= 0 && cnt < K && j + cnt < ext_len && ext[j + cnt] >= 0) {
+                draft[cnt] = ext[j + cnt];
+                cnt++;
+            }
+        }
+    }
+    else {
+        int fs = -1, fg = 0;
+        for (int g = min(N, n - 1); g >= 1; g--) {
+            if (threadIdx.x == 0) {
+                s_best = -1;
+            }
+            __syncthreads();
+            int best = -1;
+            for (int s = threadIdx.x; s <= n - g - 1; s += 256) {  // (increasing: the last hit of a thread is its largest)
+                bool eq = true;
+                for (int i = 0; i < g; i++) {
+                    eq &= tokens[s + i] == tokens[n - g + i];
+                }
+                if (eq) {
+                    best = s;
+                }
+            }
+            if (best >= 0) {
+                atomicMax(&s_best, best);
+            }
+            __syncthreads();
+            const int b = s_best;
+            __syncthreads();
+            if (b >= 0) {
+                fs = b;
+                fg = g;
+                break;
+            }
+        }
+        if (fs >= 0) {
+            cnt = min(K, n - (fs + fg));
+            for (int i = threadIdx.x; i < cnt; i += 256) {
+                draft[i] = tokens[fs + fg + i];
+            }
+        }
+    }
+    if (threadIdx.x == 0) {
+        *n_draft = cnt;
+        if (h_n_draft) {
+            *h_n_draft = cnt;
+        }
+    }
+}
+
+void launch_ngram_draft(const int* tokens, int n, const int* d_n, int K, int N, const int* ext, int ext_base, int ext_len, int* draft,
+                        int* n_draft, int* h_n_draft, const int* d_stop, hipStream_t s)
+{
+    FTCF_CHECK_ARG(K >= 1 && K <= VERIFY_MAX_ROWS - 1 && N >= 1 && N <= 8, "draft: 1 <= K <= 15 and 1 <= N <= 8");
+    FTCF_CHECK_ARG(draft && n_draft && (tokens || ext), "draft: NULL tensor");
+    hipLaunchKernelGGL(k_ngram_draft, dim3(1), dim3(256), 0, s, tokens, n, d_n, K, N, ext, ext_base, ext_len, draft, n_draft, h_n_draft,
+                       d_stop);
+    FTCF_HIP_CHECK(hipGetLastError());
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// the pass's input rows and the acceptance rule
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_verify_embed(f16* x, const f16* __restrict__ wte, const int* __restrict__ tokens,
+                                                      const int* __restrict__ draft, int step, int H)
+{
+    const int  r   = blockIdx.x;
+    const int  id  = r == 0 ? tokens[step - 1] : draft[r - 1];
+    const f16* src = wte + (size_t)id * H;
+    f16*       dst = x + (size_t)r * H;
+    for (int i = threadIdx.x * 8; i < H; i += blockDim.x * 8) {
+        *reinterpret_cast<f16x8*>(dst + i) = *reinterpret_cast<const f16x8*>(src + i);
+    }
+}
+void launch_verify_embed(f16* x, const f16* wte, const int* tokens, const int* draft, int step, int R, int H, hipStream_t s)
+{
+    FTCF_CHECK_ARG(H % 8 == 0 && R >= 1 && R <= VERIFY_MAX_ROWS && step >= 1, "verify embed: bad arguments");
+    hipLaunchKernelGGL(k_verify_embed, dim3(R), dim3(256), 0, s, x, wte, tokens, draft, step, H);
+    FTCF_HIP_CHECK(hipGetLastError());
+}
+
+// a[r] = argmax of row r: value descending, index ascending on ties (the rule of the greedy / top-k kernels)
+__global__ __launch_bounds__(256) void k_verify_argmax(const float* __restrict__ logits, int V, int* out)
+{
+    __shared__ float s_v[4];
+    __shared__ int   s_i[4];
+    const int    r = blockIdx.x, lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const float* l = logits + (size_t)r * V;
+    float        bv = -INFINITY;
+    int          bi = 0x7fffffff;
+    for (int i = threadIdx.x; i < V; i += 256) {
+        const float v = l[i];
+        if (v > bv || (v == bv && i < bi)) {
+            bv = v;
+            bi = i;
+        }
+    }
+    for (int o = 32; o >= 1; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int   oi = __shfl_xor(bi, o, 64);
+        if (ov > bv || (ov == bv && oi < bi)) {
+            bv = ov;
+            bi = oi;
+        }
+    }
+    if (lane == 0) {
+        s_v[wid] = bv;
+        s_i[wid] = bi;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; w++) {
+            if (s_v[w] > bv || (s_v[w] == bv && s_i[w] < bi)) {
+                bv = s_v[w];
+                bi = s_i[w];
+            }
+        }
+        out[r] = bi < V ? bi : 0;
+    }
+}
+
+__global__ void k_verify_accept(const VerifyAcceptParams p)
+{
+    if (threadIdx.x != 0) {
+        return;
+    }
+    const int* a = p.argmax_ws;
+    int        m = 0;
+    while (m < p.R - 1 && p.draft[m] == a[m]) {
+        m++;
+    }
+    int e = 0, fin = 0;
+    for (int i = 0; i <= m && !fin; i++) {  // the accepted drafts and the model's own next token, cut after the first end_id
+        p.output_ids[p.step + i] = a[i];
+        e++;
+        fin = a[i] == p.end_id;
+    }
+    p.seq_len[0] += e;
+    p.finished[0]         = (uint8_t)fin;
+    p.state->all_finished = fin;
+    p.state->steps_done += e;
+    p.state->step = p.step + e;
+    p.h_flags[1]  = p.step + e - 1;
+    p.h_flags[3]  = e;
+    p.h_flags[5]  = m < e ? m : e;  // drafts that became output tokens
+    __threadfence_system();
+    p.h_flags[0] = fin;
+}
+
+void launch_verify_accept(const VerifyAcceptParams& p, hipStream_t s)
+{
+    FTCF_CHECK_ARG(p.R >= 1 && p.R <= VERIFY_MAX_ROWS && p.V >= 1, "verify accept: bad arguments");
+    hipLaunchKernelGGL(k_verify_argmax, dim3(p.R), dim3(256), 0, s, p.logits, p.V, p.argmax_ws);
+    hipLaunchKernelGGL(k_verify_accept, dim3(1), dim3(64), 0, s, p);
+    FTCF_HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace ftcf

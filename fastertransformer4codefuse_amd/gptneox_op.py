@@ -23,6 +23,27 @@ def _check_input(t, name, dtype=None):
         raise RuntimeError(f"{name} has invalid dtype {t.dtype}, expected {dtype}")
 
 
+def check_speculative_args(speculative_tokens, speculative_ngram, draft_ids, output_len):
+    """Validates forward()'s speculative-decoding arguments (include/ftcf.h ftcf_forward_args) and returns (K, N): K drafted tokens
+    per verify pass (0 = off), N the longest n-gram the prompt lookup matches (0 = the engine's default, 3).  Host-side only."""
+    K = 0 if speculative_tokens is None else int(speculative_tokens)
+    N = 0 if speculative_ngram is None else int(speculative_ngram)
+    if not 0 <= K <= 15:
+        raise RuntimeError("speculative_tokens must be in [0, 15]")
+    if not 0 <= N <= 8:
+        raise RuntimeError("speculative_ngram must be in [0, 8]")
+    if draft_ids is not None:
+        if K == 0:
+            raise RuntimeError("draft_ids needs speculative_tokens >= 1")
+        if draft_ids.dtype != torch.int32 or draft_ids.dim() != 1 or not draft_ids.is_contiguous():
+            raise RuntimeError("draft_ids must be a contiguous int32 vector")
+        if int(draft_ids.numel()) != int(output_len):
+            raise RuntimeError("draft_ids must hold output_len entries")
+        if not draft_ids.is_cuda:
+            raise RuntimeError("draft_ids must be a CUDA tensor")
+    return K, N
+
+
 class LocalTensorParallelGroup:
     """Test infrastructure: the ranks of a tensor-parallel job inside ONE process on ONE device (one host thread per rank,
     see include/ftcf.h `ftcf_comm_init_local`).  Pass one shared instance as `comm` to every rank's GptNeoXOp."""
@@ -168,11 +189,19 @@ class GptNeoXOp:
     def forward(self, input_ids, input_lengths, output_len, beam_width=None, top_k=None, top_p=None,
                 beam_search_diversity_rate=None, temperature=None, len_penalty=None, repetition_penalty=None,
                 random_seed=None, stop_words_list=None, optional_last_tokens=None, return_cum_log_probs=None,
-                callback=None, _debug_logits=None, return_output_log_probs=None, return_context_log_probs=None):
+                callback=None, _debug_logits=None, return_output_log_probs=None, return_context_log_probs=None,
+                speculative_tokens=None, speculative_ngram=None, draft_ids=None):
         """Returns [output_ids, sequence_lengths], then cum_log_probs [B, beam], output_log_probs [B, beam, output_len]
         (GptNeoX.cc:967-987: each generated token's log-probability, 0 after a row has finished) and context_log_probs
         [B, max_input_len] (log P(input_ids[b, t] | input_ids[b, < t]) at t >= 1, 0 at t = 0 and in the padding), each
-        only when it was asked for."""
+        only when it was asked for.
+
+        speculative_tokens = K in 1..15 switches speculative greedy decoding on: up to K tokens are
+        drafted per step -- by prompt lookup over the last speculative_ngram tokens (default 3), or taken from draft_ids (int32
+        CUDA [output_len]: the guess for each generated position, negative = no guess) -- and verified in one decoder pass.
+        The tokens are those of the same request without it; a request the feature does not cover runs as before and
+        stats()["spec_active"] is 0."""
+        spec_k, spec_n = check_speculative_args(speculative_tokens, speculative_ngram, draft_ids, output_len)
         _check_input(input_ids, "input_ids", torch.int32)
         if input_ids.dim() != 2:
             raise RuntimeError("input_ids must be a matrix")
@@ -241,6 +270,9 @@ class GptNeoXOp:
             a.output_log_probs = output_log_probs.data_ptr()
         if context_log_probs is not None:
             a.context_log_probs = context_log_probs.data_ptr()
+        a.speculative_tokens, a.speculative_ngram = spec_k, spec_n
+        if draft_ids is not None:
+            a.draft_ids = draft_ids.data_ptr()
         capi.check(capi.lib().ftcf_gptneox_forward(self._h, C.byref(a)))
         out = [output_ids, sequence_lengths]
         for t in (cum_log_probs, output_log_probs, context_log_probs):

@@ -100,6 +100,21 @@ int ftcf_masked_multihead_attention(const void* qkv, const void* qkv_bias, void*
                                     const uint8_t* finished, int B, int nh, int dh, int rot, int s_max, int step,
                                     void* ctx, void* workspace, size_t workspace_bytes, void* stream);
 size_t ftcf_masked_multihead_attention_workspace(int B, int nh, int dh, int s_max);
+/* Speculative decoding's verify attention (no counterpart in the reference): decode attention for R
+ * consecutive NEW tokens of ONE sequence.  qkv [R, 3*nh*dh] fp16 are the tokens of positions len .. len + R - 1 of the sequence in
+ * row `cache_row` of k_cache / v_cache [rows, nh, s_max, dh], whose positions [0, len) are cached.  Row i: bias, NeoX rotary at
+ * len + i, its K / V rows stored at len + i, ctx[i] [nh*dh] = soft-max attention of its rotated q over positions [0, len + i] --
+ * the arithmetic and rounding points of ftcf_masked_multihead_attention for a step at that position.  The cached keys are
+ * read once for all rows.  1 <= R <= 16, len + R <= s_max <= ~32000, dh 64 / 128.  Nothing outside rows [len, len + R) of that cache
+ * row is written.  Deterministic: two calls give identical bits.  workspace: ftcf_verify_attention_workspace bytes. */
+int ftcf_verify_attention(const void* qkv, const void* qkv_bias, void* k_cache, void* v_cache, int cache_row, int len, int R,
+                          int nh, int dh, int rot, int s_max, void* ctx, void* workspace, size_t workspace_bytes, void* stream);
+size_t ftcf_verify_attention_workspace(int R, int nh, int dh, int s_max);
+/* Prompt-lookup ("n-gram") drafting over the tokens so far t[0, n) (device int32): for g = min(N, n - 1) down to 1, among the
+ * start indices s <= n - g - 1 with t[s, s + g) == t[n - g, n) the LARGEST s is taken; the first g that has one wins and the
+ * draft is t[s + g, min(s + g + K, n)).  No match: zero drafts.  draft [K] and n_draft [1] are device int32.  1 <= K <= 15,
+ * 1 <= N <= 8. */
+int ftcf_ngram_draft(const int* tokens, int n, int K, int N, int* draft, int* n_draft, void* stream);
 /* GptContextAttentionLayer<T>::forward minus the two projections (layers/attention_layers/
  * GptContextAttentionLayer.cc:142-345): bias + NeoX rotary + cache fill + causal masked softmax(QK^T)V.
  * qkv [B*S, 3*Hl] fp16 (row = b*S+s), ctx [B*S, Hl] fp16. */
@@ -239,6 +254,21 @@ typedef struct {
      *   fp32 engines are refused. */
     float* output_log_probs;
     float* context_log_probs;
+    /* Speculative greedy decoding (appended, 0 / NULL = off and every bit as before).  With
+     * speculative_tokens = K in 1..15 a step drafts up to K tokens -- the continuation of the most recent earlier occurrence of
+     * the last speculative_ngram tokens (N in 1..8, 0 = 3; shorter matches down to one token are tried), or, with draft_ids
+     * (device [output_len]), draft_ids[j .. j + K) for a step that starts at generated index j (cut at the first negative id) --
+     * and verifies them in ONE decoder pass over drafts + 1 rows; the accepted drafts and the model's own next token are emitted,
+     * exactly the tokens plain greedy decoding produces one at a time.  A step with no draft is the plain step; the first step
+     * of a request never drafts.  Eligible:
+     * batch 1 with input_lengths[0] == max_input_len, beam_width 1, greedy (top_k <= 1 and top_p 0), repetition_penalty 1, no
+     * min_length / optional_last_tokens / stop words / callback / return_cum_log_probs / output_log_probs / debug_logits, fp16
+     * engine (int8_mode 0 / 1), parallel residual, tensor_para_size 1, size_per_head 64 / 128, hidden and inter sizes multiples
+     * of 64, at most ~32000 positions.  An ineligible request is not an error: it runs as without the fields and ftcf_forward_stats.spec_active says so.
+     * speculative_tokens outside 0..15 or speculative_ngram outside 0..8: FTCF_ERR_INVALID_ARG. */
+    int        speculative_tokens;
+    int        speculative_ngram;
+    const int* draft_ids;
 } ftcf_forward_args;
 
 typedef struct {
@@ -268,6 +298,9 @@ typedef struct {
     /* decode_path 1: how the one- / two-row kernel ran its out-proj / FFN2 stage: 0 K pieces merged by an owner (two hops at the
      * layer boundary), 1 own-group layout (one hop; FTCF_PERSIST_OWN) */
     int   persist_layout;
+    /* speculative decoding (appended): did the last request speculate, its verify passes, the draft tokens proposed to them and
+     * the draft tokens accepted (decode_steps keeps counting generated tokens) */
+    int   spec_active, spec_steps, spec_drafted, spec_accepted;
 } ftcf_forward_stats;
 
 int ftcf_gptneox_create(const ftcf_gptneox_config* cfg, const ftcf_gptneox_weights* w, ftcf_gptneox_t* out);

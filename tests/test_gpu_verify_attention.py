@@ -1,0 +1,205 @@
+"""-m gpu: speculative decoding's verify attention at kernel level (include/ftcf.h ftcf_verify_attention) against a plain float64
+numpy reference of R decode steps of one sequence, and against ftcf_masked_multihead_attention run step by step.
+
+The reference keeps the rounding points listed in tests/test_gpu_paged_attention.py's docstring: q, k, v = half(qkv + bias); NeoX
+rotary at position len + i with the angle in fp32, cos / sin and the rotation in float64, the rotated q and k rounded to half;
+scores, soft-max (with the +1e-6 of the normaliser) and P.V in float64; the context rounded to half once.  Row i sees the cached
+keys [0, len) and the new keys 0 .. i.  Caches start as a sentinel pattern, so a write anywhere but rows [len, len + R) of the
+sequence's cache row shows."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from tests.test_gpu_paged_attention import CTX_FLOOR, _half, _rotary, _sentinel, _ulps
+
+pytestmark = [pytest.mark.gpu, pytest.mark.timeout(900)]
+
+capi = None
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _lib():
+    global capi
+    from fastertransformer4codefuse_amd import capi as _c
+    capi = _c
+    capi.require_gpu()
+    yield
+
+
+def sp():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+# The project's own bounds for these rounding points and this metric (tests/test_gpu_paged_attention.py: CTX_ULPS = 6,
+# K_ULPS = 2).  The kernel keeps the dot2 / fp32 arithmetic of the decode attention (no MFMA accumulation order), so they
+# are kept as they are.  Measured on MI355X over every case below: worst context error 2.00 ulp (R 16, len 3000, dh 64, full
+# rotary, row 11; the decode attention run step by step on the same case: 2.00), worst appended-key error 1.00 ulp (len 1023 and
+# 3000, full rotary); the appended K / V rows were bit-identical to the decode attention's in every case.
+CTX_ULPS = 6
+K_ULPS = 2
+
+
+def _unrotate(x, pos, rot):
+    """The half vector whose NeoX rotation at `pos` is (about) x: the rotation by the negative angle, in float64."""
+    if rot == 0:
+        return x
+    j = np.arange(rot // 2, dtype=np.float32)
+    den = (10000.0 ** ((2 * j) / np.float32(rot)).astype(np.float64)).astype(np.float32)
+    ang = (np.float32(pos) / den).astype(np.float64)
+    cs, sn = np.cos(ang), np.sin(ang)
+    a, b = x[..., :rot // 2].astype(np.float64), x[..., rot // 2:rot].astype(np.float64)
+    out = x.copy()
+    out[..., :rot // 2] = _half(cs * a + sn * b)
+    out[..., rot // 2:rot] = _half(cs * b - sn * a)
+    return out
+
+
+def reference(qkv, bias, kc, vc, ln, nh, dh, rot):
+    """R decode steps of one sequence in float64.  qkv [R, 3, nh, dh] fp16, bias [3, nh, dh] fp16, kc / vc [nh, s_max, dh] fp16 (the
+    sequence's cache row).  -> ctx [R, nh, dh], k_new, v_new [R, nh, dh] fp16 and the magnitudes _ulps measures them at."""
+    R = qkv.shape[0]
+    x = _half(qkv.astype(np.float64) + bias.astype(np.float64)[None])
+    q = np.stack([_rotary(x[i, 0], ln + i, rot) for i in range(R)])
+    k = np.stack([_rotary(x[i, 1], ln + i, rot) for i in range(R)])
+    v = x[:, 2]
+    ctx = np.zeros((R, nh, dh), dtype=np.float16)
+    c_mag = np.zeros((R, nh, dh))
+    for i in range(R):
+        keys = np.concatenate([kc[:, :ln].astype(np.float64), k[:i + 1].astype(np.float64).transpose(1, 0, 2)], axis=1)  # [nh, t, dh]
+        vals = np.concatenate([vc[:, :ln].astype(np.float64), v[:i + 1].astype(np.float64).transpose(1, 0, 2)], axis=1)
+        s = np.einsum("htd,hd->ht", keys, q[i].astype(np.float64)) / np.sqrt(dh)
+        p = np.exp(s - s.max(axis=1, keepdims=True))
+        den = (p.sum(axis=1) + 1e-6)[:, None]
+        ctx[i] = _half(np.einsum("ht,htd->hd", p, vals) / den)
+        c_mag[i] = np.einsum("ht,htd->hd", p, np.abs(vals)) / den
+    xk = np.abs(x[:, 1].astype(np.float64))
+    k_mag = xk.copy()
+    k_mag[..., :rot // 2] = k_mag[..., rot // 2:rot] = xk[..., :rot // 2] + xk[..., rot // 2:rot]
+    return ctx, k, v, c_mag, k_mag
+
+
+def _verify(qkv, bias, Kc, Vc, row, ln, R, nh, dh, rot, s_max, ctx):
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.int16)).cuda().view(torch.float16)
+    keep = [d(qkv), d(bias)]
+    wsb = capi.lib().ftcf_verify_attention_workspace(R, nh, dh, s_max)
+    ws = torch.empty(wsb, dtype=torch.uint8, device="cuda")
+    capi.check(capi.lib().ftcf_verify_attention(capi.vp(keep[0]), capi.vp(keep[1]), capi.vp(Kc), capi.vp(Vc), row, ln, R, nh, dh, rot,
+                                                s_max, capi.vp(ctx), capi.vp(ws), C.c_size_t(wsb), sp()))
+    torch.cuda.synchronize()
+
+
+def _mmha_steps(qkv, bias, Kc, Vc, row, ln, R, nh, dh, rot, s_max):
+    """ftcf_masked_multihead_attention, one call per row, on the sequence's cache row (a one-row cache of its own)."""
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.int16)).cuda().view(torch.float16)
+    b = d(bias)
+    wsb = capi.lib().ftcf_masked_multihead_attention_workspace(1, nh, dh, s_max)
+    ws = torch.empty(wsb, dtype=torch.uint8, device="cuda")
+    out = torch.zeros((R, nh * dh), dtype=torch.float16, device="cuda")
+    for i in range(R):
+        q = d(qkv[i:i + 1])
+        sl = torch.tensor([ln + i], dtype=torch.int32, device="cuda")
+        capi.check(capi.lib().ftcf_masked_multihead_attention(
+            capi.vp(q), capi.vp(b), capi.vp(Kc[row]), capi.vp(Vc[row]), capi.vp(sl), None, None, None, 1, nh, dh, rot, s_max,
+            ln + i + 1, capi.vp(out[i]), capi.vp(ws), C.c_size_t(wsb), sp()))
+        torch.cuda.synchronize()
+    return out.cpu().numpy().view(np.uint16).reshape(R, nh, dh)
+
+
+def _case(R, ln, dh, rot, nh=3, rows=1, row=0, slack=5, seed=0, stepwise=True):
+    rng = np.random.RandomState(seed + 1000 * R + ln)
+    s_max = ln + R + slack
+    kb = _sentinel(rng, rows * nh * s_max * dh).reshape(rows, nh, s_max, dh)
+    vb = _sentinel(rng, rows * nh * s_max * dh).reshape(rows, nh, s_max, dh)
+    kb[row, :, :ln] = _half(rng.randn(nh, ln, dh)).view(np.uint16)
+    vb[row, :, :ln] = _half(rng.randn(nh, ln, dh)).view(np.uint16)
+    qkv = _half(rng.randn(R, 3, nh, dh))
+    bias = _half(0.1 * rng.randn(3, nh, dh))
+    # planted keys: the last cached key scores ln(n) against row 0's rotated q, new key i - 1 against row i's (each then weighs
+    # about a quarter of that row's soft-max at any length): a dropped key, or a row that reads a later row's key, is far off
+    x = _half(qkv.astype(np.float64) + bias.astype(np.float64)[None])
+    for i in range(R):
+        n = ln + i + 1
+        if n < 3:
+            continue
+        q = _rotary(x[i, 0], ln + i, rot).astype(np.float64)
+        k = _half(q * (np.log(n) * np.sqrt(dh) / (q * q).sum(axis=1, keepdims=True)))
+        if i == 0:
+            if ln >= 1:
+                kb[row, :, ln - 1] = k.view(np.uint16)
+        else:
+            qkv[i - 1, 1] = _half(_unrotate(k, ln + i - 1, rot).astype(np.float64) - bias[1].astype(np.float64))
+    ref, k_new, v_new, c_mag, k_mag = reference(qkv, bias, kb[row].view(np.float16), vb[row].view(np.float16), ln, nh, dh, rot)
+
+    dev = lambda a: torch.from_numpy(a.view(np.int16).copy()).cuda()
+    Kc, Vc = dev(kb), dev(vb)
+    ctx = dev(_sentinel(rng, R * nh * dh).reshape(R, nh, dh))
+    _verify(qkv, bias, Kc, Vc, row, ln, R, nh, dh, rot, s_max, ctx)
+    ka, va, ca = (t.cpu().numpy().view(np.uint16) for t in (Kc, Vc, ctx))
+    ec = _ulps(ca.view(np.float16), ref, CTX_FLOOR * c_mag)
+    ek = _ulps(ka[row, :, ln:ln + R].transpose(1, 0, 2).view(np.float16), k_new, k_mag)
+    worst_row = int(np.unravel_index(int(ec.argmax()), ec.shape)[0])
+    print(f"[R {R} len {ln} dh {dh} rot {rot}: ctx {ec.max():.2f} ulp (row {worst_row}), k {ek.max():.2f} ulp] ", end="")
+    assert ec.max() <= CTX_ULPS, ("ctx (row, head, dim)", float(ec.max()), np.unravel_index(int(ec.argmax()), ec.shape))
+    assert ek.max() <= K_ULPS, ("appended k", float(ek.max()))
+    assert np.array_equal(va[row, :, ln:ln + R].transpose(1, 0, 2), v_new.view(np.uint16)), "appended v not bit exact"
+    wk, wv = kb.copy(), vb.copy()
+    wk[row, :, ln:ln + R] = ka[row, :, ln:ln + R]
+    wv[row, :, ln:ln + R] = va[row, :, ln:ln + R]
+    for name, got, want in (("k_cache", ka, wk), ("v_cache", va, wv)):
+        bad = np.argwhere(got != want)
+        assert bad.size == 0, (name, "stray writes (row, head, position, dim)", bad[:8].tolist())
+    # a second launch over what the first one left: the same bits
+    ctx2 = torch.zeros_like(ctx)
+    _verify(qkv, bias, Kc, Vc, row, ln, R, nh, dh, rot, s_max, ctx2)
+    assert np.array_equal(ctx2.cpu().numpy().view(np.uint16), ca)
+    assert np.array_equal(Kc.cpu().numpy().view(np.uint16), ka) and np.array_equal(Vc.cpu().numpy().view(np.uint16), va)
+    if stepwise:
+        # the decode attention, step by step on a copy of the cache: within the same bound of the same reference; the appended rows
+        # bit-identical (the rotation code -- rotary_coef / rotary_apply of attn_device.hip.h -- is shared)
+        K2, V2 = dev(kb), dev(vb)
+        cs = _mmha_steps(qkv, bias, K2, V2, row, ln, R, nh, dh, rot, s_max)
+        es = _ulps(cs.view(np.float16), ref, CTX_FLOOR * c_mag)
+        print(f"[step by step: ctx {es.max():.2f} ulp] ", end="")
+        assert es.max() <= CTX_ULPS, ("step-by-step ctx", float(es.max()))
+        k2, v2 = K2.cpu().numpy().view(np.uint16), V2.cpu().numpy().view(np.uint16)
+        assert np.array_equal(k2, ka) and np.array_equal(v2, va), "appended K / V rows differ from the decode attention's"
+
+
+@pytest.mark.parametrize("dh,rot", [(128, 32), (128, 128), (64, 16), (64, 64)])
+@pytest.mark.parametrize("ln", [0, 1, 15, 16, 17, 1023, 3000])
+@pytest.mark.parametrize("R", [1, 2, 5, 16])
+def test_verify_attention_against_float64_and_the_decode_attention(R, ln, dh, rot):
+    _case(R, ln, dh, rot, seed=dh + rot)
+
+
+@pytest.mark.parametrize("R,ln,dh,rot", [(16, 1008, 128, 32), (5, 59, 64, 64), (1, 0, 128, 128), (16, 0, 64, 16)])
+def test_verify_attention_fills_the_cache_to_its_last_position(R, ln, dh, rot):
+    """len + R == s_max: the last new row is the cache's last."""
+    _case(R, ln, dh, rot, slack=0, seed=7)
+
+
+@pytest.mark.parametrize("R,ln,dh,rot,row", [(5, 300, 128, 32, 2), (16, 17, 64, 16, 1), (2, 1023, 128, 128, 1)])
+def test_verify_attention_in_a_row_of_a_multi_row_cache(R, ln, dh, rot, row):
+    _case(R, ln, dh, rot, rows=3, row=row, seed=11)
+
+
+def test_verify_attention_with_forty_heads_and_no_rotary():
+    _case(16, 1500, 128, 0, nh=40, seed=3, stepwise=False)
+    _case(4, 700, 64, 0, nh=40, seed=4, stepwise=False)
+
+
+def test_verify_attention_refuses_bad_geometry():
+    Kc = torch.zeros((1, 2, 32, 128), dtype=torch.float16, device="cuda")
+    q = torch.zeros((17, 3 * 2 * 128), dtype=torch.float16, device="cuda")
+    ctx = torch.zeros((17, 2 * 128), dtype=torch.float16, device="cuda")
+    ws = torch.empty(1 << 22, dtype=torch.uint8, device="cuda")
+    call = lambda ln, R, dh, s_max: capi.lib().ftcf_verify_attention(capi.vp(q), None, capi.vp(Kc), capi.vp(Kc), 0, ln, R, 2, dh, 32, s_max,
+                                                                     capi.vp(ctx), capi.vp(ws), C.c_size_t(1 << 22), sp())
+    assert call(0, 17, 128, 32) != 0  # more than 16 rows
+    assert call(0, 0, 128, 32) != 0
+    assert call(30, 3, 128, 32) != 0  # len + R > s_max
+    assert call(0, 2, 96, 32) != 0  # head size
+    assert call(10, 3, 128, 32) == 0
+    torch.cuda.synchronize()

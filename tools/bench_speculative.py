@@ -1,0 +1,93 @@
+"""Speculative greedy decoding: what a verify pass costs and what it returns.
+
+The bench.py model (13B-shaped int8, synthetic weights), one request of 1024 prompt tokens and 512 generated ones.  Synthetic
+weights do not copy from their prompt, so acceptance is IMPOSED through draft_ids: a first plain run records the greedy
+tokens, the speculative runs draft them with every p-th draft replaced by a different token (p = 0: none).  Per K in {2, 4, 8}
+and acceptance setting: milliseconds per verify pass (the request's token-loop time minus its plain steps at the plain run's
+rate, over its passes), tokens per pass, tokens/s, next to the plain run's; break-even tokens per pass = verify-pass time /
+plain step time.  Plain and speculative runs alternate inside the one process, after a warm-up of each shape.
+
+    python tools/bench_speculative.py [--prompt-len 1024] [--out-len 512] [--rounds 3] [--ks 2,4,8] [--every 0,4,2,1]
+"""
+import argparse
+import json
+import os
+import sys
+import types
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from fastertransformer4codefuse_amd import capi  # noqa: E402
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--prompt-len", type=int, default=1024)
+    p.add_argument("--out-len", type=int, default=512)
+    p.add_argument("--rounds", type=int, default=3)
+    p.add_argument("--ks", default="2,4,8")
+    p.add_argument("--every", default="0,4,2,1", help="corrupt every p-th draft (0: none, 1: all)")
+    a = p.parse_args()
+    capi.require_gpu()
+    import bench
+    from fastertransformer4codefuse_amd.gptneox_op import GptNeoXOp
+    m = types.SimpleNamespace(layers=40, heads=40, head_dim=128, inter=20480, vocab=100864, dtype="int8")
+    dev = torch.device("cuda", 0)
+    print("device:", torch.cuda.get_device_name(0), flush=True)
+    weights, int8_w, scales = bench.synth_weights(m, 1, dev)
+    op = GptNeoXOp(None, 0, m.heads, m.head_dim, m.inter, m.layers, m.vocab, 32, 0, 2, 1, 1, 1, 2048, True, weights, int8_w, scales)
+    S, out_len = a.prompt_len, a.out_len
+    ids = torch.randint(3, m.vocab, (1, S), generator=torch.Generator().manual_seed(42), dtype=torch.int32).to(dev)
+    lens = torch.full((1,), S, dtype=torch.int32, device=dev)
+    k1 = torch.tensor([1], dtype=torch.int32)
+
+    def run(n_out=out_len, **kw):
+        o = op.forward(ids, lens, n_out, 1, k1, **kw)
+        torch.cuda.synchronize()
+        return o[0][0, 0, S:].cpu().tolist(), int(o[1][0, 0].item()) - S, op.stats()
+
+    gen, n_gen, st = run()
+    gen = gen[:n_gen]
+    print(json.dumps(dict(plain_tokens=n_gen, decode_path=st["decode_path"], note="tokens generated before the end token" if n_gen < out_len else "")),
+          flush=True)
+    wrong = lambda t: 3 + (t - 3 + 1) % (m.vocab - 3)
+
+    def drafts(every):
+        d = [(wrong(t) if every and i % every == every - 1 else t) for i, t in enumerate(gen)]
+        return torch.tensor(d + [3] * (out_len - len(d)), dtype=torch.int32, device=dev)
+
+    ks = [int(x) for x in a.ks.split(",") if x]
+    every = [int(x) for x in a.every.split(",") if x]
+    for K in ks:  # warm-up of each shape (arena, graph capture of the plain step, every kernel's code object)
+        run(32)
+        run(32, speculative_tokens=K, draft_ids=drafts(0)[:32].contiguous())
+    rows = []
+    for K in ks:
+        for ev in every:
+            d = drafts(ev)
+            best = None
+            for _ in range(a.rounds):
+                _, n_p, sp = run()  # plain, then speculative: alternating
+                toks, n_s, ss = run(speculative_tokens=K, draft_ids=d)
+                plain_ms = sp["decode_ms"] / sp["decode_steps"]
+                n_plain = ss["decode_steps"] - ss["spec_accepted"] - ss["spec_steps"]
+                pass_ms = (ss["decode_ms"] - n_plain * plain_ms) / max(1, ss["spec_steps"])
+                r = dict(K=K, corrupt_every=ev, plain_ms_per_token=round(plain_ms, 4), plain_tok_s=round(1e3 / plain_ms, 1),
+                         spec_active=ss["spec_active"], passes=ss["spec_steps"], drafted=ss["spec_drafted"], accepted=ss["spec_accepted"],
+                         tokens_per_pass=round((ss["spec_accepted"] + ss["spec_steps"]) / max(1, ss["spec_steps"]), 3),
+                         ms_per_pass=round(pass_ms, 4), spec_tok_s=round(ss["decode_steps"] / ss["decode_ms"] * 1e3, 1),
+                         break_even_tokens_per_pass=round(pass_ms / plain_ms, 3),
+                         speedup=round((ss["decode_steps"] / ss["decode_ms"]) / (sp["decode_steps"] / sp["decode_ms"]), 3),
+                         tokens_differ=sum(1 for x, y in zip(toks[:n_s], gen) if x != y) + abs(n_s - n_gen))
+                if best is None or r["spec_tok_s"] > best["spec_tok_s"]:
+                    best = r
+            rows.append(best)
+            print(json.dumps(best), flush=True)
+    return rows
+
+
+if __name__ == "__main__":
+    main()
