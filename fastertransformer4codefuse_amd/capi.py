@@ -57,6 +57,21 @@ class ForwardArgs(C.Structure):
         ("speculative_tokens", C.c_int), ("speculative_ngram", C.c_int), ("draft_ids", C.c_void_p)]
 
 
+class SmallmProblem(C.Structure):  # ftcf_smallm_problem
+    _fields_ = [("A", C.c_void_p), ("W", C.c_void_p), ("scale", C.c_void_p), ("bias", C.c_void_p), ("act", C.c_int),
+                ("C", C.c_void_p), ("n", C.c_int), ("k", C.c_int)]
+
+
+class LnGemvArgs(C.Structure):  # ftcf_ln_gemv_args
+    _fields_ = [(n, C.c_void_p) for n in ("x", "gamma0", "beta0", "gamma1", "beta1", "W0", "W1", "scale0", "scale1", "bias1",
+                                          "out0", "out1")] + [("K", C.c_int), ("N0", C.c_int), ("N1", C.c_int), ("eps", C.c_float)]
+
+
+class ResidualGemvArgs(C.Structure):  # ftcf_residual_gemv_args
+    _fields_ = [(n, C.c_void_p) for n in ("x_a", "x_b", "W_a", "W_b", "scale_a", "scale_b", "bias", "x_in", "out")] + [
+        (n, C.c_int) for n in ("N", "K_a", "K_b", "tp", "inplace_variant")]
+
+
 class ForwardStats(C.Structure):
     _fields_ = [("prefill_ms", C.c_float), ("decode_ms", C.c_float), ("decode_steps", C.c_int),
                 ("gemv_ms_sum", C.c_float), ("gemv_launches", C.c_long), ("gemv_bytes", C.c_double),
@@ -72,7 +87,9 @@ EXPORTED = [
     "ftcf_last_error", "ftcf_version", "ftcf_device_count", "ftcf_symmetric_quantize_int8",
     "ftcf_int8_rowmajor_to_tiled", "ftcf_int8_tiled_to_rowmajor", "ftcf_int8_cuda_sm80_to_rowmajor",
     "ftcf_int8_rowmajor_to_cuda_sm80", "ftcf_fp16_rowmajor_to_tiled",
-    "ftcf_fpA_intB_gemm", "ftcf_fp16_gemm", "ftcf_lm_head", "ftcf_lm_head_log_probs", "ftcf_layernorm", "ftcf_add_bias_attn_ffn_residual",
+    "ftcf_fpA_intB_gemm", "ftcf_fp16_gemm", "ftcf_lm_head", "ftcf_lm_head_layernorm", "ftcf_lm_head_log_probs",
+    "ftcf_gemm_smallm_group", "ftcf_gemm_smallm_workspace_bytes", "ftcf_gemm_smallm_ticket_bytes",
+    "ftcf_residual_dual_layernorm", "ftcf_add_bias_residual", "ftcf_ln_gemv", "ftcf_residual_gemv", "ftcf_residual_gemv_workspace_bytes", "ftcf_layernorm", "ftcf_add_bias_attn_ffn_residual",
     "ftcf_masked_multihead_attention", "ftcf_masked_multihead_attention_workspace", "ftcf_context_attention",
     "ftcf_verify_attention", "ftcf_verify_attention_workspace", "ftcf_ngram_draft",
     "ftcf_paged_attention", "ftcf_scatter_kv_to_pages", "ftcf_gather_pages_to_kv",
@@ -98,6 +115,9 @@ def lib():
         _lib.ftcf_masked_multihead_attention_workspace.restype = C.c_size_t
         if hasattr(_lib, "ftcf_verify_attention_workspace"):  # (FTCF_LIB_NAME may name an older build: the call itself then fails)
             _lib.ftcf_verify_attention_workspace.restype = C.c_size_t
+        for name in ("ftcf_gemm_smallm_workspace_bytes", "ftcf_gemm_smallm_ticket_bytes", "ftcf_residual_gemv_workspace_bytes"):
+            if hasattr(_lib, name):
+                getattr(_lib, name).restype = C.c_size_t
     return _lib
 
 

@@ -159,6 +159,180 @@ extern "C" int ftcf_lm_head(const void* A, const void* W, float* logits, int m, 
         lm_head_dispatch((const f16*)A, (const f16*)W, logits, m, n, k, ldc, (hipStream_t)stream);
     });
 }
+// the forms the engine launches for batched decode, short prompt phases, the batcher and the verify pass, one call each
+// (thin wrappers: argument checks, then exactly the launcher the engine calls)
+extern "C" size_t ftcf_gemm_smallm_workspace_bytes(int m, int n, int k, int int8)
+{
+    return gemm_smallm_workspace_bytes(m, n, k, int8 != 0);
+}
+extern "C" size_t ftcf_gemm_smallm_ticket_bytes(void)
+{
+    return gemm_smallm_ticket_bytes();
+}
+extern "C" int ftcf_gemm_smallm_group(const ftcf_smallm_problem* problems, int np, int m, int int8, void* workspace,
+                                      size_t partial_bytes, size_t partial_offset, const int* d_step, unsigned* launch_counter,
+                                      void* stream)
+{
+    return guarded([&] {
+        require_device();
+        FTCF_CHECK_ARG(problems && np >= 1 && np <= 2 && m >= 1 && m <= 16 && workspace && launch_counter,
+                       "small-m GEMM group: 1..2 problems, 1..16 rows, a workspace and a launch counter");
+        FTCF_CHECK_ARG(partial_bytes % 8 == 0 && partial_offset % 8 == 0 && partial_offset <= partial_bytes,
+                       "small-m GEMM group: partial_bytes / partial_offset are multiples of 8, offset <= bytes");
+        SmallmDesc d[2];
+        for (int i = 0; i < np; i++) {
+            const ftcf_smallm_problem& q = problems[i];
+            FTCF_CHECK_ARG(q.A && q.W && q.C && (!int8 || q.scale), "small-m GEMM group: NULL tensor");
+            FTCF_CHECK_ARG(q.n >= 16 && q.k >= 64 && q.n % 16 == 0 && q.k % 64 == 0, "small-m GEMM group: n % 16 == 0, k % 64 == 0");
+            FTCF_CHECK_ARG((q.act == 0 || q.act == 1) && (q.act == 0 || q.bias), "small-m GEMM group: act 0 / 1 (1 needs a bias)");
+            d[i] = SmallmDesc{(const f16*)q.A, q.W, (const f16*)q.scale, (const f16*)q.bias, q.act, (f16*)q.C, q.n, q.k};
+        }
+        launch_gemm_smallm_group(d, np, (float*)workspace, partial_bytes, m, int8 != 0, (hipStream_t)stream, d_step, launch_counter,
+                                 partial_offset);
+    });
+}
+extern "C" int ftcf_residual_dual_layernorm(void* x, const void* ffn, const void* attn, const void* bias, int tp, int inplace_variant,
+                                            const void* g1, const void* b1, const void* g2, const void* b2, void* out1, void* out2,
+                                            int m, int n, float eps, int bias_mul, int sum_mul, void* stream)
+{
+    return guarded([&] {
+        require_device();
+        FTCF_CHECK_ARG(x && m >= 0 && n >= 8, "residual + dual LayerNorm: x [m, n]");
+        FTCF_CHECK_ARG(!ffn || (attn && bias && tp >= 1 && bias_mul >= 1 && sum_mul >= 1),
+                       "residual + dual LayerNorm: the residual needs ffn, attn, bias, tp >= 1 and multipliers >= 1");
+        FTCF_CHECK_ARG(!g1 || (b1 && g2 && b2 && out1 && out2), "residual + dual LayerNorm: both LayerNorms or none");
+        launch_residual_dual_ln((f16*)x, (const f16*)ffn, (const f16*)attn, (const f16*)bias, tp, inplace_variant, (const f16*)g1,
+                                (const f16*)b1, (const f16*)g2, (const f16*)b2, (f16*)out1, (f16*)out2, m, n, eps,
+                                (hipStream_t)stream, bias_mul, sum_mul);
+    });
+}
+extern "C" int ftcf_add_bias_residual(void* out, const void* a, const void* b, const void* bias, int m, int n, void* stream)
+{
+    return guarded([&] {
+        require_device();
+        FTCF_CHECK_ARG(out && a && b && m >= 0 && n >= 1, "bias + residual: out, a, b [m, n]");
+        launch_add_bias_residual((f16*)out, (const f16*)a, (const f16*)b, (const f16*)bias, m, n, (hipStream_t)stream);
+    });
+}
+// (dynamic LDS a launch may ask for without raising the kernel's limit)
+static constexpr size_t ABI_MAX_DYNAMIC_LDS = 64 * 1024;
+extern "C" int ftcf_lm_head_layernorm(const void* A, const void* W, const void* gamma, const void* beta, float eps, const int* d_stop,
+                                      float* logits, int m, int n, int k, int ldc, void* stream)
+{
+    return guarded([&] {
+        require_device();
+        FTCF_CHECK_ARG(A && W && logits && gamma && beta, "LM head with LayerNorm: NULL tensor");
+        FTCF_CHECK_ARG(m >= 1 && m <= 4 && n >= 1 && k >= 8 && ldc >= n, "LM head with LayerNorm: 1..4 rows, ldc >= n");
+        FTCF_CHECK_ARG((size_t)m * (k + 8) * 2 + 64 <= ABI_MAX_DYNAMIC_LDS, "LM head with LayerNorm: the rows do not fit the LDS");
+        launch_lm_head((const f16*)A, (const f16*)W, logits, m, n, k, ldc, (hipStream_t)stream, (const f16*)gamma, (const f16*)beta,
+                       eps, d_stop);
+    });
+}
+extern "C" int ftcf_ln_gemv(const ftcf_ln_gemv_args* a, int m, int int8, int wpg, void* stream)
+{
+    return guarded([&] {
+        require_device();
+        FTCF_CHECK_ARG(a && a->x && m >= 1 && m <= 4 && wpg >= 0 && wpg <= 4, "LN + GEMV: 1..4 rows, wpg 0..4");
+        FTCF_CHECK_ARG(a->K >= 64 && a->K % 64 == 0 && a->N0 >= 0 && a->N1 >= 0 && a->N0 % 16 == 0 && a->N1 % 16 == 0
+                           && a->N0 + a->N1 > 0,
+                       "LN + GEMV: K % 64 == 0, N0 % 16 == 0, N1 % 16 == 0");
+        FTCF_CHECK_ARG(a->N0 == 0 || (a->gamma0 && a->beta0 && a->W0 && a->out0 && (!int8 || a->scale0)), "LN + GEMV: segment 0 tensors");
+        FTCF_CHECK_ARG(a->N1 == 0 || (a->gamma1 && a->beta1 && a->W1 && a->out1 && a->bias1 && (!int8 || a->scale1)),
+                       "LN + GEMV: segment 1 tensors");
+        FTCF_CHECK_ARG((size_t)m * (a->K + 8) * 2 + (size_t)(2 * 4 + 4 * m * 16) * 4 + 64 <= ABI_MAX_DYNAMIC_LDS,
+                       "LN + GEMV: the rows do not fit the LDS");
+        LnGemvParams p{};
+        p.x = (const f16*)a->x;
+        p.gamma0 = (const f16*)a->gamma0;
+        p.beta0 = (const f16*)a->beta0;
+        p.gamma1 = (const f16*)a->gamma1;
+        p.beta1 = (const f16*)a->beta1;
+        p.W0 = a->W0;
+        p.W1 = a->W1;
+        p.scale0 = (const f16*)a->scale0;
+        p.scale1 = (const f16*)a->scale1;
+        p.bias1 = (const f16*)a->bias1;
+        p.out0 = (f16*)a->out0;
+        p.out1 = (f16*)a->out1;
+        p.K = a->K;
+        p.NT0 = a->N0 / 16;
+        p.NT1 = a->N1 / 16;
+        p.blocks0 = (p.NT0 + 3) / 4;
+        p.blocks1 = (p.NT1 + 3) / 4;
+        p.eps = a->eps;
+        if (wpg > 0) {
+            launch_ln_gemv_group(p, int8 != 0, m, wpg, (hipStream_t)stream);
+        }
+        else {
+            launch_ln_gemv(p, int8 != 0, m, (hipStream_t)stream);
+        }
+    });
+}
+extern "C" size_t ftcf_residual_gemv_workspace_bytes(int N, int m, int Q)
+{
+    return chunk_workspace_bytes(N, m, Q);
+}
+extern "C" int ftcf_residual_gemv(const ftcf_residual_gemv_args* a, int m, int int8, int Q, void* granules, size_t granule_bytes,
+                                  const int* d_step, int step, int salt, void* stream)
+{
+    return guarded([&] {
+        require_device();
+        const int tk = int8 ? TILE_K_I8 : TILE_K_F16;
+        FTCF_CHECK_ARG(a && m >= 1 && m <= 4 && Q >= 0 && Q <= 8, "residual GEMV: 1..4 rows, Q 0..8");
+        FTCF_CHECK_ARG(a->x_a && a->x_b && a->W_a && a->W_b && a->bias && a->x_in && a->out && (!int8 || (a->scale_a && a->scale_b)),
+                       "residual GEMV: NULL tensor");
+        FTCF_CHECK_ARG(a->N >= 16 && a->N % 16 == 0 && a->K_a >= tk && a->K_b >= tk && a->K_a % tk == 0 && a->K_b % tk == 0 && a->tp >= 1,
+                       "residual GEMV: N % 16 == 0, K_a / K_b whole tiles (64 int8, 32 fp16), tp >= 1");
+        if (Q == 0) {  // one workgroup per column group, its waves split the two segments
+            SplitKParams c{};
+            c.x_a = (const f16*)a->x_a;
+            c.x_b = (const f16*)a->x_b;
+            c.W_a = a->W_a;
+            c.W_b = a->W_b;
+            c.scale_a = (const f16*)a->scale_a;
+            c.scale_b = (const f16*)a->scale_b;
+            c.bias = (const f16*)a->bias;
+            c.x_in = (const f16*)a->x_in;
+            c.out = (f16*)a->out;
+            c.N = a->N;
+            c.KT_a = a->K_a / tk;
+            c.KT_b = a->K_b / tk;
+            c.tp = a->tp;
+            c.inplace_variant = a->inplace_variant;
+            plan_splitk(c, int8 != 0, m, 10);
+            FTCF_CHECK_ARG((size_t)c.nwaves * m * c.slice_halves * 2 + (size_t)c.nwaves * m * 16 * 4 <= ABI_MAX_DYNAMIC_LDS,
+                           "residual GEMV: the x slices do not fit the LDS");
+            launch_gemv_splitk(c, int8 != 0, m, EPI_RESIDUAL, (hipStream_t)stream);
+            return;
+        }
+        ChunkParams c{};
+        c.x_a = (const f16*)a->x_a;
+        c.x_b = (const f16*)a->x_b;
+        c.W_a = a->W_a;
+        c.W_b = a->W_b;
+        c.scale_a = (const f16*)a->scale_a;
+        c.scale_b = (const f16*)a->scale_b;
+        c.bias = (const f16*)a->bias;
+        c.x_in = (const f16*)a->x_in;
+        c.out = (f16*)a->out;
+        c.N = a->N;
+        c.KT_a = a->K_a / tk;
+        c.KT_b = a->K_b / tk;
+        c.Q = Q;
+        c.T = (c.KT_a + c.KT_b + Q - 1) / Q;
+        c.tp = a->tp;
+        c.inplace_variant = a->inplace_variant;
+        c.gran = (unsigned long long*)granules;
+        c.d_step = d_step;
+        c.step = step;
+        c.salt = salt;
+        FTCF_CHECK_ARG(Q == 1 || (granules && granule_bytes >= chunk_workspace_bytes(a->N, m, Q)), "residual GEMV: granule workspace too small");
+        FTCF_CHECK_ARG(salt >= 0 && salt < 1024, "residual GEMV: salt 0..1023");
+        FTCF_CHECK_ARG((size_t)2 * m * ((c.T / 2 + 2) * tk + 8) * 2 + (size_t)2 * 2 * m * 16 * 4 <= ABI_MAX_DYNAMIC_LDS,
+                       "residual GEMV: the x slices do not fit the LDS");
+        launch_gemv_chunked(c, int8 != 0, m, (hipStream_t)stream);
+    });
+}
 extern "C" int ftcf_lm_head_log_probs(const void* A, const void* W, const int* targets, float* log_probs, float* row_logsumexp, int m,
                                       int n, int k, void* stream)
 {

@@ -114,6 +114,17 @@ __device__ __forceinline__ void dequant4(uint32_t w, f16x2 scale2, f16x2& lo, f1
     hi                   = fb * scale2;
 }
 
+// a * g + b in half with the product rounded BEFORE the sum -- the reference's LayerNorm is hmul2 then hadd2
+// (layernorm_kernels.cu:157-286), two roundings.  Written as one expression, or as two statements of one basic block, hipcc
+// contracts it into v_pk_fma_f16 (one rounding), which moves some normalised elements by one half ulp away from
+// k_layernorm_f16 and from the oracle; every fused LayerNorm goes through here so that they all agree bit for bit.
+__device__ __forceinline__ f16 mul_then_add(const f16 a, const f16 g, const f16 b)
+{
+#pragma clang fp contract(off)
+    const f16 p = a * g;
+    return p + b;
+}
+
 __device__ __forceinline__ float dot2(f16x2 a, f16x2 b, float c)
 {
     return __builtin_amdgcn_fdot2(a, b, c, false);

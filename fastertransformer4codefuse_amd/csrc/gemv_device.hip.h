@@ -193,7 +193,7 @@ __device__ __forceinline__ void ln_gemv_block(const LnGemvParams& p, char* smem,
                     f16x8 o;
 #pragma unroll
                     for (int e = 0; e < 8; e++) {
-                        o[e] = (((xv[m][j][e] - mh) * rh) * gv[j][e]) + bv[j][e];
+                        o[e] = mul_then_add((xv[m][j][e] - mh) * rh, gv[j][e], bv[j][e]);
                     }
                     *reinterpret_cast<f16x8*>(xs + (size_t)m * (K + XPAD) + i) = o;
                 }
@@ -225,7 +225,7 @@ __device__ __forceinline__ void ln_gemv_block(const LnGemvParams& p, char* smem,
                 f16x8       o;
 #pragma unroll
                 for (int j = 0; j < 8; j++) {
-                    o[j] = (((v[j] - mh) * rh) * gg[j]) + bb[j];
+                    o[j] = mul_then_add((v[j] - mh) * rh, gg[j], bb[j]);
                 }
                 *reinterpret_cast<f16x8*>(xs + (size_t)m * (K + XPAD) + i) = o;
             }
@@ -340,7 +340,7 @@ __device__ __forceinline__ void ln_gemv_group_block(const LnGemvParams& p, char*
                 f16x8 o;
 #pragma unroll
                 for (int e = 0; e < 8; e++) {
-                    o[e] = (((xv[j][e] - mh) * rh) * gv[j][e]) + bv[j][e];
+                    o[e] = mul_then_add((xv[j][e] - mh) * rh, gv[j][e], bv[j][e]);
                 }
                 *reinterpret_cast<f16x8*>(xs + i) = o;
             }
@@ -373,7 +373,7 @@ __device__ __forceinline__ void ln_gemv_group_block(const LnGemvParams& p, char*
                 f16x8       o;
 #pragma unroll
                 for (int j = 0; j < 8; j++) {
-                    o[j] = (((v[j] - mh) * rh) * gg[j]) + bb[j];
+                    o[j] = mul_then_add((v[j] - mh) * rh, gg[j], bb[j]);
                 }
                 *reinterpret_cast<f16x8*>(xs + (size_t)m * (K + XPAD) + i) = o;
             }

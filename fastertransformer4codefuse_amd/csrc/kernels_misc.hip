@@ -147,12 +147,8 @@ __global__ __launch_bounds__(256) void k_residual_dual_ln(f16* __restrict__ x, c
 #pragma unroll
             for (int j = 0; j < 8; j++) {
                 const f16 c = (v[it][j] - mh) * rh;
-                f16       a = c * ga[j];
-                a           = a + ba[j];
-                f16 b       = c * gb[j];
-                b           = b + bb[j];
-                oa[j]       = a;
-                ob[j]       = b;
+                oa[j]       = mul_then_add(c, ga[j], ba[j]);
+                ob[j]       = mul_then_add(c, gb[j], bb[j]);
             }
             *reinterpret_cast<f16x8*>(out1 + row + i) = oa;
             *reinterpret_cast<f16x8*>(out2 + row + i) = ob;

@@ -40,7 +40,7 @@ __device__ __forceinline__ void lm_head_stage_x(const f16* __restrict__ x, const
                 f16x8       o;
 #pragma unroll
                 for (int j = 0; j < 8; j++) {
-                    o[j] = (((v[j] - mh) * rh) * gg[j]) + bb[j];
+                    o[j] = mul_then_add((v[j] - mh) * rh, gg[j], bb[j]);
                 }
                 *reinterpret_cast<f16x8*>(xs + (size_t)m * K + i) = o;
             }

@@ -1745,8 +1745,8 @@ __global__ __launch_bounds__(PS_NT) void k_decode_persistent(
 #pragma unroll
                             for (int e = 0; e < 8; e++) {
                                 const f16 nrm = (x8[e] - mh) * rh;
-                                o1[e]         = (nrm * r_ln[0][k][e]) + r_ln[1][k][e];
-                                o2[e]         = (nrm * r_ln[2][k][e]) + r_ln[3][k][e];
+                                o1[e]         = mul_then_add(nrm, r_ln[0][k][e], r_ln[1][k][e]);
+                                o2[e]         = mul_then_add(nrm, r_ln[2][k][e], r_ln[3][k][e]);
                             }
                             *reinterpret_cast<f16x8*>(s.xs + (size_t)m * (H + XPAD) + v * 8)       = o1;
                             *reinterpret_cast<f16x8*>(s.xs + (size_t)(M + m) * (H + XPAD) + v * 8) = o2;

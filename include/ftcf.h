@@ -79,6 +79,84 @@ int ftcf_fp16_gemm(const void* A, const void* W_tiled, const void* bias, ftcf_ac
                    void* stream);
 /* LM head (models/gptneox/GptNeoX.cc:866-912): logits_f32[m, n] = A[m,k] (fp16) x W[n,k]^T (fp16, row major [V,H]) */
 int ftcf_lm_head(const void* A, const void* W_nk, float* logits, int m, int n, int k, int ldc, void* stream);
+/* The same LM head with the final LayerNorm (GptNeoX.cc:854-863) fused in front, as the engine's token loop runs it for <= 4
+ * rows: logits_f32[m, n] = LN(A; gamma, beta, eps)[m, k] x W[n, k]^T, the LayerNorm with ftcf_layernorm's fp16 numerics.
+ * 1 <= m <= 4, k % 8 == 0, ldc >= n (a tensor-parallel rank writes its vocabulary slice of a wider row).  d_stop (device int, or
+ * NULL): the "every row has finished" flag -- when it is set the launch writes nothing. */
+int ftcf_lm_head_layernorm(const void* A, const void* W_nk, const void* gamma, const void* beta, float eps, const int* d_stop,
+                           float* logits, int m, int n, int k, int ldc, void* stream);
+/* Batched-decode GEMM in the form the engine launches it (general path at 5..16 rows, short prompt phases, the continuous
+ * batcher, the speculative verify pass): one launch for ONE or TWO independent GEMMs with the same m,
+ * C[m, n] = epilogue(A[m, k] x W), W tiled int8 (with scale [n]) or tiled fp16, act FTCF_ACT_GELU = bias + gelu.  K is cut in
+ * slices of 20 tiles (64 k each int8, 32 fp16); the partial sums of all slices but the last travel through `workspace` as
+ * {tag, value} granules and the owner of the last slice adds them in slice order.
+ *   workspace: [partial_bytes of granules][ftcf_gemm_smallm_ticket_bytes()], caller owned, all zero before the first launch;
+ *     the int at byte partial_bytes is a sticky error word (0 = fine).  The problems of one launch take
+ *     ftcf_gemm_smallm_workspace_bytes(m, n, k, int8) bytes each, back to back from partial_offset; launches that may run
+ *     concurrently (two streams) use disjoint [partial_offset, ...) regions of one workspace.
+ *   d_step: device int that is part of the launch's tag (the engine's decode step; read at run time), or NULL.
+ *   launch_counter: host counter of the workspace, part of the tag; every launch increments it.
+ * 1 <= m <= 16, n % 16 == 0, k % 64 == 0. */
+typedef struct {
+    const void* A;     /* [m, k] fp16 */
+    const void* W;     /* tiled int8 / fp16 [k, n] */
+    const void* scale; /* [n] fp16 (int8 only) */
+    const void* bias;  /* [n] fp16 or NULL */
+    int         act;   /* ftcf_act */
+    void*       C;     /* [m, n] fp16 */
+    int         n, k;
+} ftcf_smallm_problem;
+int    ftcf_gemm_smallm_group(const ftcf_smallm_problem* problems, int np, int m, int int8, void* workspace, size_t partial_bytes,
+                              size_t partial_offset, const int* d_step, unsigned* launch_counter, void* stream);
+size_t ftcf_gemm_smallm_workspace_bytes(int m, int n, int k, int int8);
+size_t ftcf_gemm_smallm_ticket_bytes(void);
+/* One pass over x [m, n] (in place) for a parallel-residual layer of the batched paths: with ffn != NULL first the previous
+ * layer's invokeAddBiasAttentionFfnResidual, x = residual(ffn * sum_mul, attn * sum_mul, x / tp, bias * bias_mul) (the products
+ * in fp32, rounded to half once; inplace_variant as ftcf_add_bias_attn_ffn_residual), then out1 = LN(x; g1, b1) and
+ * out2 = LN(x; g2, b2) with the element sets and summation order of ftcf_layernorm (bit-identical to it).  g1 == NULL: the
+ * residual only, out1 / out2 untouched.  n % 8 == 0 and n <= 8192, anything else is FTCF_ERR_INVALID_ARG. */
+int ftcf_residual_dual_layernorm(void* x, const void* ffn, const void* attn, const void* bias, int tp, int inplace_variant,
+                                 const void* g1, const void* b1, const void* g2, const void* b2, void* out1, void* out2, int m, int n,
+                                 float eps, int bias_mul, int sum_mul, void* stream);
+/* Sequential-residual layers (use_gptj_residual == 0; invokeAddBiasResidual, kernels/add_residual_kernels.cu:22-60):
+ * out = half((bias + a) + b) with the sums in fp32; bias [n] or NULL; out may alias a or b. */
+int ftcf_add_bias_residual(void* out, const void* a, const void* b, const void* bias, int m, int n, void* stream);
+/* The per-stage decode step's LayerNorm -> GEMV launch for 1..4 rows: out0 [m, N0] = half(LN(x; gamma0, beta0) x W0) (QKV: no
+ * bias) and / or out1 [m, N1] = gelu(LN(x; gamma1, beta1) x W1 + bias1) (FFN1), W tiled int8 (scale0 / scale1) or fp16.  A
+ * segment with N = 0 is absent.  wpg = 0: four column groups per workgroup, one wave each; wpg 1..4: one column group per
+ * workgroup, wpg waves splitting K.  K % 64 == 0, N0 % 16 == 0, N1 % 16 == 0; x [m, K] must fit the LDS (m * K <= ~32000). */
+typedef struct {
+    const void* x;
+    const void *gamma0, *beta0, *gamma1, *beta1;
+    const void *W0, *W1;
+    const void *scale0, *scale1;
+    const void* bias1;
+    void *      out0, *out1;
+    int         K, N0, N1;
+    float       eps;
+} ftcf_ln_gemv_args;
+int ftcf_ln_gemv(const ftcf_ln_gemv_args* args, int m, int int8, int wpg, void* stream);
+/* The per-stage decode step's closing launch for 1..4 rows: attn = half(x_a x W_a) (out-projection), ffn = half(x_b x W_b)
+ * (FFN2), out = residual(ffn, attn, x_in / tp, bias) as ftcf_add_bias_attn_ffn_residual; out may be x_in.  Q = 0: one workgroup
+ * per 16-column group, up to 10 waves over the two K ranges.  Q in 1..8: the concatenated K range [x_a ; x_b] of a column group
+ * is cut into Q chunks of ceil(tiles / Q) tiles, one workgroup each; the partial sums travel as {tag, value} granules through
+ * `granules` (ftcf_residual_gemv_workspace_bytes(N, m, Q) bytes, caller owned, zero before the first launch; unused for Q <= 1).
+ * The tag is (step, salt): step = *d_step when d_step != NULL, else `step`; salt in 0..1023; consecutive launches on one
+ * workspace need different tags.  K_a / K_b are whole tiles (64 int8, 32 fp16), N % 16 == 0; a shape whose x slices exceed 64 KiB
+ * of LDS is FTCF_ERR_INVALID_ARG. */
+typedef struct {
+    const void *x_a, *x_b;         /* [m, K_a], [m, K_b] fp16 */
+    const void *W_a, *W_b;         /* tiled [K_a, N], [K_b, N] */
+    const void *scale_a, *scale_b; /* [N] fp16 (int8 only) */
+    const void* bias;              /* [N] */
+    const void* x_in;              /* [m, N] */
+    void*       out;               /* [m, N] */
+    int         N, K_a, K_b;
+    int         tp, inplace_variant;
+} ftcf_residual_gemv_args;
+int    ftcf_residual_gemv(const ftcf_residual_gemv_args* args, int m, int int8, int Q, void* granules, size_t granule_bytes,
+                          const int* d_step, int step, int salt, void* stream);
+size_t ftcf_residual_gemv_workspace_bytes(int N, int m, int Q);
 /* Fused LM head -> log-probability of a target token (the prompt-scoring kernel behind context_log_probs; the reference writes
  * the logits and runs kernels/logprob_kernels.cu:36-100 over them).  For each row r, l_j = sum_k A[r,k] W[j,k] (fp16 products,
  * fp32 accumulation, as ftcf_lm_head), log_probs[r] = l[targets[r]] - logsumexp_j l_j; targets[r] < 0 (or >= n) gives 0.

@@ -38,6 +38,30 @@ def test_ops_fail_loudly_without_a_gpu():
         GptNeoXOp(None, 0, 4, 64, 1024, 2, 512, 16, 0, 2, 1, 1, 0, 1024, True, [torch.zeros(1)], [], [])
 
 
+@pytest.mark.skipif(torch.cuda.is_available(), reason="CPU-only behaviour")
+def test_engine_form_entry_points_fail_loudly_without_a_gpu():
+    """the kernel-level entry points of the forms the engine launches: no device is an error, never a silent no-op; the size
+    queries are host arithmetic and answer anyway"""
+    L = capi.lib()
+    prob, ln, res = capi.SmallmProblem(), capi.LnGemvArgs(), capi.ResidualGemvArgs()
+    seq = C.c_uint(0)
+    calls = [
+        lambda: L.ftcf_gemm_smallm_group(C.byref(prob), 1, 5, 1, None, C.c_size_t(0), C.c_size_t(0), None, C.byref(seq), None),
+        lambda: L.ftcf_residual_dual_layernorm(None, None, None, None, 1, 0, None, None, None, None, None, None, 1, 8, C.c_float(1e-5), 1, 1, None),
+        lambda: L.ftcf_add_bias_residual(None, None, None, None, 1, 8, None),
+        lambda: L.ftcf_lm_head_layernorm(None, None, None, None, C.c_float(1e-5), None, None, 1, 16, 64, 16, None),
+        lambda: L.ftcf_ln_gemv(C.byref(ln), 1, 1, 0, None),
+        lambda: L.ftcf_residual_gemv(C.byref(res), 1, 1, 2, None, C.c_size_t(0), None, 0, 0, None),
+    ]
+    for call in calls:
+        assert call() == -5 and b"no HIP device" in L.ftcf_last_error()
+    assert seq.value == 0
+    assert L.ftcf_gemm_smallm_workspace_bytes(16, 5120, 20480, 1) == 16 * 16 * 5120 * 8  # 16 slices of {tag, value} granules
+    assert L.ftcf_gemm_smallm_workspace_bytes(5, 80, 1344, 1) == 8 * 5 * 80 * 8         # (never fewer than 8)
+    assert L.ftcf_gemm_smallm_ticket_bytes() >= 4
+    assert L.ftcf_residual_gemv_workspace_bytes(5120, 4, 8) == (5120 // 16) * 8 * 2 * 4 * 16 * 8
+
+
 @pytest.mark.parametrize("dtype", [torch.float16, torch.float32])
 def test_host_quantizer_matches_oracle_bit_exact(dtype):
     torch.manual_seed(0)
