@@ -1066,8 +1066,7 @@ struct ftcf_batcher {
     bool decode_overlap_now(int B, bool dual)
     {
         ftcf_gptneox* g  = e;
-        ov_auto = g->decode_overlap_mode == 2 && g->cfg.tensor_para_size > 1 && g->cfg.comm && g->cfg.comm->comm && !g->cfg.comm->local
-                  && !g->cfg.comm->hx && g->cfg.comm->world > 1;
+        ov_auto = g->decode_overlap_mode == 2 && g->rccl_ranks();
         const int env = g->decode_overlap_mode == 1 ? 1 : 0;
         ov_last = false;
         if (g->cfg.tensor_para_size == 1 || !dual || !smallm_ws || smallm_partial < 2 * smallm_region || !g->side || B < 4 || B > 32
@@ -1156,163 +1155,56 @@ struct ftcf_batcher {
             rp.max_pages = max_pages;
             launch_decode_rows(rp, int8, st);
         }
-        // tensor parallel, 4..32 slots: the layer's all-reduce on the side stream under the other micro-batch's launches (the
-        // engine's decoder_overlapped, engine.hip.h, on the paged cache; FTCF_DECODE_OVERLAP = 0 / 1, auto = timed on this node)
+        // tensor parallel, 4..32 slots: the layer's all-reduce on the side stream under the other micro-batch's launches
+        // (FTCF_DECODE_OVERLAP = 0 / 1, auto = timed on this node)
         const bool overlap = !use_rows && decode_overlap_now(B, dual);
         const auto t_dec0  = std::chrono::steady_clock::now();
-        if (overlap) {
-            e->decode_overlap_streams();
-            const int         r0[2] = {0, (B + 1) / 2}, r1[2] = {(B + 1) / 2, B};
-            const hipStream_t cs[2] = {st, e->side2};
-            FTCF_HIP_CHECK(hipEventRecord(e->dv_fork[0], st));
-            FTCF_HIP_CHECK(hipStreamWaitEvent(e->side2, e->dv_fork[0], 0));
-            for (int l = 0; l < L; l++) {
-                const LayerWeights& w = e->layers[l];
-                for (int c = 0; c < 2; c++) {
-                    const int         M  = r1[c] - r0[c];
-                    const size_t      o  = (size_t)r0[c], wo = (size_t)c * smallm_region;
-                    const hipStream_t s2 = cs[c];
-                    f16*              xr = x + o * H;
-                    const bool pair = e->tp_pair_ar;
-                    f16* const attc = att + 2 * o * H;  // (a micro-batch's attn | ffn rows adjacent)
-                    f16* const ffnc = attc + (size_t)M * H;
-                    if (l > 0 && !pair) {
-                        FTCF_HIP_CHECK(hipStreamWaitEvent(s2, e->dv_red[c], 0));
-                    }
-                    if (l == 0 || !pair) {
-                        launch_residual_dual_ln(xr, nullptr, nullptr, nullptr, 1, 0, w.ln1_g, w.ln1_b, w.ln2_g, w.ln2_b, nrm + o * H,
-                                                nrm2 + o * H, M, H, 1e-5f, s2);
-                    }
-                    MmhaPagedParams mp{};
-                    mp.qkv = qkv + o * 3 * hl;
-                    mp.qkv_bias = w.qkv.bias;
-                    mp.kpool = kpool + (size_t)l * pool_layer_elems;
-                    mp.vpool = vpool + (size_t)l * pool_layer_elems;
-                    mp.page_table = d_pt + o * max_pages;
-                    mp.len = d_len + o;
-                    mp.finished = d_fin + o;
-                    mp.B = M;
-                    mp.nh = e->nhl;
-                    mp.dh = e->dh;
-                    mp.rot = e->cfg.rotary_embedding_dim;
-                    mp.P = P;
-                    mp.max_pages = max_pages;
-                    mp.ctx = ctx + o * hl;
-                    const SmallmDesc p1[2] = {{nrm + o * H, w.qkv.kernel, w.qkv.scale, nullptr, 0, qkv + o * 3 * hl, 3 * hl, H},
-                                              {nrm2 + o * H, w.ffn1.kernel, w.ffn1.scale, w.ffn1.bias, 1, mid + o * il, il, H}};
-                    launch_gemm_smallm_group(p1, 2, smallm_ws, smallm_partial, M, int8, s2, &d_gstate->step, &smallm_seq, wo);
-                    launch_mmha_paged(mp, max_len, s2);
-                    const SmallmDesc p3[2] = {{ctx + o * hl, w.attn_out.kernel, w.attn_out.scale, nullptr, 0, attc, H, hl},
-                                              {mid + o * il, w.ffn2.kernel, w.ffn2.scale, nullptr, 0, ffnc, H, il}};
-                    launch_gemm_smallm_group(p3, 2, smallm_ws, smallm_partial, M, int8, s2, &d_gstate->step, &smallm_seq, wo);
-                    if (!pair) {
-                        launch_add_bias_attn_ffn_residual(xr, ffnc, attc, xr, w.ffn2.bias, M, H, tp, (l > 0 && l < L - 1) ? 1 : 0, true, s2);
-                    }
-                    FTCF_HIP_CHECK(hipEventRecord(e->dv_done[c], s2));
-                    FTCF_HIP_CHECK(hipStreamWaitEvent(e->side, e->dv_done[c], 0));
-                    e->allreduce(pair ? attc : xr, (size_t)(pair ? 2 : 1) * M * H, e->side);
-                    FTCF_HIP_CHECK(hipEventRecord(e->dv_red[c], e->side));
-                    if (pair) {
-                        const LayerWeights* nx = l + 1 < L ? &e->layers[l + 1] : nullptr;
-                        FTCF_HIP_CHECK(hipStreamWaitEvent(s2, e->dv_red[c], 0));
-                        launch_residual_dual_ln(xr, ffnc, attc, w.ffn2.bias, 1, 1, nx ? nx->ln1_g : nullptr, nx ? nx->ln1_b : nullptr,
-                                                nx ? nx->ln2_g : nullptr, nx ? nx->ln2_b : nullptr, nrm + o * H, nrm2 + o * H, M, H, 1e-5f,
-                                                s2, tp);
-                    }
-                }
+        if (!use_rows) {
+            // the batched parallel-residual layers (layers.hip.h) over the paged K/V pool, with this batcher's buffers and burst
+            // workspace.  (Every slot's hidden state is recomputed from its token each step: the residual never aliases across steps.)
+            if (overlap) {
+                e->decode_overlap_streams();
             }
-            FTCF_HIP_CHECK(hipEventRecord(e->dv_fork[1], e->side2));
-            FTCF_HIP_CHECK(hipStreamWaitEvent(st, e->dv_fork[1], 0));
-            for (int c = 0; c < 2; c++) {
-                FTCF_HIP_CHECK(hipStreamWaitEvent(st, e->dv_red[c], 0));
-            }
-        }
-        for (int l = 0; l < (use_rows || overlap ? 0 : L); l++) {
-            const LayerWeights& w = e->layers[l];
-            if (!dual) {
-                launch_layernorm(x, w.ln1_g, w.ln1_b, nrm, B, H, 1e-5f, true, st);
-                launch_layernorm(x, w.ln2_g, w.ln2_b, nrm2, B, H, 1e-5f, true, st);
-            }
-            else if (l == 0 || (!tp1 && !e->tp_pair_ar)) {
-                launch_residual_dual_ln(x, nullptr, nullptr, nullptr, 1, 0, w.ln1_g, w.ln1_b, w.ln2_g, w.ln2_b, nrm, nrm2, B, H,
-                                        1e-5f, st);
-            }
-            MmhaPagedParams mp{};
-            mp.qkv = qkv;
-            mp.qkv_bias = w.qkv.bias;
-            mp.kpool = kpool + (size_t)l * pool_layer_elems;
-            mp.vpool = vpool + (size_t)l * pool_layer_elems;
-            mp.page_table = d_pt;
-            mp.len = d_len;
-            mp.finished = d_fin;
-            mp.B = B;
-            mp.nh = e->nhl;
-            mp.dh = e->dh;
-            mp.rot = e->cfg.rotary_embedding_dim;
-            mp.P = P;
-            mp.max_pages = max_pages;
-            mp.ctx = ctx;
-            if (smallm_ws && e->decode_branches && e->side) {
-                // the attention branch and the FFN branch on two streams, as the engine's batched decode
-                const int    bc = std::min(B, 16);
-                const size_t o_qkv = 0, o_f1 = o_qkv + gemm_smallm_workspace_bytes(bc, 3 * hl, H, int8),
-                             o_out = o_f1 + gemm_smallm_workspace_bytes(bc, il, H, int8),
-                             o_f2  = o_out + gemm_smallm_workspace_bytes(bc, H, hl, int8);
-                auto one = [&](const SmallmDesc& d0, size_t off, hipStream_t s2) {
-                    for (int r0 = 0; r0 < B; r0 += 16) {
-                        SmallmDesc d = d0;
-                        d.A          = d0.A + (size_t)r0 * d0.k;
-                        d.C          = d0.C + (size_t)r0 * d0.n;
-                        launch_gemm_smallm_group(&d, 1, smallm_ws, smallm_partial, std::min(16, B - r0), int8, s2, &d_gstate->step,
-                                                 &smallm_seq, off);
-                    }
-                };
-                const size_t offs[4] = {o_qkv, o_f1, o_out, o_f2};
-                GemmFn burst = [&](const f16* A, const DenseWeight& dw, const f16* bias, int act, f16* C, int, int n, int k,
-                                   hipStream_t s2, int slot) { one(SmallmDesc{A, dw.kernel, dw.scale, bias, act, C, n, k}, offs[slot], s2); };
-                FTCF_HIP_CHECK(hipEventRecord(e->ev_fork, st));
-                FTCF_HIP_CHECK(hipStreamWaitEvent(e->side, e->ev_fork, 0));
-                DecoderSelfAttentionLayer{burst, H, hl}.forward_paged(nrm, qkv, ctx, att, w, mp, max_len, B, st);
-                FfnLayer{burst, H, il}.forward(nrm2, mid, ffn, w, B, e->side);
-                FTCF_HIP_CHECK(hipEventRecord(e->ev_join, e->side));
-                FTCF_HIP_CHECK(hipStreamWaitEvent(st, e->ev_join, 0));
-            }
-            else if (smallm_ws && B <= 16) {
-                const SmallmDesc p1[2] = {{nrm, w.qkv.kernel, w.qkv.scale, nullptr, 0, qkv, 3 * hl, H},
-                                          {nrm2, w.ffn1.kernel, w.ffn1.scale, w.ffn1.bias, 1, mid, il, H}};
-                launch_gemm_smallm_group(p1, 2, smallm_ws, smallm_partial, B, int8, st, &d_gstate->step, &smallm_seq);
-                launch_mmha_paged(mp, max_len, st);
-                const SmallmDesc p3[2] = {{ctx, w.attn_out.kernel, w.attn_out.scale, nullptr, 0, att, H, hl},
-                                          {mid, w.ffn2.kernel, w.ffn2.scale, nullptr, 0, ffn, H, il}};
-                launch_gemm_smallm_group(p3, 2, smallm_ws, smallm_partial, B, int8, st, &d_gstate->step, &smallm_seq);
+            ParallelResidualDecoder walk = e->layer_walk();
+            walk.fake_mul = 1;  // (fake peers: the all-reduce below scales the sum itself)
+            walk.x = x, walk.nrm = nrm, walk.nrm2 = nrm2, walk.qkv = qkv, walk.ctx = ctx, walk.att = att, walk.ffn = ffn, walk.mid = mid;
+            walk.ws = smallm_ws, walk.partial = smallm_partial, walk.region = smallm_region;
+            walk.d_step = &d_gstate->step;
+            walk.seq = &smallm_seq;
+            walk.plain = [&](const f16* A, const DenseWeight& dw, const f16* bias, int act, f16* C, int m, int n, int k, hipStream_t s2, int) {
+                gemm_dispatch(A, dw.kernel, dw.scale, bias, act, C, m, n, k, int8, s2, nullptr, 0, e->num_cu, nullptr, nullptr,
+                              s2 == st ? tiled_ws : nullptr);
+            };
+            auto attention = [&](int l, const LayerWeights& w, int r0, int M, hipStream_t s2) {
+                const size_t    o = (size_t)r0;
+                MmhaPagedParams mp{};
+                mp.qkv = qkv + o * 3 * hl;
+                mp.qkv_bias = w.qkv.bias;
+                mp.kpool = kpool + (size_t)l * pool_layer_elems;
+                mp.vpool = vpool + (size_t)l * pool_layer_elems;
+                mp.page_table = d_pt + o * max_pages;
+                mp.len = d_len + o;
+                mp.finished = d_fin + o;
+                mp.B = M;
+                mp.nh = e->nhl;
+                mp.dh = e->dh;
+                mp.rot = e->cfg.rotary_embedding_dim;
+                mp.P = P;
+                mp.max_pages = max_pages;
+                mp.ctx = ctx + o * hl;
+                launch_mmha_paged(mp, max_len, s2);
+            };
+            auto reduce = [&](f16* buf, size_t count, hipStream_t s2, bool) { e->allreduce(buf, count, s2); };
+            if (overlap) {
+                walk.forward_overlapped(B, attention, reduce);
             }
             else {
-                GemmFn plain = [&](const f16* A, const DenseWeight& dw, const f16* bias, int act, f16* C, int m, int n, int k,
-                                   hipStream_t s2, int) {
-                    gemm_dispatch(A, dw.kernel, dw.scale, bias, act, C, m, n, k, int8, s2, nullptr, 0, e->num_cu, nullptr, nullptr,
-                                  s2 == st ? tiled_ws : nullptr);
-                };
-                DecoderSelfAttentionLayer{plain, H, hl}.forward_paged(nrm, qkv, ctx, att, w, mp, max_len, B, st);
-                FfnLayer{plain, H, il}.forward(nrm2, mid, ffn, w, B, st);
-            }
-            // (every slot's hidden state is recomputed from its token each step: the residual never aliases across steps,
-            // so the fp32-sum variant of the context decoder applies to all layers)
-            if (dual && !tp1 && e->tp_pair_ar) {
-                // attn | ffn as one all-reduce message, the residual inside the next layer's LayerNorm pass (engine.hip.h decoder)
-                e->allreduce(att, (size_t)2 * B * H, st);
-                const LayerWeights* nx = l + 1 < L ? &e->layers[l + 1] : nullptr;
-                launch_residual_dual_ln(x, ffn, att, w.ffn2.bias, 1, 1, nx ? nx->ln1_g : nullptr, nx ? nx->ln1_b : nullptr,
-                                        nx ? nx->ln2_g : nullptr, nx ? nx->ln2_b : nullptr, nrm, nrm2, B, H, 1e-5f, st, tp);
-            }
-            else if (dual && tp1) {
-                const LayerWeights* nx = l + 1 < L ? &e->layers[l + 1] : nullptr;
-                launch_residual_dual_ln(x, ffn, att, w.ffn2.bias, 1, (l > 0 && l < L - 1) ? 1 : 0, nx ? nx->ln1_g : nullptr,
-                                        nx ? nx->ln1_b : nullptr, nx ? nx->ln2_g : nullptr, nx ? nx->ln2_b : nullptr, nrm, nrm2, B, H,
-                                        1e-5f, st);
-            }
-            else {
-                launch_add_bias_attn_ffn_residual(x, ffn, att, x, w.ffn2.bias, B, H, tp, (l > 0 && l < L - 1) ? 1 : 0, true, st);
-                e->allreduce(x, (size_t)B * H, st);
+                // the attention branch and the FFN branch on two streams, as the engine's batched decode, else up to
+                // 16 slots the independent GEMMs paired per launch, else gemm_dispatch
+                const DecodeGemms gemms = (smallm_ws && e->decode_branches && e->side) ? DecodeGemms::branches
+                                          : (smallm_ws && B <= 16)                     ? DecodeGemms::grouped
+                                                                                       : DecodeGemms::plain;
+                walk.forward(B, gemms, attention, reduce);
             }
         }
         {

@@ -1088,8 +1088,8 @@ int ftcf_gptneox::step(int max_steps)
 }
 
 // One verify pass: the token of position step - 1 and `drafts` drafted tokens as R = drafts + 1 rows of the
-// one sequence through the general path's layer loop for <= 16 rows (decoder(): the burst GEMM pairs [QKV, FFN1] -> attention ->
-// [out-proj, FFN2], residual + both LayerNorms in one pass) with the verify attention where launch_mmha stands, then the final
+// one sequence through the batched decode layers in their grouped form (ParallelResidualDecoder, layers.hip.h: the burst GEMM pairs
+// [QKV, FFN1] -> attention -> [out-proj, FFN2], residual + both LayerNorms in one pass) with the verify attention, then the final
 // LayerNorm, the LM head on R rows and the acceptance kernel, which closes the step as the greedy kernels do.  The K / V rows of
 // rejected drafts stay in the cache beyond the sequence's length; the next step overwrites them.
 void ftcf_gptneox::verify_pass(int st, int drafts)
@@ -1097,53 +1097,32 @@ void ftcf_gptneox::verify_pass(int st, int drafts)
     Range r("ftcf.verify_pass");
     const int    R = drafts + 1, len = st - 1, s_max = ses.s_max, rot = cfg.rotary_embedding_dim;
     const size_t cache_l = (size_t)ses.B * nhl * s_max * dh;
-    const double wbytes  = int8 ? 1.0 : 2.0;
-    const bool   dual    = residual_dual_ln_supported(H);
     launch_verify_embed(vx, wte, step_ids, spec_draft, st, R, H, stream);
     launch_verify_rotary(vrot, len, R, rot, stream);
-    for (int l = 0; l < L; l++) {
-        const LayerWeights& w       = layers[l];
-        const int           inplace = (l > 0 && l < L - 1) ? 1 : 0;
-        if (!dual) {
-            launch_layernorm(vx, w.ln1_g, w.ln1_b, vnrm, R, H, 1e-5f, true, stream);
-            launch_layernorm(vx, w.ln2_g, w.ln2_b, vnrm2, R, H, 1e-5f, true, stream);
-        }
-        else if (l == 0) {
-            launch_residual_dual_ln(vx, nullptr, nullptr, nullptr, 1, 0, w.ln1_g, w.ln1_b, w.ln2_g, w.ln2_b, vnrm, vnrm2, R, H, 1e-5f,
-                                    stream);
-        }
-        const SmallmDesc p1[2] = {{vnrm, w.qkv.kernel, w.qkv.scale, nullptr, 0, vqkv, 3 * hl, H},
-                                  {vnrm2, w.ffn1.kernel, w.ffn1.scale, w.ffn1.bias, 1, vmid, il, H}};
-        timed(KIND_SMALLM, wbytes * H * (3.0 * hl + il),
-              [&] { launch_gemm_smallm_group(p1, 2, spec_gws, spec_partial, R, int8, stream, &state->step, &smallm_seq); });
-        VerifyAttnParams ap{};
-        ap.qkv       = vqkv;
-        ap.qkv_bias  = w.qkv.bias;
-        ap.k_cache   = k_cache + l * cache_l;
-        ap.v_cache   = v_cache + l * cache_l;
-        ap.rot_table = rot > 0 ? vrot : nullptr;
-        ap.ctx       = vctx;
-        ap.ws        = spec_aws;
-        ap.len       = len;
-        ap.R         = R;
-        ap.nh        = nhl;
-        ap.dh        = dh;
-        ap.rot       = rot;
-        ap.s_max     = s_max;
-        launch_verify_attention(ap, stream);
-        const SmallmDesc p3[2] = {{vctx, w.attn_out.kernel, w.attn_out.scale, nullptr, 0, vatt, H, hl},
-                                  {vmid, w.ffn2.kernel, w.ffn2.scale, nullptr, 0, vffn, H, il}};
-        timed(KIND_SMALLM, wbytes * H * ((double)hl + il),
-              [&] { launch_gemm_smallm_group(p3, 2, spec_gws, spec_partial, R, int8, stream, &state->step, &smallm_seq); });
-        if (dual) {
-            const LayerWeights* nx = l + 1 < L ? &layers[l + 1] : nullptr;
-            launch_residual_dual_ln(vx, vffn, vatt, w.ffn2.bias, 1, inplace, nx ? nx->ln1_g : nullptr, nx ? nx->ln1_b : nullptr,
-                                    nx ? nx->ln2_g : nullptr, nx ? nx->ln2_b : nullptr, vnrm, vnrm2, R, H, 1e-5f, stream);
-        }
-        else {
-            launch_add_bias_attn_ffn_residual(vx, vffn, vatt, vx, w.ffn2.bias, R, H, 1, inplace, true, stream);
-        }
-    }
+    ParallelResidualDecoder walk = layer_walk();
+    walk.tp = 1;  // (a request speculates at TP = 1 only: no layer of the pass all-reduces)
+    walk.x = vx, walk.nrm = vnrm, walk.nrm2 = vnrm2, walk.qkv = vqkv, walk.ctx = vctx, walk.att = vatt, walk.ffn = vffn, walk.mid = vmid;
+    walk.ws = spec_gws, walk.partial = spec_partial;
+    walk.forward(
+        R, DecodeGemms::grouped,
+        [&](int l, const LayerWeights& w, int, int, hipStream_t s) {
+            VerifyAttnParams ap{};
+            ap.qkv       = vqkv;
+            ap.qkv_bias  = w.qkv.bias;
+            ap.k_cache   = k_cache + l * cache_l;
+            ap.v_cache   = v_cache + l * cache_l;
+            ap.rot_table = rot > 0 ? vrot : nullptr;
+            ap.ctx       = vctx;
+            ap.ws        = spec_aws;
+            ap.len       = len;
+            ap.R         = R;
+            ap.nh        = nhl;
+            ap.dh        = dh;
+            ap.rot       = rot;
+            ap.s_max     = s_max;
+            launch_verify_attention(ap, s);
+        },
+        [](f16*, size_t, hipStream_t, bool) {}, [&](double bytes, auto&& launch, hipStream_t s) { timed(KIND_SMALLM, bytes, launch, s); });
     launch_layernorm(vx, final_g, final_b, vnrm, R, H, 1e-5f, true, stream);
     timed(KIND_LM_HEAD, 2.0 * V * H, [&] { lm_head_dispatch(vnrm, lm_head, vlogits, R, V, H, V, stream); });
     VerifyAcceptParams vp{};

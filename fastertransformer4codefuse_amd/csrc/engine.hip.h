@@ -11,7 +11,7 @@ void lm_head_dispatch(const f16* A, const f16* W, float* logits, int m, int n, i
 
 namespace {
 // (DenseWeight / LayerWeights and the host-side layer units DecoderSelfAttentionLayer, GptContextAttentionLayer, FfnLayer,
-// DynamicDecodeLayer: layers.hip.h)
+// ParallelResidualDecoder, DynamicDecodeLayer: layers.hip.h)
 
 struct DeviceBuffer {
     void*  ptr = nullptr;
@@ -417,7 +417,6 @@ struct ftcf_gptneox {
         }
     }
 
-    // ---- FfnLayer / attention projections over M rows (general path) ----
     // ---- host-side layer units (layers.hip.h), bound to this engine's GEMM dispatch -----------------------------------
     DecoderSelfAttentionLayer self_attention_layer;
     GptContextAttentionLayer  context_attention_layer;
@@ -467,6 +466,11 @@ struct ftcf_gptneox {
         return cfg.tensor_para_size > 1 && cfg.comm && cfg.comm->world == 1 && !cfg.comm->local && !cfg.comm->hx;
     }
     int fake_peers_mul() const { return fake_peers() ? cfg.tensor_para_size : 1; }
+    // ranks joined by RCCL (what an all-reduce between them hides can only be measured on the node: the "auto" overlap trials)
+    bool rccl_ranks() const
+    {
+        return cfg.tensor_para_size > 1 && cfg.comm && cfg.comm->comm && !cfg.comm->local && !cfg.comm->hx && cfg.comm->world > 1;
+    }
 
     // (consumer_scales: the kernel that reads the result multiplies it by fake_peers_mul() itself -- no launch here)
     void allreduce(f16* buf, size_t count, hipStream_t on = nullptr, bool consumer_scales = false)
@@ -989,14 +993,39 @@ struct ftcf_gptneox {
             }
             return;
         }
-        if (!staged && decoder_overlapped(B, s_max)) {
+        if (!staged && cfg.use_gptj_residual) {
+            // general path: the batched parallel-residual layers (layers.hip.h) with this engine's attention, all-reduce and timing
+            auto attention = [&](int l, const LayerWeights& w, int r0, int M, hipStream_t st) {
+                // (beam search reads K/V through the cache indirection)
+                MmhaParams mp = mmha_params(l, w, B, s_max, r0, M, l);
+                if (ses.K > 1) {
+                    mp.cache_indir   = cache_indir;
+                    mp.beam_width    = ses.K;
+                    mp.max_input_len = ses.S;
+                    mp.indir_plane   = (size_t)B * s_max;
+                }
+                launch_mmha(mp, st);
+            };
+            auto reduce = [&](f16* buf, size_t count, hipStream_t st, bool scaled) { allreduce(buf, count, st, scaled); };
+            auto time   = [&](double bytes, auto&& launch, hipStream_t st) { timed(KIND_SMALLM, bytes, launch, st); };
+            if (decoder_overlapped(B)) {
+                Range ro("ftcf.GptNeoXDecoder.overlapped");
+                layer_walk().forward_overlapped(B, attention, reduce, time);
+                return;
+            }
+            // Up to SMALLM_MAX_ROWS rows the attention and the FFN branch on two streams, else up to 16 rows the independent GEMMs
+            // paired per launch, else gemm()
+            const DecodeGemms gemms = (B <= SMALLM_MAX_ROWS && smallm_ws && decode_branches && side) ? DecodeGemms::branches
+                                      : (B <= 16 && smallm_ws)                                    ? DecodeGemms::grouped
+                                                                                                   : DecodeGemms::plain;
+            layer_walk().forward(B, gemms, attention, reduce, time);
             return;
         }
         for (int l = 0; l < L; l++) {
             const LayerWeights& w = layers[l];
-            // layer_input/output alias for 0 < l < L-1 in the reference (:249-250) -> which residual form it runs
-            const int inplace = (l > 0 && l < L - 1) ? 1 : 0;
             if (staged) {
+                // layer_input/output alias for 0 < l < L-1 in the reference (:249-250) -> which residual form it runs
+                const int inplace = (l > 0 && l < L - 1) ? 1 : 0;
                 // Per-stage launches over row groups of <= 4 rows (the GEMV kernels' register budget).  STAGE_MAX_ROWS > 4
                 // would replay every stage per group; measured no faster than the batched GEMM path (the m = 4 forms
                 // of these kernels stream at half the m = 1 rate), so larger batches take the small-m GEMM below.
@@ -1007,123 +1036,50 @@ struct ftcf_gptneox {
                         stage_launch(stage, l, w, inplace, B, s_max, r0, M, l + rg * L, ngrp == 1);
                     }
                 }
+                allreduce(x, (size_t)B * H);
+                continue;
             }
-            else {
-                // general path: both LayerNorms of the layer come from one pass over x, fused with the previous layer's
-                // residual when there is no collective in between
-                MmhaParams mp = mmha_params(l, w, B, s_max, 0, B, l);
-                if (ses.K > 1) {
-                    mp.cache_indir   = cache_indir;
-                    mp.beam_width    = ses.K;
-                    mp.max_input_len = ses.S;
-                    mp.indir_plane   = (size_t)B * s_max;
-                }
-                if (!cfg.use_gptj_residual) {
-                    // sequential residual (GptNeoXDecoder.cc:313-331,362-367): h = attn + bias + x ; x' = ffn(LN2(h)) + bias + h
-                    launch_layernorm(x, w.ln1_g, w.ln1_b, nrm, B, H, 1e-5f, true, stream);
-                    self_attention_layer.forward(nrm, qkv, ctx, att, w, mp, B, stream);
-                    allreduce(att, (size_t)B * H);
-                    launch_add_bias_residual(att, x, att, w.attn_out.bias, B, H, stream);
-                    launch_layernorm(att, w.ln2_g, w.ln2_b, nrm, B, H, 1e-5f, true, stream);
-                    ffn_layer.forward(nrm, mid, ffn, w, B, stream);
-                    allreduce(ffn, (size_t)B * H);
-                    launch_add_bias_residual(x, ffn, att, w.ffn2.bias, B, H, stream);
-                    continue;
-                }
-                const bool dual = residual_dual_ln_supported(H);
-                const bool tp1  = cfg.tensor_para_size == 1;
-                if (!dual) {
-                    launch_layernorm(x, w.ln1_g, w.ln1_b, nrm, B, H, 1e-5f, true, stream);
-                    launch_layernorm(x, w.ln2_g, w.ln2_b, nrm2, B, H, 1e-5f, true, stream);
-                }
-                else if (l == 0 || (!tp1 && !tp_pair_ar)) {
-                    launch_residual_dual_ln(x, nullptr, nullptr, nullptr, 1, 0, w.ln1_g, w.ln1_b, w.ln2_g, w.ln2_b, nrm,
-                                            nrm2, B, H, 1e-5f, stream);
-                }
-                if (B <= SMALLM_MAX_ROWS && smallm_ws && decode_branches && side) {
-                    // The attention branch [QKV -> MMHA -> out-proj] (78.6 + K/V + 26.2 MB at 13B int8) and the FFN branch
-                    // [FFN1 -> FFN2] (2 x 104.9 MB) of a parallel-residual layer are independent: two streams.  Every one
-                    // of these launches is a short burst -- the whole matrix requested at once, gone in ~30 us -- whose
-                    // ramp-up and drain leave the HBM idle; the other branch's launch fills those gaps.
-                    const int    bc = std::min(B, 16);
-                    const size_t o_qkv = 0, o_f1 = o_qkv + gemm_smallm_workspace_bytes(bc, 3 * hl, H, int8),
-                                 o_out = o_f1 + gemm_smallm_workspace_bytes(bc, il, H, int8),
-                                 o_f2  = o_out + gemm_smallm_workspace_bytes(bc, H, hl, int8);
-                    auto one = [&](const SmallmDesc& d0, size_t off, hipStream_t s) {
-                        // (one launch that keeps the weights in registers and passes the rows 16 at a time through the x tile
-                        // was measured: 256 VGPRs, one workgroup per CU -- 8.2 / 8.3 / 13.0 ms at 24 / 32 / 64 rows, i.e.
-                        // slower than re-reading the weights per 16 rows except at 64)
-                        for (int r0 = 0; r0 < B; r0 += 16) {  // 16 rows per launch (launches of one GEMM are in stream order)
-                            SmallmDesc d = d0;
-                            d.A          = d0.A + (size_t)r0 * d0.k;
-                            d.C          = d0.C + (size_t)r0 * d0.n;
-                            const int M  = std::min(16, B - r0);
-                            timed(KIND_SMALLM, wbytes * (double)d.n * d.k, [&] {
-                                launch_gemm_smallm_group(&d, 1, smallm_ws, smallm_partial, M, int8, s, &state->step, &smallm_seq, off);
-                            }, s);
-                        }
-                    };
-                    // the attention layer on the engine stream, the FFN layer on the side stream: the same two layer units, their
-                    // GEMMs bound to the burst kernel with one workspace region per GEMM of the layer
-                    const size_t offs[4] = {o_qkv, o_f1, o_out, o_f2};
-                    GemmFn burst = [&](const f16* A, const DenseWeight& dw, const f16* bias, int act, f16* C, int, int n, int k,
-                                       hipStream_t s, int slot) { one(SmallmDesc{A, dw.kernel, dw.scale, bias, act, C, n, k}, offs[slot], s); };
-                    const DecoderSelfAttentionLayer attn_b{burst, H, hl};
-                    const FfnLayer                  ffn_b{burst, H, il};
-                    FTCF_HIP_CHECK(hipEventRecord(ev_fork, stream));
-                    FTCF_HIP_CHECK(hipStreamWaitEvent(side, ev_fork, 0));
-                    attn_b.forward(nrm, qkv, ctx, att, w, mp, B, stream);
-                    ffn_b.forward(nrm2, mid, ffn, w, B, side);
-                    FTCF_HIP_CHECK(hipEventRecord(ev_join, side));
-                    FTCF_HIP_CHECK(hipStreamWaitEvent(stream, ev_join, 0));
-                }
-                else if (B <= 16 && smallm_ws) {
-                    // independent GEMMs share a launch (a dependent launch costs ~8 us of dispatch latency, most of a layer
-                    // at tensor-parallel shard sizes): [QKV, FFN1] -> MMHA -> [out-proj, FFN2]
-                    const SmallmDesc p1[2] = {{nrm, w.qkv.kernel, w.qkv.scale, nullptr, 0, qkv, 3 * hl, H},
-                                              {nrm2, w.ffn1.kernel, w.ffn1.scale, w.ffn1.bias, 1, mid, il, H}};
-                    timed(KIND_SMALLM, wbytes * H * (3.0 * hl + il),
-                          [&] { launch_gemm_smallm_group(p1, 2, smallm_ws, smallm_partial, B, int8, stream, &state->step, &smallm_seq); });
-                    launch_mmha(mp, stream);
-                    const SmallmDesc p3[2] = {{ctx, w.attn_out.kernel, w.attn_out.scale, nullptr, 0, att, H, hl},
-                                              {mid, w.ffn2.kernel, w.ffn2.scale, nullptr, 0, ffn, H, il}};
-                    timed(KIND_SMALLM, wbytes * H * ((double)hl + il),
-                          [&] { launch_gemm_smallm_group(p3, 2, smallm_ws, smallm_partial, B, int8, stream, &state->step, &smallm_seq); });
-                }
-                else {
-                    self_attention_layer.forward(nrm, qkv, ctx, att, w, mp, B, stream);
-                    ffn_layer.forward(nrm2, mid, ffn, w, B, stream);
-                }
-                if (dual && !tp1 && tp_pair_ar) {
-                    // Tensor parallel: the reference closes the layer with x / TP + attn + ffn + bias and ONE all-reduce of the sum
-                    // (GptNeoXDecoder.cc:342-359, add_residual_kernels.cu:116-152), then the next layer's LayerNorms: three launches
-                    // on a path that is bound by the latency of dependent launches.  Here attn | ffn (adjacent in the arena) travel
-                    // as one message of twice the size and the residual -- x + attn + ffn + TP x (bias / TP) in fp32, rounded once
-                    // -- runs inside the next layer's LayerNorm pass, as at TP = 1: two launches (FTCF_TP_PAIR_AR=0: the former).
-                    allreduce(att, (size_t)2 * B * H, nullptr, true);
-                    const LayerWeights* nx = l + 1 < L ? &layers[l + 1] : nullptr;
-                    launch_residual_dual_ln(x, ffn, att, w.ffn2.bias, 1, 1, nx ? nx->ln1_g : nullptr, nx ? nx->ln1_b : nullptr,
-                                            nx ? nx->ln2_g : nullptr, nx ? nx->ln2_b : nullptr, nrm, nrm2, B, H, 1e-5f, stream,
-                                            cfg.tensor_para_size, fake_peers_mul());
-                    continue;
-                }
-                if (dual && tp1) {
-                    const LayerWeights* nx = l + 1 < L ? &layers[l + 1] : nullptr;
-                    launch_residual_dual_ln(x, ffn, att, w.ffn2.bias, 1, inplace, nx ? nx->ln1_g : nullptr,
-                                            nx ? nx->ln1_b : nullptr, nx ? nx->ln2_g : nullptr, nx ? nx->ln2_b : nullptr,
-                                            nrm, nrm2, B, H, 1e-5f, stream);
-                }
-                else {
-                    launch_add_bias_attn_ffn_residual(x, ffn, att, x, w.ffn2.bias, B, H, cfg.tensor_para_size, inplace,
-                                                      true, stream);
-                }
+            // sequential residual (GptNeoXDecoder.cc:313-331,362-367): h = attn + bias + x ; x' = ffn(LN2(h)) + bias + h
+            MmhaParams mp = mmha_params(l, w, B, s_max, 0, B, l);
+            if (ses.K > 1) {
+                mp.cache_indir   = cache_indir;
+                mp.beam_width    = ses.K;
+                mp.max_input_len = ses.S;
+                mp.indir_plane   = (size_t)B * s_max;
             }
-            allreduce(x, (size_t)B * H);
+            launch_layernorm(x, w.ln1_g, w.ln1_b, nrm, B, H, 1e-5f, true, stream);
+            self_attention_layer.forward(nrm, qkv, ctx, att, w, [&] { launch_mmha(mp, stream); }, B, stream);
+            allreduce(att, (size_t)B * H);
+            launch_add_bias_residual(att, x, att, w.attn_out.bias, B, H, stream);
+            launch_layernorm(att, w.ln2_g, w.ln2_b, nrm, B, H, 1e-5f, true, stream);
+            ffn_layer.forward(nrm, mid, ffn, w, B, stream);
+            allreduce(ffn, (size_t)B * H);
+            launch_add_bias_residual(x, ffn, att, w.ffn2.bias, B, H, stream);
         }
     }
 
+    // the batched parallel-residual decode layers (layers.hip.h) over this engine's decode buffers, burst workspace and streams
+    ParallelResidualDecoder layer_walk()
+    {
+        ParallelResidualDecoder d;
+        d.layers = layers.data();
+        d.L = L, d.H = H, d.hl = hl, d.il = il;
+        d.int8 = int8;
+        d.tp = cfg.tensor_para_size;
+        d.fake_mul = fake_peers_mul();
+        d.pair_ar = tp_pair_ar;
+        d.x = x, d.nrm = nrm, d.nrm2 = nrm2, d.qkv = qkv, d.ctx = ctx, d.att = att, d.ffn = ffn, d.mid = mid;
+        d.ws = smallm_ws, d.partial = smallm_partial, d.region = smallm_region;
+        d.d_step = &state->step;
+        d.seq = &smallm_seq;
+        d.plain = self_attention_layer.gemm;
+        d.stream = stream, d.side = side, d.side2 = side2;
+        d.ev_fork = ev_fork, d.ev_join = ev_join;
+        d.dv_fork = dv_fork, d.dv_done = dv_done, d.dv_red = dv_red;
+        return d;
+    }
     // Batched decode under tensor parallelism with the layer's all-reduce OFF the compute stream (GptNeoXDecoder.cc:342-359 runs it
-    // in line).  A parallel-residual layer has ONE reduction, of x' = x + attn + ffn, and everything of the next layer depends on
+    // in line; the walk itself is ParallelResidualDecoder::forward_overlapped, layers.hip.h).  A parallel-residual layer has ONE reduction, of x' = x + attn + ffn, and everything of the next layer depends on
     // it: the only independent work is another row's.  So the batch is cut in two micro-batches of <= 16 rows that walk the
     // layers on TWO compute streams, independent of each other from the token's embedding to its final LayerNorm; micro-batch c
     // hands x' to the comm stream by event and waits for the reduced x' by event before its next layer, so c's reduction runs
@@ -1131,8 +1087,8 @@ struct ftcf_gptneox {
     // (a TP 8 shard's layer at 16 rows: six launches, 43 us, 39 MB), one micro-batch's launch gaps are filled by the other's
     // kernels.  Each micro-batch reads the layer's weight shard once: for 17..32 rows that is what the chunked GEMMs do anyway, for
     // 4..16 rows it doubles the weight bytes.  All reductions sit on ONE stream in the order c = 0, 1, 0, 1, ...: the window
-    // all-reduce's flag words and RCCL see a serial sequence, identical on every rank.  Row-wise arithmetic is that of the loop
-    // below (the burst GEMM's K slices do not depend on the row count; the micro-batches' GEMMs have their own split-K regions), so
+    // all-reduce's flag words and RCCL see a serial sequence, identical on every rank.  Row-wise arithmetic is that of the whole-batch
+    // walk (the burst GEMM's K slices do not depend on the row count; the micro-batches' GEMMs have their own split-K regions), so
     // the tokens are bit-identical to the un-overlapped path (tests/test_gpu_tp_overlap.py, test_gpu_tp_process.py).
     // FTCF_DECODE_OVERLAP = 1 switches it on; "auto" (ranks joined by RCCL): the first eligible request's token loop runs plain,
     // the second one overlapped, every rank keeps the slowest rank's ms per step (comm_max in finish()) and the engine stays with
@@ -1166,8 +1122,7 @@ struct ftcf_gptneox {
     bool decode_overlap_wanted(int B, bool* auto_trial = nullptr) const
     {
         // (decode_overlap_mode: FTCF_DECODE_OVERLAP read when a request begins -- 0, the default, 1, or 2 = "auto")
-        const bool  aut = decode_overlap_mode == 2 && cfg.tensor_para_size > 1 && cfg.comm && cfg.comm->comm && !cfg.comm->local
-                         && !cfg.comm->hx && cfg.comm->world > 1;
+        const bool  aut = decode_overlap_mode == 2 && rccl_ranks();
         const int   env = decode_overlap_mode == 1 ? 1 : 0;
         if ((!env && !aut) || !decode_overlap_shape(B)) {
             return false;
@@ -1177,7 +1132,8 @@ struct ftcf_gptneox {
         }
         return !aut || dv_trial == 1 || (dv_trial == 2 && dv_ms[1] < dv_ms[0]);
     }
-    bool decoder_overlapped(int B, int s_max)
+    // whether this step's layers take the overlapped walk (ParallelResidualDecoder::forward_overlapped); makes its streams ready
+    bool decoder_overlapped(int B)
     {
         bool aut = false;
         const bool want = decode_overlap_wanted(B, &aut);
@@ -1185,70 +1141,8 @@ struct ftcf_gptneox {
         if (!want) {
             return false;
         }
-        Range r("ftcf.GptNeoXDecoder.overlapped");
         dv_ran = true;
         decode_overlap_streams();
-        const double      wbytes = int8 ? 1.0 : 2.0;
-        const int         r0[2] = {0, (B + 1) / 2}, r1[2] = {(B + 1) / 2, B};
-        const hipStream_t cs[2] = {stream, side2};
-        // what is on the engine stream so far (embedding rows, the step's state) happens-before both micro-batches
-        FTCF_HIP_CHECK(hipEventRecord(dv_fork[0], stream));
-        FTCF_HIP_CHECK(hipStreamWaitEvent(side2, dv_fork[0], 0));
-        for (int l = 0; l < L; l++) {
-            const LayerWeights& w = layers[l];
-            const int inplace = (l > 0 && l < L - 1) ? 1 : 0;
-            for (int c = 0; c < 2; c++) {
-                const int         M  = r1[c] - r0[c];
-                const size_t      o  = (size_t)r0[c], wo = (size_t)c * smallm_region;
-                const hipStream_t st = cs[c];
-                f16*              xr = x + o * H;
-                if (l > 0 && !tp_pair_ar) {
-                    FTCF_HIP_CHECK(hipStreamWaitEvent(st, dv_red[c], 0));  // this micro-batch's x has been reduced
-                }
-                // (a micro-batch's attn | ffn rows are adjacent: [2 r0 H, 2 r0 H + M H) and the M H behind it)
-                f16* const attc = att + 2 * o * H;
-                f16* const ffnc = attc + (size_t)M * H;
-                if (l == 0 || !tp_pair_ar) {
-                    launch_residual_dual_ln(xr, nullptr, nullptr, nullptr, 1, 0, w.ln1_g, w.ln1_b, w.ln2_g, w.ln2_b, nrm + o * H,
-                                            nrm2 + o * H, M, H, 1e-5f, st);
-                }
-                MmhaParams mp = mmha_params(l, w, B, s_max, r0[c], M, l);
-                // [QKV, FFN1] -> MMHA -> [out-proj, FFN2], independent GEMMs in one launch (as the loop below)
-                const SmallmDesc p1[2] = {{nrm + o * H, w.qkv.kernel, w.qkv.scale, nullptr, 0, qkv + o * 3 * hl, 3 * hl, H},
-                                          {nrm2 + o * H, w.ffn1.kernel, w.ffn1.scale, w.ffn1.bias, 1, mid + o * il, il, H}};
-                timed(KIND_SMALLM, wbytes * H * (3.0 * hl + il), [&] {
-                    launch_gemm_smallm_group(p1, 2, smallm_ws, smallm_partial, M, int8, st, &state->step, &smallm_seq, wo);
-                }, st);
-                launch_mmha(mp, st);
-                const SmallmDesc p3[2] = {{ctx + o * hl, w.attn_out.kernel, w.attn_out.scale, nullptr, 0, attc, H, hl},
-                                          {mid + o * il, w.ffn2.kernel, w.ffn2.scale, nullptr, 0, ffnc, H, il}};
-                timed(KIND_SMALLM, wbytes * H * ((double)hl + il), [&] {
-                    launch_gemm_smallm_group(p3, 2, smallm_ws, smallm_partial, M, int8, st, &state->step, &smallm_seq, wo);
-                }, st);
-                if (!tp_pair_ar) {
-                    launch_add_bias_attn_ffn_residual(xr, ffnc, attc, xr, w.ffn2.bias, M, H, cfg.tensor_para_size, inplace, true, st);
-                }
-                FTCF_HIP_CHECK(hipEventRecord(dv_done[c], st));
-                FTCF_HIP_CHECK(hipStreamWaitEvent(side, dv_done[c], 0));
-                allreduce(tp_pair_ar ? attc : xr, (size_t)(tp_pair_ar ? 2 : 1) * M * H, side, tp_pair_ar);
-                FTCF_HIP_CHECK(hipEventRecord(dv_red[c], side));
-                if (tp_pair_ar) {
-                    // the layer's residual inside the next layer's LayerNorm pass, behind the reduction (general loop below)
-                    const LayerWeights* nx = l + 1 < L ? &layers[l + 1] : nullptr;
-                    FTCF_HIP_CHECK(hipStreamWaitEvent(st, dv_red[c], 0));
-                    launch_residual_dual_ln(xr, ffnc, attc, w.ffn2.bias, 1, 1, nx ? nx->ln1_g : nullptr, nx ? nx->ln1_b : nullptr,
-                                            nx ? nx->ln2_g : nullptr, nx ? nx->ln2_b : nullptr, nrm + o * H, nrm2 + o * H, M, H, 1e-5f,
-                                            st, cfg.tensor_para_size, fake_peers_mul());
-                }
-            }
-        }
-        // join: both micro-batches' last reductions, and the second compute stream itself (its last wait is for dv_red[1] of layer
-        // L - 2: nothing of it is left running behind dv_red[1] of the last layer, but a capture wants every fork joined)
-        FTCF_HIP_CHECK(hipEventRecord(dv_fork[1], side2));
-        FTCF_HIP_CHECK(hipStreamWaitEvent(stream, dv_fork[1], 0));
-        for (int c = 0; c < 2; c++) {
-            FTCF_HIP_CHECK(hipStreamWaitEvent(stream, dv_red[c], 0));
-        }
         return true;
     }
 

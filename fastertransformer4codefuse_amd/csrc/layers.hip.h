@@ -1,16 +1,19 @@
 // Host-side layer units of the GPT-NeoX decode path: what the reference's layer classes do, as sequences of this library's
 // HIP launches on a caller-given stream.  No layer owns memory (the reference's allocateBuffer / freeBuffer per call,
 // DecoderSelfAttentionLayer.cc:148-187, FfnLayer.cc:455-530, are the engine's one arena: engine.hip plan()), no layer
-// synchronises, and none calls a collective: a parallel-residual layer reduces x' ONCE, after the residual
-// (GptNeoXDecoder.cc:342-359), which is the decoder's business.
+// synchronises, and none calls a collective itself: a parallel-residual layer reduces x' ONCE, after the residual
+// (GptNeoXDecoder.cc:342-359), which is the decoder's business -- ParallelResidualDecoder is handed the all-reduce by its caller.
 //
 //   DecoderSelfAttentionLayer  <- layers/attention_layers/DecoderSelfAttentionLayer.cc:459-686 (+ TensorParallel wrapper :190-226)
 //   GptContextAttentionLayer   <- layers/attention_layers/GptContextAttentionLayer.cc:25-403
 //   FfnLayer (GeluFfnLayer)    <- layers/FfnLayer.cc:34-380, TensorParallelGeluFfnLayer.cc:33-63
+//   ParallelResidualDecoder    <- models/gptneox/GptNeoXDecoder.cc:245-384 (use_gptj_residual), the batched decode rows
 //   DynamicDecodeLayer         <- layers/DynamicDecodeLayer.cc:192-497 (sampling layers, online beam search)
 //
-// The fused forms -- the persistent decode kernel (persist_device.hip.h), the per-stage GEMV launches, the grouped burst GEMM
-// that runs two layers' independent GEMMs in one launch -- cut ACROSS these units on purpose and stay in engine.hip.
+// ParallelResidualDecoder is the ONE walk over the layers of a batched decode step: the engine's general path and its overlapped
+// form, the speculative verify pass and the continuous batcher (plain and overlapped) run it with their own attention launch,
+// buffers and GEMM binding.  The fused forms -- the persistent decode kernel (persist_device.hip.h), the rows kernel, the
+// per-stage GEMV launches -- cut ACROSS these units on purpose and stay in engine.hip.
 #pragma once
 #include <functional>
 
@@ -39,20 +42,13 @@ struct DecoderSelfAttentionLayer {
     int    H = 0, hl = 0;  // hidden size, local hidden size (heads of this rank x size_per_head)
     // in [m, H] (LayerNorm'd) -> qkv_buf [m, 3 hl] -> masked multi-head attention over the K/V cache (appends this step's
     // key / value; qkv bias and NeoX rotary inside the kernel like the reference's) -> ctx [m, hl] -> out [m, H] (no bias:
-    // it rides on the residual kernel)
-    void forward(const f16* in, f16* qkv_buf, const f16* ctx_buf, f16* out, const LayerWeights& w, const MmhaParams& mp, int m,
+    // it rides on the residual kernel).  attention(): the caller's launch over its K/V cache -- contiguous, paged, the verify pass's
+    template<typename Attention>
+    void forward(const f16* in, f16* qkv_buf, const f16* ctx_buf, f16* out, const LayerWeights& w, Attention&& attention, int m,
                  hipStream_t s) const
     {
         gemm(in, w.qkv, nullptr, 0, qkv_buf, m, 3 * hl, H, s, 0);
-        launch_mmha(mp, s);
-        gemm(ctx_buf, w.attn_out, nullptr, 0, out, m, H, hl, s, 2);
-    }
-    // the same over a paged K/V pool (continuous batching)
-    void forward_paged(const f16* in, f16* qkv_buf, const f16* ctx_buf, f16* out, const LayerWeights& w, const MmhaPagedParams& mp,
-                       int max_len, int m, hipStream_t s) const
-    {
-        gemm(in, w.qkv, nullptr, 0, qkv_buf, m, 3 * hl, H, s, 0);
-        launch_mmha_paged(mp, max_len, s);
+        attention();
         gemm(ctx_buf, w.attn_out, nullptr, 0, out, m, H, hl, s, 2);
     }
 };
@@ -84,6 +80,203 @@ struct FfnLayer {
     {
         gemm(in, w.ffn1, w.ffn1.bias, 1, mid_buf, m, il, H, s, 1);
         gemm(mid_buf, w.ffn2, nullptr, 0, out, m, H, il, s, 3);
+    }
+};
+
+// How a batched decode layer's four GEMMs are launched (the caller decides by its own eligibility rules):
+//   branches: [QKV -> attention -> out-proj] on `stream`, [FFN1 -> FFN2] on `side`, one burst launch per GEMM per 16 rows
+//   grouped:  independent GEMMs share a launch, [QKV, FFN1] -> attention -> [out-proj, FFN2] (<= 16 rows)
+//   plain:    the caller's row-count dispatch, one GEMM after the other
+enum class DecodeGemms { branches, grouped, plain };
+
+struct Untimed {  // (the timing hook of a caller that keeps no profiling records)
+    template<typename F>
+    void operator()(double, F&& f, hipStream_t) const
+    {
+        f();
+    }
+};
+
+// The layers of one batched decode step of a parallel-residual model (GptNeoXDecoder.cc:245-384): per layer the entry LayerNorms
+// (one dual-LN pass over x), [QKV, FFN1], attention, [out-proj, FFN2] and the closing residual -- fused into the next layer's
+// LayerNorm pass where no all-reduce of x' stands in between.  The callers pass
+//   attention(l, w, r0, M, s):       their attention launch for rows [r0, r0 + M) of layer l on stream s
+//   allreduce(buf, count, s, scaled): the layer's all-reduce (scaled: the kernel that reads the sum applies fake_mul itself)
+//   timed(bytes, launch, s):          their profiling bracket around a burst GEMM launch
+struct ParallelResidualDecoder {
+    const LayerWeights* layers = nullptr;
+    int                 L = 0, H = 0, hl = 0, il = 0;
+    bool                int8 = false;
+    int                 tp = 1, fake_mul = 1;  // tensor-parallel size, fake-peer multiplier of the summed attn | ffn
+    // tp > 1: attn | ffn all-reduced as ONE message and the residual inside the next layer's LayerNorm pass, as at tp = 1: two
+    // launches where the reference's residual -> all-reduce -> LayerNorms (GptNeoXDecoder.cc:342-359) are three
+    bool                pair_ar = false;
+    // the buffer view, row-major: x [rows, H], nrm / nrm2 [rows, H], qkv [rows, 3 hl], ctx [rows, hl], att / ffn [rows, H], mid [rows, il]
+    f16 *x = nullptr, *nrm = nullptr, *nrm2 = nullptr, *qkv = nullptr, *ctx = nullptr, *att = nullptr, *ffn = nullptr, *mid = nullptr;
+    // the burst GEMM's workspace ([partial bytes of split-K sums][tickets]), device step pointer and host launch counter (its
+    // granule tags); region: the bytes one micro-batch's GEMMs use
+    float*          ws = nullptr;
+    size_t          partial = 0, region = 0;
+    const int*      d_step = nullptr;
+    unsigned*       seq = nullptr;
+    GemmFn          plain;  // DecodeGemms::plain
+    hipStream_t     stream = nullptr, side = nullptr, side2 = nullptr;  // side: FFN branch / the reductions; side2: second micro-batch
+    hipEvent_t      ev_fork = nullptr, ev_join = nullptr;
+    const hipEvent_t *dv_fork = nullptr, *dv_done = nullptr, *dv_red = nullptr;  // [2] each, forward_overlapped
+
+    bool pair() const { return tp > 1 && pair_ar && residual_dual_ln_supported(H); }
+
+    // the whole batch on `stream`
+    template<typename Attention, typename AllReduce, typename Timed = Untimed>
+    void forward(int B, DecodeGemms gemms, Attention&& attention, AllReduce&& allreduce, Timed&& timed = Timed{}) const
+    {
+        FTCF_CHECK_ARG(!pair() || ffn == att + (size_t)B * H, "the pair all-reduce needs ffn directly behind att");
+        DecoderSelfAttentionLayer attn_u{plain, H, hl};
+        FfnLayer                  ffn_u{plain, H, il};
+        if (gemms == DecodeGemms::branches) {
+            // The attention branch [QKV -> MMHA -> out-proj] (78.6 + K/V + 26.2 MB at 13B int8) and the FFN branch
+            // [FFN1 -> FFN2] (2 x 104.9 MB) of a parallel-residual layer are independent: two streams.  Every one
+            // of these launches is a short burst -- the whole matrix requested at once, gone in ~30 us -- whose
+            // ramp-up and drain leave the HBM idle; the other branch's launch fills those gaps.  The same two layer units,
+            // their GEMMs bound to the burst kernel with one workspace region per GEMM of the layer.
+            const int    bc      = std::min(B, 16);
+            const size_t o_f1    = gemm_smallm_workspace_bytes(bc, 3 * hl, H, int8);
+            const size_t o_out   = o_f1 + gemm_smallm_workspace_bytes(bc, il, H, int8);
+            const size_t offs[4] = {0, o_f1, o_out, o_out + gemm_smallm_workspace_bytes(bc, H, hl, int8)};
+            const double wbytes  = int8 ? 1.0 : 2.0;
+            attn_u.gemm = [this, &timed, wbytes, offs](const f16* A, const DenseWeight& dw, const f16* bias, int act, f16* C, int m,
+                                                       int n, int k, hipStream_t s, int slot) {
+                // (one launch that keeps the weights in registers and passes the rows 16 at a time through the x tile
+                // was measured: 256 VGPRs, one workgroup per CU -- 8.2 / 8.3 / 13.0 ms at 24 / 32 / 64 rows, i.e.
+                // slower than re-reading the weights per 16 rows except at 64)
+                for (int r0 = 0; r0 < m; r0 += 16) {  // 16 rows per launch (launches of one GEMM are in stream order)
+                    const SmallmDesc d{A + (size_t)r0 * k, dw.kernel, dw.scale, bias, act, C + (size_t)r0 * n, n, k};
+                    timed(wbytes * (double)n * k, [&] {
+                        launch_gemm_smallm_group(&d, 1, ws, partial, std::min(16, m - r0), int8, s, d_step, seq, offs[slot]);
+                    }, s);
+                }
+            };
+            ffn_u.gemm = attn_u.gemm;
+        }
+        for (int l = 0; l < L; l++) {
+            layer(l, 0, B, att, ffn, stream, 0, gemms, attn_u, ffn_u, attention,
+                  [&](f16* buf, size_t count, bool scaled) { allreduce(buf, count, stream, scaled); }, timed);
+        }
+    }
+
+    // Two micro-batches, rows [0, (B + 1) / 2) on `stream` and the rest on `side2`, independent of each other from the first layer
+    // to the last; their reductions on `side` in the order c = 0, 1, 0, 1, ...: micro-batch c hands its sum over by event and waits
+    // for the reduced rows by event, so c's reduction runs under (1 - c)'s launches.  Grouped GEMMs, each micro-batch with its own
+    // split-K region.  Needs tp > 1 and the dual LayerNorm kernel (H % 8 == 0, H <= 8192).
+    template<typename Attention, typename AllReduce, typename Timed = Untimed>
+    void forward_overlapped(int B, Attention&& attention, AllReduce&& allreduce, Timed&& timed = Timed{}) const
+    {
+        // (a micro-batch's attn | ffn rows are adjacent: [2 r0 H, 2 r0 H + M H) and the M H behind it)
+        FTCF_CHECK_ARG(ffn == att + (size_t)B * H, "the micro-batches' attn | ffn need ffn directly behind att");
+        const int                       r0[2] = {0, (B + 1) / 2}, r1[2] = {(B + 1) / 2, B};
+        const hipStream_t               cs[2] = {stream, side2};
+        const bool                      pr = pair();
+        const DecoderSelfAttentionLayer no_attn{};
+        const FfnLayer                  no_ffn{};
+        // what is on `stream` so far (embedding rows, the step's state) happens-before both micro-batches
+        FTCF_HIP_CHECK(hipEventRecord(dv_fork[0], stream));
+        FTCF_HIP_CHECK(hipStreamWaitEvent(side2, dv_fork[0], 0));
+        for (int l = 0; l < L; l++) {
+            for (int c = 0; c < 2; c++) {
+                const int         M  = r1[c] - r0[c];
+                const hipStream_t st = cs[c];
+                if (l > 0 && !pr) {
+                    FTCF_HIP_CHECK(hipStreamWaitEvent(st, dv_red[c], 0));  // this micro-batch's x has been reduced
+                }
+                f16* const attc = att + 2 * (size_t)r0[c] * H;
+                layer(l, r0[c], M, attc, attc + (size_t)M * H, st, (size_t)c * region, DecodeGemms::grouped, no_attn, no_ffn, attention,
+                      [&](f16* buf, size_t count, bool scaled) {
+                          FTCF_HIP_CHECK(hipEventRecord(dv_done[c], st));
+                          FTCF_HIP_CHECK(hipStreamWaitEvent(side, dv_done[c], 0));
+                          allreduce(buf, count, side, scaled);
+                          FTCF_HIP_CHECK(hipEventRecord(dv_red[c], side));
+                          if (pr) {  // the layer's residual inside the next layer's LayerNorm pass, behind the reduction
+                              FTCF_HIP_CHECK(hipStreamWaitEvent(st, dv_red[c], 0));
+                          }
+                      },
+                      timed);
+            }
+        }
+        // join: both micro-batches' last reductions, and the second compute stream itself (its last wait is for dv_red[1] of layer
+        // L - 2: nothing of it is left running behind dv_red[1] of the last layer, but a capture wants every fork joined)
+        FTCF_HIP_CHECK(hipEventRecord(dv_fork[1], side2));
+        FTCF_HIP_CHECK(hipStreamWaitEvent(stream, dv_fork[1], 0));
+        for (int c = 0; c < 2; c++) {
+            FTCF_HIP_CHECK(hipStreamWaitEvent(stream, dv_red[c], 0));
+        }
+    }
+
+private:
+    // layer l for rows [r0, r0 + M) on stream s; attc / ffnc: where these rows' attention and FFN outputs go; reduce(buf, count,
+    // scaled): the layer's all-reduce as the walk mode orders it
+    template<typename Attention, typename Reduce, typename Timed>
+    void layer(int l, int r0, int M, f16* attc, f16* ffnc, hipStream_t s, size_t region_off, DecodeGemms gemms,
+               const DecoderSelfAttentionLayer& attn_u, const FfnLayer& ffn_u, Attention& attention, Reduce&& reduce, Timed& timed) const
+    {
+        const LayerWeights& w  = layers[l];
+        const LayerWeights* nx = l + 1 < L ? &layers[l + 1] : nullptr;
+        // layer_input/output alias for 0 < l < L-1 in the reference (:249-250) -> which residual form it runs
+        const int    inplace = (l > 0 && l < L - 1) ? 1 : 0;
+        const bool   dual = residual_dual_ln_supported(H), tp1 = tp == 1, pr = pair();
+        const size_t o  = (size_t)r0;
+        f16 *const   xr = x + o * H, *const n1 = nrm + o * H, *const n2 = nrm2 + o * H, *const q = qkv + o * 3 * hl,
+                     *const cx = ctx + o * hl, *const md = mid + o * il;
+        // both LayerNorms of the layer come from one pass over x, fused with the previous layer's residual when there is no
+        // collective in between
+        if (!dual) {
+            launch_layernorm(xr, w.ln1_g, w.ln1_b, n1, M, H, 1e-5f, true, s);
+            launch_layernorm(xr, w.ln2_g, w.ln2_b, n2, M, H, 1e-5f, true, s);
+        }
+        else if (l == 0 || (!tp1 && !pr)) {
+            launch_residual_dual_ln(xr, nullptr, nullptr, nullptr, 1, 0, w.ln1_g, w.ln1_b, w.ln2_g, w.ln2_b, n1, n2, M, H, 1e-5f, s);
+        }
+        if (gemms == DecodeGemms::grouped) {
+            // independent GEMMs share a launch (a dependent launch costs ~8 us of dispatch latency, most of a layer
+            // at tensor-parallel shard sizes): [QKV, FFN1] -> attention -> [out-proj, FFN2]
+            const double     wbytes = int8 ? 1.0 : 2.0;
+            const SmallmDesc p1[2]  = {{n1, w.qkv.kernel, w.qkv.scale, nullptr, 0, q, 3 * hl, H},
+                                       {n2, w.ffn1.kernel, w.ffn1.scale, w.ffn1.bias, 1, md, il, H}};
+            timed(wbytes * H * (3.0 * hl + il), [&] { launch_gemm_smallm_group(p1, 2, ws, partial, M, int8, s, d_step, seq, region_off); }, s);
+            attention(l, w, r0, M, s);
+            const SmallmDesc p3[2] = {{cx, w.attn_out.kernel, w.attn_out.scale, nullptr, 0, attc, H, hl},
+                                      {md, w.ffn2.kernel, w.ffn2.scale, nullptr, 0, ffnc, H, il}};
+            timed(wbytes * H * ((double)hl + il), [&] { launch_gemm_smallm_group(p3, 2, ws, partial, M, int8, s, d_step, seq, region_off); }, s);
+        }
+        else {
+            const bool fork = gemms == DecodeGemms::branches;
+            if (fork) {
+                FTCF_HIP_CHECK(hipEventRecord(ev_fork, s));
+                FTCF_HIP_CHECK(hipStreamWaitEvent(side, ev_fork, 0));
+            }
+            attn_u.forward(n1, q, cx, attc, w, [&] { attention(l, w, r0, M, s); }, M, s);
+            ffn_u.forward(n2, md, ffnc, w, M, fork ? side : s);
+            if (fork) {
+                FTCF_HIP_CHECK(hipEventRecord(ev_join, side));
+                FTCF_HIP_CHECK(hipStreamWaitEvent(s, ev_join, 0));
+            }
+        }
+        if (pr) {
+            // attn | ffn travel as one message of twice the size and the residual -- x + attn + ffn + TP x (bias / TP) in fp32,
+            // rounded once -- runs inside the next layer's LayerNorm pass (add_residual_kernels.cu:116-152 is the reference's)
+            reduce(attc, (size_t)2 * M * H, true);
+            launch_residual_dual_ln(xr, ffnc, attc, w.ffn2.bias, 1, 1, nx ? nx->ln1_g : nullptr, nx ? nx->ln1_b : nullptr,
+                                    nx ? nx->ln2_g : nullptr, nx ? nx->ln2_b : nullptr, n1, n2, M, H, 1e-5f, s, tp, fake_mul);
+        }
+        else if (dual && tp1) {
+            launch_residual_dual_ln(xr, ffnc, attc, w.ffn2.bias, 1, inplace, nx ? nx->ln1_g : nullptr, nx ? nx->ln1_b : nullptr,
+                                    nx ? nx->ln2_g : nullptr, nx ? nx->ln2_b : nullptr, n1, n2, M, H, 1e-5f, s);
+        }
+        else {
+            launch_add_bias_attn_ffn_residual(xr, ffnc, attc, xr, w.ffn2.bias, M, H, tp, inplace, true, s);
+            if (!tp1) {
+                reduce(xr, (size_t)M * H, false);
+            }
+        }
     }
 };
 

@@ -109,6 +109,19 @@ def test_end_id_stops_a_sequence_and_frees_its_slot(gh):
 @pytest.mark.parametrize("int8_mode,max_batch", [(0, 2), (1, 6), (1, 20)])
 def test_mid_model_batches_follow_the_engine(gh, int8_mode, max_batch):
     """1024-hidden model: max_batch 2 (GEMV forms), 6 (burst GEMMs with the in-launch split-K reduction), 20 (tiled GEMM)."""
+    _mid_model_batches_follow_the_engine(gh, int8_mode, max_batch)
+
+
+@pytest.mark.parametrize("max_batch", [6, 20])
+def test_mid_model_batches_off_the_branch_streams(gh, monkeypatch, max_batch):
+    """FTCF_DECODE_BRANCHES=0 at TP = 1, off the rows kernel (FTCF_BATCHER_ROWS=0): the decode step's layers on one stream, up
+    to 16 slots with the independent GEMMs paired per burst launch, above with one gemm_dispatch call per GEMM."""
+    monkeypatch.setenv("FTCF_DECODE_BRANCHES", "0")
+    monkeypatch.setenv("FTCF_BATCHER_ROWS", "0")
+    _mid_model_batches_follow_the_engine(gh, 1, max_batch)
+
+
+def _mid_model_batches_follow_the_engine(gh, int8_mode, max_batch):
     from fastertransformer4codefuse_amd.batcher import ContinuousBatcher
     cfg = MID
     w = random_model(cfg, seed=17)
@@ -361,6 +374,18 @@ def test_tensor_parallel_batchers_follow_the_single_gpu_engine(gh, monkeypatch, 
     every rank must emit the same events, and every request what the TP = 1 engine generates for it alone.
     overlap = 1 (round 5): the decode step's layers as two micro-batches of slots on two streams with the all-reduce on a third
     (FTCF_DECODE_OVERLAP=1; GptNeoXDecoder.cc:342-359 has it in line) -- same events, and the stats say it ran."""
+    _tensor_parallel_batchers_follow_the_single_gpu_engine(gh, monkeypatch, tp, max_batch, overlap)
+
+
+@pytest.mark.parametrize("overlap", [0, 1])
+def test_tensor_parallel_batchers_in_the_reference_order_of_residual_and_all_reduce(gh, monkeypatch, overlap):
+    """FTCF_TP_PAIR_AR=0: the decode step's layers close with residual -> all-reduce of x' -> LayerNorms (the reference's order)
+    where the default all-reduces attn | ffn as one message; two ranks, six slots, un-overlapped and overlapped."""
+    monkeypatch.setenv("FTCF_TP_PAIR_AR", "0")
+    _tensor_parallel_batchers_follow_the_single_gpu_engine(gh, monkeypatch, 2, 6, overlap)
+
+
+def _tensor_parallel_batchers_follow_the_single_gpu_engine(gh, monkeypatch, tp, max_batch, overlap):
     import threading
     monkeypatch.setenv("FTCF_DECODE_OVERLAP", str(overlap))
     from fastertransformer4codefuse_amd.batcher import ContinuousBatcher

@@ -113,6 +113,17 @@ def test_mid_model_decode_steps_above_16_rows(gh, monkeypatch, max_rows, int8_mo
     _mid_model_follows_the_oracle(gh, 20, int8_mode, out=6)
 
 
+@pytest.mark.one_decode_path
+@pytest.mark.parametrize("int8_mode", [0, 1])
+def test_mid_model_general_path_with_grouped_gemms(gh, monkeypatch, int8_mode):
+    """FTCF_DECODE_BRANCHES=0 at TP = 1: six rows on the general path (FTCF_ROWS=0 keeps the rows kernel off it) with the
+    independent GEMMs of a layer paired per launch on one stream, where the default is the two-stream branch form."""
+    monkeypatch.setenv("FTCF_ROWS", "0")
+    monkeypatch.setenv("FTCF_DECODE_BRANCHES", "0")
+    op = _mid_model_follows_the_oracle(gh, 6, int8_mode, out=8)
+    assert op.stats()["decode_path"] == 2
+
+
 def _mid_model_follows_the_oracle(gh, B, int8_mode, out=12):
     cfg = MID
     w = random_model(cfg, seed=B + 10 * int8_mode, std=0.04)
@@ -143,6 +154,7 @@ def _mid_model_follows_the_oracle(gh, B, int8_mode, out=12):
                 assert top2[1] - top2[0] < 2 * LOGIT_FRAC * np.abs(ref).max(), "token flip without a near tie"
                 break
     assert total_checked >= B * 2
+    return op
 
 
 def test_sampling_topk_topp_penalties_follow_oracle(gh, tiny):

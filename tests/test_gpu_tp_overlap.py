@@ -47,6 +47,23 @@ def test_batched_decode_with_overlapped_all_reduce_is_bit_identical(gh, monkeypa
     finish early and an odd row count (micro-batches of 4 + 3) -- and `decode_overlap` in the stats says which ran.  Above 16
     rows the un-overlapped path is the tiled GEMM over all rows, the micro-batches (12 + 11, 16 + 16) stay on the burst GEMM:
     close, not equal."""
+    _overlapped_and_plain_ranks_agree(gh, monkeypatch, rows, int8_mode, tp)
+
+
+def test_overlapped_all_reduce_in_the_reference_order_of_residual_all_reduce_layernorm(gh, monkeypatch):
+    """FTCF_TP_PAIR_AR=0: the layer closes as the reference's does (GptNeoXDecoder.cc:342-359) -- residual, all-reduce of x',
+    then the next layer's LayerNorms -- where the default sends attn | ffn as one message and runs the residual inside the
+    LayerNorm pass.  Seven rows (micro-batches of 4 + 3) of the int8 model on two ranks, un-overlapped and overlapped: both follow
+    the TP = 1 engine, the ranks agree token for token, and the overlapped run equals the un-overlapped one bit for bit: the
+    residual kernel and the all-reduce are elementwise and the LayerNorms row-wise, so the argument of the test above holds here too."""
+    monkeypatch.setenv("FTCF_TP_PAIR_AR", "0")
+    got, r1, lens, out = _overlapped_and_plain_ranks_agree(gh, monkeypatch, 7, 1, 2)
+    for mode in ("0", "1"):
+        check_ragged(r1, got[mode][0], lens, out, f"overlap {mode}, residual before the all-reduce, vs tp1 engine", 2e-2, MID["end_id"])
+        assert got[mode][1]["output_ids"].tolist() == got[mode][0]["output_ids"].tolist()
+
+
+def _overlapped_and_plain_ranks_agree(gh, monkeypatch, rows, int8_mode, tp):
     cfg = MID
     w = random_model(cfg, seed=33)
     rng = np.random.RandomState(rows)
@@ -97,4 +114,5 @@ def test_batched_decode_with_overlapped_all_reduce_is_bit_identical(gh, monkeypa
     r1 = gh.run_op(op1, ids, lens, out, cfg["vocab_size"], top_k=1)
     check_ragged(r1, got["1"][0], lens, out, f"overlapped decode, {rows} rows vs tp1 engine", 5e-3 if int8_mode == 0 else 2e-2,
                  cfg["end_id"])
+    return got, r1, lens, out
 
