@@ -72,6 +72,27 @@ class ResidualGemvArgs(C.Structure):  # ftcf_residual_gemv_args
         (n, C.c_int) for n in ("N", "K_a", "K_b", "tp", "inplace_variant")]
 
 
+class DynamicDecodeArgs(C.Structure):  # ftcf_dynamic_decode_args
+    _fields_ = [(n, C.c_void_p) for n in (
+        "logits", "output_ids", "finished", "seq_len", "cum_log_probs", "output_log_probs", "draw_counter", "pad_count",
+        "input_lengths", "stop_words", "optional_last_tokens", "row_len", "top_k", "top_p", "temperature",
+        "repetition_penalty", "min_length", "random_seed")] + [
+        ("all_finished", C.POINTER(C.c_int)), ("next_step", C.POINTER(C.c_int)), ("form", C.POINTER(C.c_int))] + [
+        (n, C.c_int) for n in (
+            "n_top_k", "n_top_p", "n_temperature", "n_repetition_penalty", "n_min_length", "n_random_seed", "stop_len",
+            "optional_count", "B", "V", "step", "max_input_len", "total_len", "end_id", "return_cum_log_probs", "finish")]
+
+
+class BeamSearchArgs(C.Structure):  # ftcf_beam_search_args
+    _fields_ = [(n, C.c_void_p) for n in (
+        "logits", "output_ids", "parent_ids", "finished", "seq_len", "cum_log_probs", "cache_indir", "input_lengths",
+        "stop_words", "optional_last_tokens", "temperature", "repetition_penalty", "beam_search_diversity_rate",
+        "len_penalty", "min_length")] + [
+        (n, C.c_int) for n in (
+            "n_temperature", "n_repetition_penalty", "n_beam_search_diversity_rate", "n_len_penalty", "n_min_length",
+            "stop_len", "optional_count", "B", "K", "V", "step", "max_input_len", "total_len", "s_max", "end_id")]
+
+
 class ForwardStats(C.Structure):
     _fields_ = [("prefill_ms", C.c_float), ("decode_ms", C.c_float), ("decode_steps", C.c_int),
                 ("gemv_ms_sum", C.c_float), ("gemv_launches", C.c_long), ("gemv_bytes", C.c_double),
@@ -93,6 +114,7 @@ EXPORTED = [
     "ftcf_masked_multihead_attention", "ftcf_masked_multihead_attention_workspace", "ftcf_context_attention",
     "ftcf_verify_attention", "ftcf_verify_attention_workspace", "ftcf_ngram_draft",
     "ftcf_paged_attention", "ftcf_scatter_kv_to_pages", "ftcf_gather_pages_to_kv",
+    "ftcf_dynamic_decode_step", "ftcf_beam_search_step",
     "ftcf_comm_get_unique_id", "ftcf_comm_init", "ftcf_comm_destroy", "ftcf_comm_local_unique_id",
     "ftcf_comm_init_local", "ftcf_comm_init_host_exchange", "ftcf_comm_allreduce_sum",
     "ftcf_comm_allgather", "ftcf_gptneox_create", "ftcf_gptneox_forward", "ftcf_gptneox_begin", "ftcf_gptneox_step", "ftcf_gptneox_finish",

@@ -502,6 +502,260 @@ extern "C" int ftcf_gather_pages_to_kv(void* k_cache, void* v_cache, const void*
     });
 }
 
+template<typename T>
+static std::vector<T> broadcast_arg(const T* p, int n, int B, T dflt, const char* name)
+{
+    std::vector<T> v((size_t)B, dflt);
+    if (n > 0) {
+        FTCF_CHECK_ARG(p != nullptr, std::string(name) + " pointer is NULL");
+        FTCF_CHECK_ARG(n == 1 || n == B, std::string(name) + " must have 1 or batch_size entries");
+        for (int b = 0; b < B; b++) {
+            v[b] = p[n == 1 ? 0 : b];
+        }
+    }
+    return v;
+}
+
+// The runtime-arg routing of TopKSamplingLayer.cu:27-77 / TopPSamplingLayer.cu:30-110 and the ALL_OF switches of
+// BaseSamplingLayer.cc:283-313, in ONE place (the engine's begin() and the kernel-level ftcf_dynamic_decode_step): from the
+// broadcast host arguments to what the decode kernels read.  k == 0 && p == 0 is greedy (k = 1), k is cut at 1024, a top-k row
+// without a p samples from all of its k, and a penalty switches on for the batch as soon as one row differs from its default.
+struct SamplingRouting {
+    std::vector<int>   k_eff;           // per row: the k of the top-k layer, 0 = the row belongs to the top-p layer
+    std::vector<float> p_topk, p_topp;  // per row: the p each layer uses
+    int  max_top_k = 1, any_top_p = 0, apply_temperature = 0, apply_repetition = 0;
+    bool any_min = false, rep_given = false;
+    // the host view of the batch; sp.repetition_penalty / sp.min_length hold the device copies and are dropped where not given
+    void apply(SamplingParams& sp) const
+    {
+        sp.max_top_k         = max_top_k;
+        sp.any_top_p         = any_top_p;
+        sp.apply_temperature = apply_temperature;
+        sp.apply_repetition  = apply_repetition;
+        if (!rep_given) {
+            sp.repetition_penalty = nullptr;
+        }
+        if (!any_min) {
+            sp.min_length = nullptr;
+        }
+    }
+};
+static SamplingRouting route_sampling_args(const std::vector<int>& top_k, const std::vector<float>& top_p, const std::vector<float>& temp,
+                                           const std::vector<float>& rep, const std::vector<int>& minl, bool rep_given)
+{
+    const int       batch = (int)top_k.size();
+    SamplingRouting r;
+    r.k_eff.resize(batch);
+    r.p_topk.resize(batch);
+    r.p_topp.resize(batch);
+    r.rep_given = rep_given;
+    bool temp_all_one = true, rep_all_default = true;
+    for (int b = 0; b < batch; b++) {
+        int   k = top_k[b];
+        float p = top_p[b];
+        FTCF_CHECK_ARG(k >= 0, "top_k must be >= 0");
+        if (k == 0 && p == 0.0f) {
+            k = 1;
+        }
+        float pk = p;
+        if (k > 0 && pk == 0.0f) {
+            pk = 1.0f;
+        }
+        r.k_eff[b]  = k > 1024 ? 1024 : k;
+        r.p_topk[b] = pk < 0.f ? 0.f : (pk > 1.f ? 1.f : pk);
+        r.p_topp[b] = p < 0.f ? 0.f : (p > 1.f ? 1.f : p);
+        temp_all_one &= (temp[b] == 1.0f);
+        rep_all_default &= (rep[b] == 1.0f);
+        r.any_min |= (minl[b] > 0);
+        r.max_top_k = std::max(r.max_top_k, r.k_eff[b]);
+        r.any_top_p |= (r.k_eff[b] == 0);
+    }
+    r.apply_temperature = temp_all_one ? 0 : 1;
+    r.apply_repetition  = (rep_given && !rep_all_default) ? 1 : 0;
+    return r;
+}
+
+// ---- one step of the dynamic-decode layer / of the beam-search layer on the CALLER's logits and state ----
+// (the engine and the batcher launch the same launchers; these entries own what a request's arena holds for them: the
+// DecodeState, the pinned flag words, the workspace and the device copies of the runtime arguments, for the one call)
+namespace {
+struct StepScratch {  // freed when the call returns, also when it throws
+    std::vector<void*> dev;
+    void*              pinned = nullptr;
+    ~StepScratch()
+    {
+        for (void* d : dev) {
+            (void)hipFree(d);
+        }
+        if (pinned) {
+            (void)hipHostFree(pinned);
+        }
+    }
+    template<typename T>
+    T* alloc(size_t n)
+    {
+        void* d = nullptr;
+        FTCF_HIP_CHECK(hipMalloc(&d, std::max<size_t>(n, 1) * sizeof(T)));
+        dev.push_back(d);
+        return (T*)d;
+    }
+    template<typename T>
+    T* upload(const std::vector<T>& v, hipStream_t s)
+    {
+        T* d = alloc<T>(v.size());
+        FTCF_HIP_CHECK(hipMemcpyAsync(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
+        return d;
+    }
+    DecodeState* state(int step, hipStream_t s)  // as k_decode_init leaves it, at `step`
+    {
+        const DecodeState h{step, 0, 0, 0};
+        DecodeState*      d = alloc<DecodeState>(1);
+        FTCF_HIP_CHECK(hipMemcpyAsync(d, &h, sizeof(h), hipMemcpyHostToDevice, s));
+        FTCF_HIP_CHECK(hipStreamSynchronize(s));  // (`h` dies at scope exit)
+        return d;
+    }
+};
+}  // namespace
+
+extern "C" int ftcf_dynamic_decode_step(const ftcf_dynamic_decode_args* a, void* stream)
+{
+    return guarded([&] {
+        require_device();
+        FTCF_CHECK_ARG(a != nullptr, "NULL arguments");
+        hipStream_t s = (hipStream_t)stream;
+        const int   B = a->B, V = a->V;
+        FTCF_CHECK_ARG(a->logits && a->output_ids && a->finished && a->seq_len && a->draw_counter && a->input_lengths, "NULL tensor");
+        FTCF_CHECK_ARG(B >= 1 && V >= 1 && a->max_input_len >= 0 && a->total_len >= 1, "dynamic decode step: bad geometry");
+        FTCF_CHECK_ARG(a->row_len || (a->step >= a->max_input_len && a->step <= a->total_len),
+                       "dynamic decode step: step must be in [max_input_len, total_len]");
+        FTCF_CHECK_ARG(a->end_id >= 0 && a->end_id < V, "dynamic decode step: end_id outside the vocabulary");
+        FTCF_CHECK_ARG(!a->output_log_probs || a->row_len || a->step < a->total_len, "output_log_probs has no row for step == total_len");
+        FTCF_CHECK_ARG(!a->stop_words || a->stop_len >= 1, "stop_words needs stop_len >= 1");
+        FTCF_CHECK_ARG(!a->optional_last_tokens || a->optional_count >= 1, "optional_last_tokens needs optional_count >= 1");
+        auto top_k = broadcast_arg<int>(a->top_k, a->n_top_k, B, 0, "top_k");
+        auto top_p = broadcast_arg<float>(a->top_p, a->n_top_p, B, 0.f, "top_p");
+        auto temp  = broadcast_arg<float>(a->temperature, a->n_temperature, B, 1.f, "temperature");
+        auto rep   = broadcast_arg<float>(a->repetition_penalty, a->n_repetition_penalty, B, 1.f, "repetition_penalty");
+        auto seed  = broadcast_arg<uint64_t>(a->random_seed, a->n_random_seed, B, 0, "random_seed");
+        auto minl  = broadcast_arg<int>(a->min_length, a->n_min_length, B, 0, "min_length");
+        const SamplingRouting route = route_sampling_args(top_k, top_p, temp, rep, minl, a->n_repetition_penalty > 0);
+
+        StepScratch    mem;
+        SamplingParams sp{};
+        sp.logits             = a->logits;
+        sp.B                  = B;
+        sp.V                  = V;
+        sp.max_input_len      = a->max_input_len;
+        sp.total_len          = a->total_len;
+        sp.end_id             = a->end_id;
+        sp.input_lengths      = a->input_lengths;
+        sp.top_k              = mem.upload(route.k_eff, s);
+        sp.top_p_topk         = mem.upload(route.p_topk, s);
+        sp.top_p_topp         = mem.upload(route.p_topp, s);
+        sp.temperature        = mem.upload(temp, s);
+        sp.repetition_penalty = mem.upload(rep, s);
+        sp.min_length         = mem.upload(minl, s);
+        route.apply(sp);
+        sp.random_seed          = mem.upload(seed, s);
+        sp.draw_counter         = a->draw_counter;
+        sp.stop_words           = a->stop_words;
+        sp.stop_len             = a->stop_len;
+        sp.optional_last_tokens = a->optional_last_tokens;
+        sp.optional_count       = a->optional_count;
+        sp.return_cum_log_probs = (a->return_cum_log_probs || a->output_log_probs) ? 1 : 0;
+        sp.output_ids           = a->output_ids;
+        sp.finished             = a->finished;
+        sp.seq_len              = a->seq_len;
+        sp.cum_log_probs        = a->cum_log_probs;
+        sp.output_log_probs     = a->output_log_probs;
+        sp.row_len              = a->row_len;
+        sp.pad_count            = a->pad_count;
+        if (!sp.pad_count) {
+            sp.pad_count = mem.alloc<int>(B);
+            FTCF_HIP_CHECK(hipMemsetAsync(sp.pad_count, 0, (size_t)B * sizeof(int), s));
+        }
+        sp.ws = mem.alloc<char>(sampling_workspace_bytes(B, V));
+        FTCF_HIP_CHECK(hipHostMalloc(&mem.pinned, 8 * sizeof(int), hipHostMallocDefault));
+        sp.h_flags = (int*)mem.pinned;
+        memset(sp.h_flags, 0, 8 * sizeof(int));
+        sp.state = mem.state(a->step, s);  // (synchronises: the host vectors above have been copied)
+        const bool finish = a->finish != 0;
+        if (a->form) {
+            *a->form = dynamic_decode_form(sp, finish);
+        }
+        launch_dynamic_decode(sp, s, finish);
+        DecodeState h{};
+        FTCF_HIP_CHECK(hipMemcpyAsync(&h, sp.state, sizeof(h), hipMemcpyDeviceToHost, s));
+        FTCF_HIP_CHECK(hipStreamSynchronize(s));
+        if (a->all_finished) {
+            *a->all_finished = h.all_finished;
+        }
+        if (a->next_step) {
+            *a->next_step = h.step;
+        }
+    });
+}
+
+extern "C" int ftcf_beam_search_step(const ftcf_beam_search_args* a, void* stream)
+{
+    return guarded([&] {
+        require_device();
+        FTCF_CHECK_ARG(a != nullptr, "NULL arguments");
+        hipStream_t s = (hipStream_t)stream;
+        const int   B = a->B, K = a->K, V = a->V;
+        FTCF_CHECK_ARG(a->logits && a->output_ids && a->parent_ids && a->finished && a->seq_len && a->cum_log_probs && a->cache_indir
+                           && a->input_lengths,
+                       "NULL tensor");
+        FTCF_CHECK_ARG(B >= 1 && K >= 2 && K <= BEAM_MAX_K && V >= K && a->max_input_len >= 0 && a->total_len >= 1 && a->s_max >= 1,
+                       "beam search step: bad geometry (beam_width in [2, 64], at least beam_width tokens)");
+        FTCF_CHECK_ARG(a->step >= a->max_input_len && a->step >= 1 && a->step < a->total_len,
+                       "beam search step: step must be in [max(1, max_input_len), total_len)");
+        FTCF_CHECK_ARG(a->end_id >= 0 && a->end_id < V, "beam search step: end_id outside the vocabulary");
+        FTCF_CHECK_ARG(!a->stop_words || a->stop_len >= 1, "stop_words needs stop_len >= 1");
+        FTCF_CHECK_ARG(!a->optional_last_tokens || a->optional_count >= 1, "optional_last_tokens needs optional_count >= 1");
+        auto temp = broadcast_arg<float>(a->temperature, a->n_temperature, B, 1.f, "temperature");
+        auto rep  = broadcast_arg<float>(a->repetition_penalty, a->n_repetition_penalty, B, 1.f, "repetition_penalty");
+        auto divr = broadcast_arg<float>(a->beam_search_diversity_rate, a->n_beam_search_diversity_rate, B, 0.f, "beam_search_diversity_rate");
+        auto lenp = broadcast_arg<float>(a->len_penalty, a->n_len_penalty, B, 0.f, "len_penalty");
+        auto minl = broadcast_arg<int>(a->min_length, a->n_min_length, B, 0, "min_length");
+        bool any_min = false;
+        for (int b = 0; b < B; b++) {
+            any_min |= (minl[b] > 0);
+        }
+        StepScratch mem;
+        BeamParams  bp{};
+        bp.logits               = a->logits;
+        bp.B                    = B;
+        bp.K                    = K;
+        bp.V                    = V;
+        bp.max_input_len        = a->max_input_len;
+        bp.total_len            = a->total_len;
+        bp.end_id               = a->end_id;
+        bp.s_max                = a->s_max;
+        bp.input_lengths        = a->input_lengths;
+        bp.temperature          = mem.upload(temp, s);
+        bp.repetition_penalty   = a->n_repetition_penalty > 0 ? mem.upload(rep, s) : nullptr;  // penalty type None otherwise
+        bp.diversity_rate       = mem.upload(divr, s);
+        bp.len_penalty          = mem.upload(lenp, s);
+        bp.min_length           = any_min ? mem.upload(minl, s) : nullptr;
+        bp.stop_words           = a->stop_words;
+        bp.stop_len             = a->stop_len;
+        bp.optional_last_tokens = a->optional_last_tokens;
+        bp.optional_count       = a->optional_count;
+        bp.output_ids           = a->output_ids;
+        bp.parent_ids           = a->parent_ids;
+        bp.finished             = a->finished;
+        bp.seq_len              = a->seq_len;
+        bp.cum_log_probs        = a->cum_log_probs;
+        bp.cache_indir          = a->cache_indir;
+        bp.ws                   = mem.alloc<char>(beam_workspace_bytes(B, K));
+        bp.state                = mem.state(a->step, s);  // (synchronises: the host vectors above have been copied)
+        launch_beam_search(bp, s);
+        FTCF_HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
+
 // ---------------------------------------------------------------------------------------------------------------
 // the engine
 // ---------------------------------------------------------------------------------------------------------------
@@ -530,20 +784,6 @@ __global__ void k_scale_by_tp(T* buf, size_t n, float tp)
 }
 template __global__ void k_scale_by_tp<f16>(f16*, size_t, float);
 template __global__ void k_scale_by_tp<float>(float*, size_t, float);
-
-template<typename T>
-static std::vector<T> broadcast_arg(const T* p, int n, int B, T dflt, const char* name)
-{
-    std::vector<T> v((size_t)B, dflt);
-    if (n > 0) {
-        FTCF_CHECK_ARG(p != nullptr, std::string(name) + " pointer is NULL");
-        FTCF_CHECK_ARG(n == 1 || n == B, std::string(name) + " must have 1 or batch_size entries");
-        for (int b = 0; b < B; b++) {
-            v[b] = p[n == 1 ? 0 : b];
-        }
-    }
-    return v;
-}
 
 void ftcf_gptneox::begin(const ftcf_forward_args& a)
 {
@@ -640,27 +880,10 @@ void ftcf_gptneox::begin(const ftcf_forward_args& a)
     auto divr  = broadcast_arg<float>(a.beam_search_diversity_rate, a.n_beam_search_diversity_rate, batch, 0.f,
                                       "beam_search_diversity_rate");
     auto lenp  = broadcast_arg<float>(a.len_penalty, a.n_len_penalty, batch, 0.f, "len_penalty");
-    std::vector<int>   k_eff(batch);
-    std::vector<float> p_topk(batch), p_topp(batch);
-    bool               temp_all_one = true, rep_all_default = true, any_min = false;
-    for (int b = 0; b < batch; b++) {
-        int   k = top_k[b];
-        float p = top_p[b];
-        FTCF_CHECK_ARG(k >= 0, "top_k must be >= 0");
-        if (k == 0 && p == 0.0f) {
-            k = 1;
-        }
-        float pk = p;
-        if (k > 0 && pk == 0.0f) {
-            pk = 1.0f;
-        }
-        k_eff[b]  = k > 1024 ? 1024 : k;
-        p_topk[b] = pk < 0.f ? 0.f : (pk > 1.f ? 1.f : pk);
-        p_topp[b] = p < 0.f ? 0.f : (p > 1.f ? 1.f : p);
-        temp_all_one &= (temp[b] == 1.0f);
-        rep_all_default &= (rep[b] == 1.0f);
-        any_min |= (minl[b] > 0);
-    }
+    const SamplingRouting route = route_sampling_args(top_k, top_p, temp, rep, minl, a.n_repetition_penalty > 0);
+    const std::vector<int>&   k_eff  = route.k_eff;
+    const std::vector<float>& p_topk = route.p_topk;
+    const std::vector<float>& p_topp = route.p_topp;
     FTCF_HIP_CHECK(hipMemcpyAsync(d_top_k, k_eff.data(), batch * 4, hipMemcpyHostToDevice, stream));
     FTCF_HIP_CHECK(hipMemcpyAsync(d_p_topk, p_topk.data(), batch * 4, hipMemcpyHostToDevice, stream));
     FTCF_HIP_CHECK(hipMemcpyAsync(d_p_topp, p_topp.data(), batch * 4, hipMemcpyHostToDevice, stream));
@@ -802,21 +1025,14 @@ void ftcf_gptneox::begin(const ftcf_forward_args& a)
     sp.end_id = cfg.end_id;
     sp.input_lengths = in_len;
     sp.top_k = d_top_k;
-    sp.max_top_k = 1;
-    sp.any_top_p = 0;
-    for (int i = 0; i < batch; i++) {
-        sp.max_top_k = std::max(sp.max_top_k, k_eff[i]);
-        sp.any_top_p |= (k_eff[i] == 0);
-    }
     sp.top_p_topk = d_p_topk;
     sp.top_p_topp = d_p_topp;
     sp.temperature = d_temp;
-    sp.repetition_penalty = a.n_repetition_penalty > 0 ? d_rep : nullptr;
-    sp.min_length = any_min ? d_min_length : nullptr;
+    sp.repetition_penalty = d_rep;
+    sp.min_length = d_min_length;
+    route.apply(sp);
     sp.random_seed = d_seed;
     sp.draw_counter = draws;
-    sp.apply_temperature = temp_all_one ? 0 : 1;
-    sp.apply_repetition = (a.n_repetition_penalty > 0 && !rep_all_default) ? 1 : 0;
     sp.stop_words = K > 1 ? nullptr : a.stop_words_list;  // (the beam kernel checks them along the parent chain)
     sp.stop_len = a.stop_words_len;
     sp.optional_last_tokens = a.optional_last_tokens;
@@ -855,7 +1071,7 @@ void ftcf_gptneox::begin(const ftcf_forward_args& a)
         bp.repetition_penalty = a.n_repetition_penalty > 0 ? d_rep : nullptr;  // penalty type None otherwise
         bp.diversity_rate = d_div;
         bp.len_penalty = d_lenpen;
-        bp.min_length = any_min ? d_min_length : nullptr;
+        bp.min_length = route.any_min ? d_min_length : nullptr;
         bp.stop_words = a.stop_words_list;
         bp.stop_len = a.stop_words_len;
         bp.optional_last_tokens = a.optional_last_tokens;

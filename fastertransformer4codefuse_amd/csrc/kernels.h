@@ -415,6 +415,8 @@ struct SamplingParams {
 };
 // does launch_dynamic_decode(p, s, finish) take the one-launch path of an all-greedy batch (k_greedy_decode)?
 bool dynamic_decode_is_fused(const SamplingParams& p, bool finish);
+// which form launch_dynamic_decode(p, s, finish) takes: 0 the general four launches, 1 k_topk_decode, 2 k_greedy_decode
+int  dynamic_decode_form(const SamplingParams& p, bool finish);
 // beam search (beam_width > 1): OnlineBeamSearchLayer semantics, rows bb = batch * K + beam
 constexpr int BEAM_MAX_K = 64;  // online_softmax_beamsearch_kernels.cu:691-695
 struct BeamParams {

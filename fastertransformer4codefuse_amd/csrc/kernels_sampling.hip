@@ -271,9 +271,12 @@ __global__ __launch_bounds__(1024) void k_decode_prep(const SamplingParams p)
 constexpr int STAGE1_MAXE = 60;  // elements per thread of a stage-1 slice (registers): V <= 8 x 256 x 60 = 122880
 constexpr int TOPP_K = 128;  // candidates per slice kept for the rows of the top-p layer (see k_sample)
 
-__device__ __forceinline__ unsigned fkey(const float v)  // v1 > v2 <=> fkey(v1) > fkey(v2) (no NaNs among logits)
+// v1 > v2 <=> fkey(v1) > fkey(v2), v1 == v2 <=> fkey(v1) == fkey(v2) (no NaNs among logits): -0.0 has the key of +0.0 -- the two
+// are ONE value for `better`, the oracle and the reference's comparison, and the index decides between them
+__device__ __forceinline__ unsigned fkey(const float v)
 {
-    const unsigned u = __float_as_uint(v);
+    unsigned u = __float_as_uint(v);
+    u          = (u == 0x80000000u) ? 0u : u;
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 // exclusive prefix sum of one int per thread over the 256-thread block; `tot` = block total.  red: 4 ints of LDS.
@@ -743,6 +746,9 @@ __global__ __launch_bounds__(256) void k_sample(const SamplingParams p, float* c
     if (p.finished[b]) {
         if (threadIdx.x == 0) {
             *out_id = p.end_id;  // sampling_topk_kernels.cu:239-242 ; top-p: arg max of the end mask
+            if (p.top_k[b] == 0) {
+                p.draw_counter[b] += 1;  // (the top-p layer draws before it looks at `finished`: sampling_topp_kernels.cu:910-913)
+            }
         }
         return;
     }
@@ -1900,6 +1906,11 @@ static bool dynamic_decode_is_greedy_fused(const SamplingParams& p, bool finish)
 bool dynamic_decode_is_fused(const SamplingParams& p, bool finish)
 {
     return dynamic_decode_is_topk_fused(p, finish) || dynamic_decode_is_greedy_fused(p, finish);
+}
+
+int dynamic_decode_form(const SamplingParams& p, bool finish)  // (the order launch_dynamic_decode asks in)
+{
+    return dynamic_decode_is_topk_fused(p, finish) ? 1 : (dynamic_decode_is_greedy_fused(p, finish) ? 2 : 0);
 }
 
 void launch_dynamic_decode(const SamplingParams& p, hipStream_t s, bool finish)

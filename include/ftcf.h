@@ -219,6 +219,76 @@ int ftcf_scatter_kv_to_pages(const void* k_cache, const void* v_cache, void* k_p
 int ftcf_gather_pages_to_kv(void* k_cache, void* v_cache, const void* k_pool, const void* v_pool, const int* pages, int L, int nh,
                             int dh, int s_max, int T, int page_tokens, size_t pool_layer_elems, size_t dst_layer_elems,
                             void* stream);
+/* ONE step of the dynamic-decode layer (DynamicDecodeLayer.cc:192-497 with beam_width 1: optional-token mask, temperature,
+ * repetition penalty, min-length mask, end mask, top-k / top-p sampling, stop words, length criterion) on the caller's logits and
+ * state -- the launch sequence the engine and the continuous batcher run per token, with the same routing of the runtime
+ * arguments.  Device buffers of the caller: logits [B, V] fp32 (modified in place), output_ids time-major [rows, B] int32 with
+ * rows >= max(total_len, step + 1): the token goes to row `step` (row row_len[b] + 1 with row_len), rows [0, step) are the
+ * history the repetition penalty and the stop words read; finished [B] uint8, seq_len [B] int32, cum_log_probs [B] fp32 or
+ * NULL, output_log_probs time-major [total_len - max_input_len, B] fp32 or NULL (the value this step adds to cum_log_probs, at
+ * row step - max_input_len; row 0 with row_len; it switches the soft-max statistics on as return_cum_log_probs does), draw_counter [B] uint64, pad_count [B] int32 or NULL, input_lengths [B] int32, stop_words [B, 2, stop_len]
+ * or NULL, optional_last_tokens [B, optional_count] (-1 padded) or NULL, row_len [B] int32 or NULL (every row at its own step).
+ * Runtime arguments: host arrays of 1 or B entries as in ftcf_forward_args, n == 0 "not given".  finish != 0: the step's
+ * bookkeeping (stop words, length criterion, padding count) follows, and *all_finished / *next_step (host, may be NULL) receive
+ * the state it leaves; finish == 0 is the batcher's form (no bookkeeping: *all_finished 0, *next_step = step).  *form (host,
+ * may be NULL): 0 the general four launches, 1 the one-launch top-k step, 2 the one-launch greedy step.  Synchronises the
+ * stream.  V > 122880 on the general path and a repetition penalty with total_len > 7680 are FTCF_ERR_INVALID_ARG. */
+typedef struct {
+    float*          logits;
+    int*            output_ids;
+    uint8_t*        finished;
+    int*            seq_len;
+    float*          cum_log_probs;
+    float*          output_log_probs;
+    uint64_t*       draw_counter;
+    int*            pad_count;
+    const int*      input_lengths;
+    const int*      stop_words;
+    const int*      optional_last_tokens;
+    const int*      row_len;
+    const int*      top_k;
+    const float*    top_p;
+    const float*    temperature;
+    const float*    repetition_penalty;
+    const int*      min_length;
+    const uint64_t* random_seed;
+    int*            all_finished;
+    int*            next_step;
+    int*            form;
+    int n_top_k, n_top_p, n_temperature, n_repetition_penalty, n_min_length, n_random_seed;
+    int stop_len, optional_count;
+    int B, V, step, max_input_len, total_len, end_id, return_cum_log_probs, finish;
+} ftcf_dynamic_decode_args;
+int ftcf_dynamic_decode_step(const ftcf_dynamic_decode_args* args, void* stream);
+/* ONE step of the beam-search layer (OnlineBeamSearchLayer without beam hypotheses: penalties, per-row top K of log-softmax +
+ * cum_log_probs, the K best of a batch entry's K * K candidates, parents, lengths, cache indirection, stop words along the
+ * parent chain; not the length criterion).  Rows bb = batch * K + beam.  Device buffers of the caller: logits [B * K, V] fp32
+ * (modified in place), output_ids / parent_ids time-major [total_len, B * K] int32, finished [B * K] uint8, seq_len [B * K]
+ * int32, cum_log_probs [B * K] fp32, cache_indir [2, B * K, s_max] int32 (plane (step - max_input_len) % 2 is read, the other
+ * one written), input_lengths [B * K] int32 (tiled), stop_words [B, 2, stop_len] or NULL, optional_last_tokens [B,
+ * optional_count] or NULL.  Runtime arguments: host arrays of 1 or B entries, n == 0 "not given".  2 <= K <= 64, V >= K,
+ * max(1, max_input_len) <= step < total_len.  Synchronises the stream. */
+typedef struct {
+    float*       logits;
+    int*         output_ids;
+    int*         parent_ids;
+    uint8_t*     finished;
+    int*         seq_len;
+    float*       cum_log_probs;
+    int*         cache_indir;
+    const int*   input_lengths;
+    const int*   stop_words;
+    const int*   optional_last_tokens;
+    const float* temperature;
+    const float* repetition_penalty;
+    const float* beam_search_diversity_rate;
+    const float* len_penalty;
+    const int*   min_length;
+    int n_temperature, n_repetition_penalty, n_beam_search_diversity_rate, n_len_penalty, n_min_length;
+    int stop_len, optional_count;
+    int B, K, V, step, max_input_len, total_len, s_max, end_id;
+} ftcf_beam_search_args;
+int ftcf_beam_search_step(const ftcf_beam_search_args* args, void* stream);
 
 /* ================================================================================================
  * libth_gptneox counterpart -- the engine behind GptNeoXOp

@@ -920,6 +920,9 @@ void orc_dynamic_decode(float* logits, int B, int V, int step, int max_input_len
                     if (!sp->return_cum_log_probs) {
                         u = expf(u - smax); /* :271-275 */
                     }
+                    else if (top[i].i < 0) {
+                        u = 0.f; /* a place beyond the vocabulary (k > V) holds no probability */
+                    }
                     val2[i] = u;
                     ssum += u;
                 }

@@ -44,6 +44,7 @@ def test_engine_form_entry_points_fail_loudly_without_a_gpu():
     queries are host arithmetic and answer anyway"""
     L = capi.lib()
     prob, ln, res = capi.SmallmProblem(), capi.LnGemvArgs(), capi.ResidualGemvArgs()
+    dec, beam = capi.DynamicDecodeArgs(), capi.BeamSearchArgs()
     seq = C.c_uint(0)
     calls = [
         lambda: L.ftcf_gemm_smallm_group(C.byref(prob), 1, 5, 1, None, C.c_size_t(0), C.c_size_t(0), None, C.byref(seq), None),
@@ -52,6 +53,8 @@ def test_engine_form_entry_points_fail_loudly_without_a_gpu():
         lambda: L.ftcf_lm_head_layernorm(None, None, None, None, C.c_float(1e-5), None, None, 1, 16, 64, 16, None),
         lambda: L.ftcf_ln_gemv(C.byref(ln), 1, 1, 0, None),
         lambda: L.ftcf_residual_gemv(C.byref(res), 1, 1, 2, None, C.c_size_t(0), None, 0, 0, None),
+        lambda: L.ftcf_dynamic_decode_step(C.byref(dec), None),
+        lambda: L.ftcf_beam_search_step(C.byref(beam), None),
     ]
     for call in calls:
         assert call() == -5 and b"no HIP device" in L.ftcf_last_error()
