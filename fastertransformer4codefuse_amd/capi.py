@@ -106,6 +106,7 @@ class ForwardStats(C.Structure):
 # every symbol include/ftcf.h declares (tests/test_capi_host.py checks the list against the header and the library)
 EXPORTED = [
     "ftcf_last_error", "ftcf_version", "ftcf_device_count", "ftcf_symmetric_quantize_int8",
+    "ftcf_symmetric_quantize_int8_device", "ftcf_symmetric_quantize_int8_device_workspace",
     "ftcf_int8_rowmajor_to_tiled", "ftcf_int8_tiled_to_rowmajor", "ftcf_int8_cuda_sm80_to_rowmajor",
     "ftcf_int8_rowmajor_to_cuda_sm80", "ftcf_fp16_rowmajor_to_tiled",
     "ftcf_fpA_intB_gemm", "ftcf_fp16_gemm", "ftcf_lm_head", "ftcf_lm_head_layernorm", "ftcf_lm_head_log_probs",
@@ -137,7 +138,8 @@ def lib():
         _lib.ftcf_masked_multihead_attention_workspace.restype = C.c_size_t
         if hasattr(_lib, "ftcf_verify_attention_workspace"):  # (FTCF_LIB_NAME may name an older build: the call itself then fails)
             _lib.ftcf_verify_attention_workspace.restype = C.c_size_t
-        for name in ("ftcf_gemm_smallm_workspace_bytes", "ftcf_gemm_smallm_ticket_bytes", "ftcf_residual_gemv_workspace_bytes"):
+        for name in ("ftcf_gemm_smallm_workspace_bytes", "ftcf_gemm_smallm_ticket_bytes", "ftcf_residual_gemv_workspace_bytes",
+                     "ftcf_symmetric_quantize_int8_device_workspace"):
             if hasattr(_lib, name):
                 getattr(_lib, name).restype = C.c_size_t
     return _lib

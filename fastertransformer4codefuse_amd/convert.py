@@ -5,7 +5,7 @@ by either side loads in the other (the int8 `.q.bin` files hold this engine's gf
 exactly like the reference's CUDA layout -- see DESIGN.md).
 
     python -m fastertransformer4codefuse_amd.convert hf2ft -i <hf_dir> -o <out_dir> -i_g 2 -weight_data_type fp16 -m_n codefuse
-    python -m fastertransformer4codefuse_amd.convert quant --in_dir <out_dir>/2-gpu --out_dir <q_dir> --tensor_para_size 2
+    python -m fastertransformer4codefuse_amd.convert quant --in_dir <out_dir>/2-gpu --out_dir <q_dir> --tensor_para_size 2 [--on-device]
 """
 import argparse
 import configparser
@@ -105,11 +105,14 @@ def convert_model(model, saved_dir, factor, weight_data_type="fp32", model_name=
             (a + b).astype(np_dt).tofile(f"{saved_dir}/model.layers.{l}.mlp.attention.bias.sum.bin")
 
 
-def quant_and_save(in_dir, out_dir, tensor_para_size, inference_data_type="fp16"):
+def quant_and_save(in_dir, out_dir, tensor_para_size, inference_data_type="fp16", on_device=False):
     """Copies a checkpoint and replaces the four GEMM kernels of every layer/rank by `.q.bin` (int8, engine tile
-    layout) + `.s.bin` (scales in the checkpoint's weight dtype)."""
+    layout) + `.s.bin` (scales in the checkpoint's weight dtype).  on_device: quantise on the GPU (the same bytes)."""
     import torch
-    from .gptneox_op import symmetric_quantize_last_axis_of_batched_matrix_int8 as quantize
+    if on_device:
+        from .gptneox_op import symmetric_quantize_last_axis_of_batched_matrix_int8_device as quantize
+    else:
+        from .gptneox_op import symmetric_quantize_last_axis_of_batched_matrix_int8 as quantize
     if os.path.exists(out_dir):
         shutil.rmtree(out_dir)
     shutil.copytree(in_dir, out_dir)
@@ -129,7 +132,7 @@ def quant_and_save(in_dir, out_dir, tensor_para_size, inference_data_type="fp16"
             for li in range(L):
                 base = os.path.join(out_dir, f"model.layers.{li}.{fn}.{rk}")
                 w = torch.from_numpy(np.fromfile(base + ".bin", dtype=np_dt)).to(t_dt).reshape(shape).contiguous()
-                q, s = quantize(w)
+                q, s = (t.cpu() for t in quantize(w))
                 q.numpy().astype(np.int8).tofile(base + ".q.bin")
                 s.numpy().astype(np_dt).tofile(base + ".s.bin")
                 os.remove(base + ".bin")
@@ -182,6 +185,7 @@ def main():
     q.add_argument("--out_dir", required=True)
     q.add_argument("--tensor_para_size", type=int, required=True)
     q.add_argument("--inference_data_type", "--data_type", choices=["fp32", "fp16"], default="fp16")
+    q.add_argument("--on-device", action="store_true", help="quantise on the GPU (the same bytes as the host quantiser)")
     i = sub.add_parser("import-cuda-qbin", help="re-lay .q.bin files written by a CUDA build (SM75..SM89 layout)")
     i.add_argument("--in_dir", required=True)
     i.add_argument("--out_dir", required=True)
@@ -197,7 +201,7 @@ def main():
         convert_model(GPTNeoXForCausalLM.from_pretrained(a.in_file), out, a.infer_gpu_num, a.weight_data_type,
                       a.model_name)
     else:
-        quant_and_save(a.in_dir, a.out_dir, a.tensor_para_size, a.inference_data_type)
+        quant_and_save(a.in_dir, a.out_dir, a.tensor_para_size, a.inference_data_type, on_device=a.on_device)
 
 
 if __name__ == "__main__":

@@ -37,6 +37,24 @@ extern "C" int ftcf_symmetric_quantize_int8(const void* weight, ftcf_dtype dtype
 {
     return guarded([&] { host_symmetric_quantize_int8(weight, (int)dtype, E, K, N, out_q, out_scale); });
 }
+extern "C" size_t ftcf_symmetric_quantize_int8_device_workspace(size_t E, size_t N)
+{
+    return symmetric_quantize_int8_workspace_bytes(E, N);
+}
+extern "C" int ftcf_symmetric_quantize_int8_device(const void* weight, ftcf_dtype dtype, size_t E, size_t K, size_t N,
+                                                   int8_t* out_q, void* out_scale, void* workspace, size_t workspace_bytes,
+                                                   void* stream)
+{
+    return guarded([&] {
+        require_device();
+        check_symmetric_quantize_args(weight, (int)dtype, E, K, N, out_q, out_scale);  // (the host function's rule)
+        FTCF_CHECK_ARG(workspace != nullptr, "NULL workspace");
+        FTCF_CHECK_ARG(workspace_bytes >= symmetric_quantize_int8_workspace_bytes(E, N), "workspace too small");
+        FTCF_CHECK_ARG(((uintptr_t)weight | (uintptr_t)out_q | (uintptr_t)out_scale | (uintptr_t)workspace) % 16 == 0,
+                       "device quantiser pointers must be 16-byte aligned");
+        launch_symmetric_quantize_int8(weight, (int)dtype, E, K, N, out_q, out_scale, workspace, (hipStream_t)stream);
+    });
+}
 extern "C" int ftcf_int8_rowmajor_to_tiled(const int8_t* q, size_t K, size_t N, int8_t* out)
 {
     return guarded([&] { host_int8_rowmajor_to_tiled(q, K, N, out); });

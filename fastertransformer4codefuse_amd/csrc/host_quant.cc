@@ -125,14 +125,20 @@ static void quantize_one(const T* w, size_t K, size_t N, int8_t* q_rowmajor, T* 
     }
 }
 
-void host_symmetric_quantize_int8(const void* weight, int dtype, size_t E, size_t K, size_t N, int8_t* out_q,
-                                  void* out_scale)
+void check_symmetric_quantize_args(const void* weight, int dtype, size_t E, size_t K, size_t N, const int8_t* out_q,
+                                   const void* out_scale)
 {
     FTCF_CHECK_ARG(dtype >= 0 && dtype <= 2, "weight dtype must be fp32 (0), fp16 (1) or bf16 (2)");
     FTCF_CHECK_ARG(weight && out_q && out_scale, "NULL tensor");
     FTCF_CHECK_ARG(E >= 1 && K >= 1 && N >= 1, "empty weight");
     FTCF_CHECK_ARG(K % TILE_K_I8 == 0 && N % TILE_N == 0,
                    "weight-only int8 needs K % 64 == 0 (as the reference, fpA_intB_gemm_template.h:159-163) and N % 16 == 0");
+}
+
+void host_symmetric_quantize_int8(const void* weight, int dtype, size_t E, size_t K, size_t N, int8_t* out_q,
+                                  void* out_scale)
+{
+    check_symmetric_quantize_args(weight, dtype, E, K, N, out_q, out_scale);
     std::vector<int8_t> tmp(K * N);
     for (size_t e = 0; e < E; e++) {
         if (dtype == 1) {

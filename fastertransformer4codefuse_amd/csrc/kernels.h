@@ -127,6 +127,14 @@ void launch_gather_last_token(f16* out, const f16* hidden, const int* input_leng
 void launch_tile_prompt_ids(int* output_ids, const int* ids, int B, int K, int S, hipStream_t s);
 void launch_fp16_rowmajor_to_tiled(const f16* w, size_t K, size_t N, f16* out, hipStream_t s);
 
+// ---- weight-only int8 quantiser on the device : kernels_quant.hip ----
+// host_symmetric_quantize_int8 (host_quant.h) bit for bit: w [E, K, N] row major (dtype 0 fp32, 1 fp16, 2 bf16 raw bits) ->
+// out_q [E, K, N] bytes in the int8 tile layout + out_scale [E, N] in the weight dtype.  K % 64 == 0, N % 16 == 0, every pointer
+// 16-byte aligned; workspace: symmetric_quantize_int8_workspace_bytes(E, N) = E * N * 4 bytes (the fp32 column maxima), any contents.
+size_t symmetric_quantize_int8_workspace_bytes(size_t E, size_t N);
+void   launch_symmetric_quantize_int8(const void* w, int dtype, size_t E, size_t K, size_t N, int8_t* out_q, void* out_scale,
+                                      void* workspace, hipStream_t s);
+
 // ---- attention : kernels_attn.hip ----
 struct MmhaParams {
     const f16* qkv;       // [B, 3*Hl]

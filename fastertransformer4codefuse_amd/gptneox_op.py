@@ -314,3 +314,39 @@ def symmetric_quantize_last_axis_of_batched_matrix_int8(weight):
         {torch.float16: capi.FP16, torch.bfloat16: capi.BF16, torch.float32: capi.FP32}[weight.dtype], C.c_size_t(E),
         C.c_size_t(K), C.c_size_t(N), C.c_void_p(q.data_ptr()), C.c_void_p(scales.data_ptr())))
     return [q, scales]
+
+
+def symmetric_quantize_last_axis_of_batched_matrix_int8_device(weight):
+    """The same quantiser on the GPU (include/ftcf.h ftcf_symmetric_quantize_int8_device): bit for bit the result of
+    `symmetric_quantize_last_axis_of_batched_matrix_int8` for the same values, as device tensors.
+
+    weight: contiguous [K,N] or [E,K,N], fp32 / fp16 / bf16, on the device or on the CPU (then it is uploaded to the current
+    device).  Runs on torch's current stream of the weight's device.  Returns [int8 tensor of the same shape in the engine's
+    private gfx950 tile layout, scales [N] (or [E,N]) in the weight dtype], both on the device."""
+    if not weight.is_contiguous():
+        raise RuntimeError("weight must be contiguous")
+    if weight.numel() == 0:
+        raise RuntimeError("weight should not be empty tensor")
+    if weight.dim() not in (2, 3):
+        raise RuntimeError("Invalid dim. The dim of weight should be 2 or 3")
+    if weight.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise RuntimeError("Invalid datatype. Weight must be FP16 or BF16")
+    capi.require_gpu()
+    if not weight.is_cuda:
+        weight = weight.cuda()
+    if weight.data_ptr() % 16:
+        weight = weight.clone()  # (a view into a larger storage: the kernels load 16 bytes at a time)
+    E = 1 if weight.dim() == 2 else int(weight.size(0))
+    K, N = int(weight.size(-2)), int(weight.size(-1))
+    with torch.cuda.device(weight.device):
+        q = torch.empty(weight.shape, dtype=torch.int8, device=weight.device)
+        scales = torch.empty((N,) if weight.dim() == 2 else (E, N), dtype=weight.dtype, device=weight.device)
+        ws_bytes = int(capi.lib().ftcf_symmetric_quantize_int8_device_workspace(C.c_size_t(E), C.c_size_t(N)))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=weight.device)
+        # (ws is freed to torch's caching allocator on return: a later allocation on the same stream is ordered after the kernels)
+        capi.check(capi.lib().ftcf_symmetric_quantize_int8_device(
+            C.c_void_p(weight.data_ptr()),
+            {torch.float16: capi.FP16, torch.bfloat16: capi.BF16, torch.float32: capi.FP32}[weight.dtype], C.c_size_t(E),
+            C.c_size_t(K), C.c_size_t(N), C.c_void_p(q.data_ptr()), C.c_void_p(scales.data_ptr()), C.c_void_p(ws.data_ptr()),
+            C.c_size_t(ws_bytes), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return [q, scales]

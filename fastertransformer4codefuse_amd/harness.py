@@ -185,14 +185,21 @@ class GptNeoXWeights:
 
     def __init__(self, head_num, size_per_head, layer_num, vocab_size, max_seq_len, tensor_para_size,
                  pipeline_para_size, use_gptj_residual, int8_mode=0, inference_data_type="fp16",
-                 weights_data_type=np.float32, enable_int8_weights=False, use_pybind11=False, inter_size=None):
+                 weights_data_type=np.float32, enable_int8_weights=False, use_pybind11=False, inter_size=None,
+                 quantize_on_device=False):
         assert head_num % tensor_para_size == 0
         assert int8_mode in (0, 1), "Invalid int8 mode for GPT. Must be 0 or 1"
+        # quantize_on_device (not in the reference): load() uploads each GEMM kernel in turn, quantises it with the GPU form of the
+        # quantiser (the same bits) and keeps int8_w / scale on the current device; one fp matrix is on the device at a time
+        self.quantize_on_device = bool(quantize_on_device)
         if int8_mode == 1:
             assert str_type_map[inference_data_type] == torch.float16, \
                 "Weight only quant only supported for infer type fp16 or bf16."
-            from .gptneox_op import symmetric_quantize_last_axis_of_batched_matrix_int8
-            self.weight_transpose_calibrate_quantize = symmetric_quantize_last_axis_of_batched_matrix_int8
+            from .gptneox_op import (symmetric_quantize_last_axis_of_batched_matrix_int8,
+                                     symmetric_quantize_last_axis_of_batched_matrix_int8_device)
+            self.weight_transpose_calibrate_quantize = (symmetric_quantize_last_axis_of_batched_matrix_int8_device
+                                                        if self.quantize_on_device
+                                                        else symmetric_quantize_last_axis_of_batched_matrix_int8)
         if isinstance(weights_data_type, str):
             if weights_data_type not in _NP_TYPES:
                 raise ValueError(f"Don't know how to interpret weights_data_type: {weights_data_type}")
@@ -310,7 +317,7 @@ class GptNeoX(torch.nn.Module):
     def __init__(self, head_num, size_per_head, vocab_size, rotary_embedding_dim, start_id, end_id, layer_num,
                  max_seq_len, tensor_para_size, pipeline_para_size, use_gptj_residual, lib_path=None, int8_mode=0,
                  inference_data_type="fp16", weights_data_type=np.float32, enable_int8_weights=False,
-                 use_pybind11=True, inter_size=None):
+                 use_pybind11=True, inter_size=None, quantize_on_device=False):
         super().__init__()
         import torch.distributed as dist
         self.head_num, self.size_per_head = head_num, size_per_head
@@ -331,7 +338,7 @@ class GptNeoX(torch.nn.Module):
                                       pipeline_para_size, use_gptj_residual, int8_mode=int8_mode,
                                       weights_data_type=weights_data_type, inference_data_type=inference_data_type,
                                       use_pybind11=True, enable_int8_weights=enable_int8_weights,
-                                      inter_size=self.inter_size)
+                                      inter_size=self.inter_size, quantize_on_device=quantize_on_device)
         if not dist.is_initialized() and tensor_para_size * pipeline_para_size > 1:
             dist.init_process_group(backend="nccl")
         self.rank = dist.get_rank() if dist.is_initialized() else 0

@@ -53,6 +53,17 @@ int ftcf_device_count(void);
  * out_scale: host [E, N] in the weight dtype.  Requires K % 64 == 0 and N % 16 == 0. */
 int ftcf_symmetric_quantize_int8(const void* weight, ftcf_dtype dtype, size_t E, size_t K, size_t N, int8_t* out_q,
                                  void* out_scale);
+/* Device form of ftcf_symmetric_quantize_int8: weight [E, K, N] row major ON THE DEVICE, out_q [E, K, N] bytes in the
+ * engine tile layout and out_scale [E, N] in the weight dtype on the device, bit for bit what the host function returns
+ * for the same values.  Asynchronous on `stream`; out-of-place (weight is not modified); workspace:
+ * ftcf_symmetric_quantize_int8_device_workspace(E, N) = E * N * 4 bytes (the fp32 column maxima), no initial contents
+ * required.  The four pointers are 16-byte aligned.  Covers every input whose column maximum / 128 is a normal fp32 number
+ * or zero (fp16 subnormal weights and fp16 subnormal scales included; fp32 weights below about 2^-119 are not).
+ * The workspace query is host arithmetic and answers without a device. */
+int    ftcf_symmetric_quantize_int8_device(const void* weight, ftcf_dtype dtype, size_t E, size_t K, size_t N,
+                                           int8_t* out_q, void* out_scale, void* workspace, size_t workspace_bytes,
+                                           void* stream);
+size_t ftcf_symmetric_quantize_int8_device_workspace(size_t E, size_t N);
 /* row-major int8 [K,N] (the reference's "unprocessed" tensor) <-> engine tile layout (host) */
 int ftcf_int8_rowmajor_to_tiled(const int8_t* q_rowmajor, size_t K, size_t N, int8_t* q_tiled);
 int ftcf_int8_tiled_to_rowmajor(const int8_t* q_tiled, size_t K, size_t N, int8_t* q_rowmajor);
