@@ -134,7 +134,7 @@ struct ftcf_batcher {
     // Beam search inside the batcher (round 4; the reference's serving layer runs beam requests through the same decoder:
     // triton_backend/gptneox/GptNeoXTritonModelInstance.cc).  A request of beam width K lives in K CONSECUTIVE slots -- its
     // beams ride in the same batched GEMMs as everybody else's rows -- and is scored by the engine's own beam kernels
-    // (launch_beam_search with batch 1: OnlineBeamSearchLayer semantics, kernels_sampling.hip) on per-group state.  The cache
+    // (launch_beam_search with batch 1: OnlineBeamSearchLayer semantics, kernels_beam.hip) on per-group state.  The cache
     // indirection of the reference (BaseBeamSearchLayer.cu:30-62: which beam's cache row holds position t) is replaced by what a
     // paged cache is for: after every step beam k's page list becomes a copy of its parent's (pages are reference counted),
     // and only the page the next token will be appended to is copied when it is shared (copy-on-write, all layers, one launch

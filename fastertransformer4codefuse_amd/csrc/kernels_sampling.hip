@@ -12,6 +12,7 @@
 #include "kernels.h"
 #include "attn_device.hip.h"  // rotary_coef (the next token's prologue inside k_greedy_decode)
 #include "lm_head_device.hip.h"  // k_lm_head_greedy
+#include "sampling_device.hip.h"
 
 #include <mutex>
 
@@ -36,48 +37,6 @@ __device__ __forceinline__ float ftcf_uniform(uint64_t seed, uint64_t row, uint6
     const uint64_t z = splitmix64(seed ^ splitmix64(row * 0x632be59bd9b4e019ULL + draw));
     const uint32_t r = (uint32_t)(z >> 40);
     return (float)(r + 1u) * (1.0f / 16777216.0f);
-}
-
-struct VI {
-    float v;
-    int   i;
-};
-__device__ __forceinline__ bool better(float v, int i, float bv, int bi)
-{
-    return (v > bv) || (v == bv && i < bi);
-}
-__device__ __forceinline__ VI wave_best(VI x)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const float ov = __shfl_xor(x.v, o, 64);
-        const int   oi = __shfl_xor(x.i, o, 64);
-        if (better(ov, oi, x.v, x.i)) {
-            x.v = ov;
-            x.i = oi;
-        }
-    }
-    return x;
-}
-// block arg-best; result valid in all threads.  red: 2*nw words of LDS.
-__device__ __forceinline__ VI block_best(VI x, float* redv, int* redi)
-{
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    x = wave_best(x);
-    if (lane == 0) {
-        redv[wid] = x.v;
-        redi[wid] = x.i;
-    }
-    __syncthreads();
-    VI r{redv[0], redi[0]};
-    for (int w = 1; w < nw; w++) {
-        if (better(redv[w], redi[w], r.v, r.i)) {
-            r.v = redv[w];
-            r.i = redi[w];
-        }
-    }
-    __syncthreads();
-    return r;
 }
 
 // the log-probability a step adds to cum_log_probs, kept per token (GptNeoX.cc:967-987 output_log_probs): row (step -
@@ -107,25 +66,8 @@ __global__ __launch_bounds__(1024) void k_decode_prep(const SamplingParams p)
 
     // K15 select_optional_last_tokens: first generated step only (DynamicDecodeLayer.cc:250-267)
     if (p.optional_last_tokens && step == p.max_input_len) {
-        uint32_t* bits = reinterpret_cast<uint32_t*>(smem);
-        const int words = (V + 31) / 32;
-        for (int i = tid; i < words; i += nt) {
-            bits[i] = 0u;
-        }
-        __syncthreads();
-        for (int j = tid; j < p.optional_count; j += nt) {
-            const int t = p.optional_last_tokens[(size_t)b * p.optional_count + j];
-            if (t >= 0 && t < V) {
-                atomicOr(&bits[t >> 5], 1u << (t & 31));
-            }
-        }
-        __syncthreads();
-        for (int i = tid; i < V; i += nt) {
-            if (!((bits[i >> 5] >> (i & 31)) & 1u)) {
-                l[i] = -INFINITY;
-            }
-        }
-        __syncthreads();
+        mask_optional_tokens(l, V, p.optional_last_tokens + (size_t)b * p.optional_count, p.optional_count,
+                             reinterpret_cast<uint32_t*>(smem));
     }
     if (p.apply_temperature) {  // sampling_penalty_kernels.cu:117-147
         const float   inv = 1.0f / (p.temperature[b] + 1e-6f);
@@ -208,15 +150,7 @@ __global__ __launch_bounds__(1024) void k_decode_prep(const SamplingParams p)
                 mx = fmaxf(mx, t[u]);
             }
         }
-        mx = wave_max(mx);
-        if ((tid & 63) == 0) {
-            red[tid >> 6] = mx;
-        }
-        __syncthreads();
-        mx = red[0];
-        for (int w = 1; w < (nt >> 6); w++) {
-            mx = fmaxf(mx, red[w]);
-        }
+        mx = block_max(mx, red, nt >> 6);
         __syncthreads();
         float sum = 0.f;
         for (int i0 = tid; i0 < V; i0 += nt * UNR) {
@@ -233,15 +167,7 @@ __global__ __launch_bounds__(1024) void k_decode_prep(const SamplingParams p)
                 }
             }
         }
-        sum = wave_sum(sum);
-        if ((tid & 63) == 0) {
-            red[tid >> 6] = sum;
-        }
-        __syncthreads();
-        float tot = 0.f;
-        for (int w = 0; w < (nt >> 6); w++) {
-            tot += red[w];
-        }
+        const float tot = block_sum_ordered(sum, red, nt >> 6);
         const float den = tot + 1e-6f;
         for (int i0 = tid; i0 < V; i0 += nt * UNR) {
             float t[UNR];
@@ -440,6 +366,61 @@ __device__ __forceinline__ void slice_select(const float (&vals)[MAXE], const in
     }
 }
 
+// The load pass of a slice of n logits at `l`: the block's threads keep element threadIdx.x + 256 j in vals[j] (j < ne) -- in REGISTERS
+// from here on (all loads in flight at once; the arg max, the soft-max statistics, the four select passes and the emission read
+// them there -- an earlier form staged the slice in LDS and every pass serialised on its LDS read -> atomic dependency).
+// end_local >= 0: that element reads as -FLT_MAX (min_length, sampling_penalty_kernels.cu:485-520: end_id cannot be chosen yet).
+// Returns the thread's arg-best (local index) and, in lmax, the maximum of its elements.
+template<int MAXE>
+__device__ __forceinline__ VI slice_load(float (&vals)[MAXE], const float* l, const int ne, const int end_local, float& lmax)
+{
+#pragma unroll
+    for (int j = 0; j < MAXE; j++) {
+        vals[j] = (j < ne) ? l[threadIdx.x + 256 * j] : -INFINITY;
+    }
+    VI best{-INFINITY, 0x7fffffff};
+    lmax = -FLT_MAX;
+#pragma unroll
+    for (int j = 0; j < MAXE; j++) {
+        if (j < ne) {
+            const int i = threadIdx.x + 256 * j;
+            if (i == end_local) {
+                vals[j] = -FLT_MAX;
+            }
+            const float v = vals[j];
+            lmax          = fmaxf(lmax, v);
+            if (best.i == 0x7fffffff || better(v, i, best.v, best.i)) {
+                best.v = v;
+                best.i = i;
+            }
+        }
+    }
+    return best;
+}
+// soft-max statistics of the slice (addBiasSoftMax, sampling_topp_kernels.cu:1296-1345, slice by slice): m = its maximum, the
+// return value = sum of exp(v - m), both in all threads.  redv: 4 floats of LDS, free again on return.
+template<int MAXE>
+__device__ __forceinline__ float slice_stats(const float (&vals)[MAXE], const int ne, const float lmax, float* redv, float& m)
+{
+    m = block_max(lmax, redv, 4);
+    __syncthreads();
+    float se = 0.f;
+#pragma unroll
+    for (int j = 0; j < MAXE; j++) {
+        if (j < ne) {
+            se += __expf(vals[j] - m);
+        }
+    }
+    se = wave_sum(se);
+    if ((threadIdx.x & 63) == 0) {
+        redv[threadIdx.x >> 6] = se;
+    }
+    __syncthreads();
+    const float sum = (redv[0] + redv[1]) + (redv[2] + redv[3]);
+    __syncthreads();
+    return sum;
+}
+
 __global__ __launch_bounds__(256) void k_topk_stage1(const SamplingParams p, float* cand_v, int* cand_i, int slice)
 {
     if (p.state->all_finished) {
@@ -465,56 +446,18 @@ __global__ __launch_bounds__(256) void k_topk_stage1(const SamplingParams p, flo
     const float* l  = p.logits + (size_t)b * V + i0;
     float*       ov = cand_v + ((size_t)b * TOPK_BLOCKS + blk) * TOPK_MAX;
     int*         oi = cand_i + ((size_t)b * TOPK_BLOCKS + blk) * TOPK_MAX;
-    // the thread's elements i = tid + 256 j live in REGISTERS from here on (all loads in flight at once; the arg max, the
-    // soft-max statistics, the four select passes and the emission read them there -- an earlier form staged the slice in LDS
-    // and every pass serialised on its LDS read -> atomic dependency)
-    float     vals[STAGE1_MAXE];
-    const int ne = n > (int)threadIdx.x ? (n - (int)threadIdx.x + 255) / 256 : 0;
-#pragma unroll
-    for (int j = 0; j < STAGE1_MAXE; j++) {
-        vals[j] = (j < ne) ? l[threadIdx.x + 256 * j] : -INFINITY;
-    }
-    VI    best{-INFINITY, 0x7fffffff};
-    float lmax = -FLT_MAX;
-#pragma unroll
-    for (int j = 0; j < STAGE1_MAXE; j++) {
-        if (j < ne) {
-            const float v = vals[j];
-            const int   i = threadIdx.x + 256 * j;
-            lmax          = fmaxf(lmax, v);
-            if (best.i == 0x7fffffff || better(v, i, best.v, best.i)) {
-                best.v = v;
-                best.i = i;
-            }
-        }
-    }
+    float     vals[STAGE1_MAXE], lmax;
+    const int ne   = n > (int)threadIdx.x ? (n - (int)threadIdx.x + 255) / 256 : 0;
+    const VI  best = slice_load(vals, l, ne, -1, lmax);
     __syncthreads();
-    if (p.return_cum_log_probs && !topp) {  // softmax statistics of the slice: {max, sum of exp(v - max)}
-        lmax = wave_max(lmax);
-        if ((threadIdx.x & 63) == 0) {
-            redv[threadIdx.x >> 6] = lmax;
-        }
-        __syncthreads();
-        const float m = fmaxf(fmaxf(redv[0], redv[1]), fmaxf(redv[2], redv[3]));
-        __syncthreads();
-        float se = 0.f;
-#pragma unroll
-        for (int j = 0; j < STAGE1_MAXE; j++) {
-            if (j < ne) {
-                se += __expf(vals[j] - m);
-            }
-        }
-        se = wave_sum(se);
-        if ((threadIdx.x & 63) == 0) {
-            redv[threadIdx.x >> 6] = se;
-        }
-        __syncthreads();
+    if (p.return_cum_log_probs && !topp) {  // {max, sum of exp(v - max)} of the slice: k_sample builds the row's soft-max from them
+        float       m;
+        const float sum = slice_stats(vals, ne, lmax, redv, m);
         if (threadIdx.x == 0) {
             float* st = reinterpret_cast<float*>(cand_i + (size_t)p.B * TOPK_BLOCKS * TOPK_MAX) + ((size_t)b * TOPK_BLOCKS + blk) * 2;
             st[0]     = n > 0 ? m : -FLT_MAX;
-            st[1]     = n > 0 ? ((redv[0] + redv[1]) + (redv[2] + redv[3])) : 0.f;
+            st[1]     = n > 0 ? sum : 0.f;
         }
-        __syncthreads();
     }
     const int ke = k < n ? k : n;  // candidates this slice can supply
     for (int i = ke + threadIdx.x; i < k; i += 256) {
@@ -729,6 +672,110 @@ __device__ __forceinline__ void union_topk(float* sv, int* si, const int n2, con
     __syncthreads();
 }
 
+// ---- a row's step, by the one thread that owns the row (s_ids: the tokens of rows 0..7 in LDS where the kernel keeps them) ----
+// a finished row repeats its end token (sampling_topk_kernels.cu:239-242; top-p: the arg max of the end mask)
+__device__ __forceinline__ void finished_row_step(const SamplingParams& p, int* out_id, const int row, int* s_ids)
+{
+    *out_id = p.end_id;
+    if (s_ids && row < 8) {
+        s_ids[row] = p.end_id;
+    }
+}
+// Commits a row's pick `id` of probability `prob` (sampling_topk_kernels.cu:296-308, sampling_topp_kernels.cu:974-1000): the token,
+// cum_log_probs and the step's log-probability, sequence length, finished.  cum / slen: the row's cum_log_probs / seq_len before.
+__device__ __forceinline__ void commit_pick(const SamplingParams& p, const int step, const int row, int* out_id, int id, const float prob,
+                                            const float cum, const int slen, int* s_ids)
+{
+    if (id == 0x7fffffff || id < 0) {
+        id = 0;
+    }
+    *out_id = id;
+    if (p.return_cum_log_probs) {
+        const float lp = logf(prob);
+        if (p.cum_log_probs) {
+            p.cum_log_probs[row] = cum + lp;
+        }
+        store_output_log_prob(p, step, row, lp);
+    }
+    p.seq_len[row]  = slen + 1;
+    p.finished[row] = (id == p.end_id);
+    if (s_ids && row < 8) {
+        s_ids[row] = id;
+    }
+}
+// (for a caller that has not requested the row's state ahead)
+__device__ __forceinline__ void commit_pick(const SamplingParams& p, const int step, const int row, int* out_id, const int id,
+                                            const float prob, int* s_ids)
+{
+    const float cum = (p.return_cum_log_probs && p.cum_log_probs) ? p.cum_log_probs[row] : 0.f;
+    commit_pick(p, step, row, out_id, id, prob, cum, p.seq_len[row], s_ids);
+}
+
+// one candidate per slice (k = 1): the best of the nsl (<= 256) in sv / si -> sv[0] / si[0]
+__device__ __forceinline__ void best_of_slices(float* sv, int* si, const int nsl, float* redv, int* redi)
+{
+    __syncthreads();
+    VI best{-INFINITY, 0x7fffffff};
+    if ((int)threadIdx.x < nsl) {
+        best.v = sv[threadIdx.x];
+        best.i = si[threadIdx.x];
+    }
+    const VI r = block_best(best, redv, redi);
+    if (threadIdx.x == 0) {
+        sv[0] = r.v;
+        si[0] = r.i;
+    }
+    __syncthreads();
+}
+
+// The top-k layer's draw by ONE thread (sampling_topk_kernels.cu:210-311): sv[0, k) are the row's k best values, best first; they
+// become their probabilities, a uniform number is drawn (draw_counter advances) and the walk's place is returned.  stat(2 q),
+// stat(2 q + 1): {max, sum of exponentials} of slice q < NSL, read only with return_cum_log_probs.
+template<int NSL, class Stat>
+__device__ __forceinline__ int topk_draw(const SamplingParams& p, const int row, const int k, float* sv, Stat stat)
+{
+    const float smax = sv[0];
+    float       ssum = 0.f;
+    float       row_max = 0.f, row_den = 1.f;
+    if (p.return_cum_log_probs) {  // addBiasSoftMax of the row (sampling_topp_kernels.cu:1296-1345) from the slice statistics
+        float sm[NSL], ss[NSL];
+        row_max = -FLT_MAX;
+        for (int q = 0; q < NSL; q++) {
+            sm[q]   = stat(2 * q);
+            ss[q]   = stat(2 * q + 1);
+            row_max = fmaxf(row_max, sm[q]);
+        }
+        float tot = 0.f;
+        for (int q = 0; q < NSL; q++) {
+            tot += ss[q] * __expf(sm[q] - row_max);
+        }
+        row_den = tot + 1e-6f;
+    }
+    for (int i = 0; i < k; i++) {
+        float u = sv[i];
+        if (!p.return_cum_log_probs) {
+            u = __expf(u - smax);  // :271-275
+        }
+        else {
+            u = __expf(u - row_max) / row_den;  // the probability the reference's in-place softmax leaves there
+        }
+        sv[i] = u;
+        ssum += u;
+    }
+    const float u01 = ftcf_uniform(p.random_seed[row], 0, p.draw_counter[row]);
+    p.draw_counter[row] += 1;
+    float rnd  = u01 * p.top_p_topk[row] * ssum;  // :283
+    int   pick = k - 1;
+    for (int i = 0; i < k; i++) {
+        rnd -= sv[i];
+        if (rnd <= 0.0f || i == k - 1) {
+            pick = i;
+            break;
+        }
+    }
+    return pick;
+}
+
 __global__ __launch_bounds__(256) void k_sample(const SamplingParams p, float* cand_v, int* cand_i)
 {
     if (p.state->all_finished) {
@@ -745,7 +792,7 @@ __global__ __launch_bounds__(256) void k_sample(const SamplingParams p, float* c
     int*             out_id = p.output_ids + (size_t)step * p.B + b;
     if (p.finished[b]) {
         if (threadIdx.x == 0) {
-            *out_id = p.end_id;  // sampling_topk_kernels.cu:239-242 ; top-p: arg max of the end mask
+            finished_row_step(p, out_id, b, nullptr);
             if (p.top_k[b] == 0) {
                 p.draw_counter[b] += 1;  // (the top-p layer draws before it looks at `finished`: sampling_topp_kernels.cu:910-913)
             }
@@ -791,75 +838,16 @@ __global__ __launch_bounds__(256) void k_sample(const SamplingParams p, float* c
         else if (kc > 1) {
             bitonic_sort_best_first(sv, si, n2);
         }
-        else {  // one candidate per slice: the best of 8
-            __syncthreads();
-            VI best{-INFINITY, 0x7fffffff};
-            if (threadIdx.x < TOPK_BLOCKS) {
-                best.v = sv[threadIdx.x];
-                best.i = si[threadIdx.x];
-            }
-            const VI r = block_best(best, redv, redi);
-            if (threadIdx.x == 0) {
-                sv[0] = r.v;
-                si[0] = r.i;
-            }
-            __syncthreads();
+        else {
+            best_of_slices(sv, si, TOPK_BLOCKS, redv, redi);
         }
     }
     if (k > 0) {
         // ---- top-k layer (sampling_topk_kernels.cu:210-311): sv / si [0, k) are the row's k best ----
         if (threadIdx.x == 0) {
-            const float smax = sv[0];
-            float       ssum = 0.f;
-            float       row_max = 0.f, row_den = 1.f;
-            if (p.return_cum_log_probs) {  // addBiasSoftMax of the row (sampling_topp_kernels.cu:1296-1345) from the slice statistics
-                const float* st = reinterpret_cast<const float*>(cand_i + (size_t)p.B * TOPK_BLOCKS * TOPK_MAX) + (size_t)b * TOPK_BLOCKS * 2;
-                row_max         = -FLT_MAX;
-                for (int q = 0; q < TOPK_BLOCKS; q++) {
-                    row_max = fmaxf(row_max, st[2 * q]);
-                }
-                float tot = 0.f;
-                for (int q = 0; q < TOPK_BLOCKS; q++) {
-                    tot += st[2 * q + 1] * __expf(st[2 * q] - row_max);
-                }
-                row_den = tot + 1e-6f;
-            }
-            for (int i = 0; i < k; i++) {
-                float u = sv[i];
-                if (!p.return_cum_log_probs) {
-                    u = __expf(u - smax);  // :271-275
-                }
-                else {
-                    u = __expf(u - row_max) / row_den;  // the probability the reference's in-place softmax leaves there
-                }
-                sv[i] = u;
-                ssum += u;
-            }
-            const float u01 = ftcf_uniform(p.random_seed[b], 0, p.draw_counter[b]);
-            p.draw_counter[b] += 1;
-            float rnd  = u01 * p.top_p_topk[b] * ssum;  // :283
-            int   pick = k - 1;
-            for (int i = 0; i < k; i++) {
-                rnd -= sv[i];
-                if (rnd <= 0.0f || i == k - 1) {
-                    pick = i;
-                    break;
-                }
-            }
-            int id = si[pick];
-            if (id == 0x7fffffff || id < 0) {
-                id = 0;
-            }
-            *out_id = id;
-            if (p.return_cum_log_probs) {
-                const float lp = logf(sv[pick]);
-                if (p.cum_log_probs) {
-                    p.cum_log_probs[b] += lp;
-                }
-                store_output_log_prob(p, step, b, lp);
-            }
-            p.seq_len[b] += 1;  // :305-308
-            p.finished[b] = (id == p.end_id);
+            const float* st   = reinterpret_cast<const float*>(cand_i + (size_t)p.B * TOPK_BLOCKS * TOPK_MAX) + (size_t)b * TOPK_BLOCKS * 2;
+            const int    pick = topk_draw<TOPK_BLOCKS>(p, b, k, sv, [&](const int i) { return st[i]; });
+            commit_pick(p, step, b, out_id, si[pick], sv[pick], nullptr);
         }
     }
     else {
@@ -886,12 +874,7 @@ __global__ __launch_bounds__(256) void k_sample(const SamplingParams p, float* c
                     for (int j = threadIdx.x; j < TOPP_K; j += 256) {
                         mn = fminf(mn, cv[q * TOPK_MAX + j]);
                     }
-                    mn = -wave_max(-mn);
-                    if ((threadIdx.x & 63) == 0) {
-                        redv[threadIdx.x >> 6] = mn;
-                    }
-                    __syncthreads();
-                    v_cut = fmaxf(v_cut, fminf(fminf(redv[0], redv[1]), fminf(redv[2], redv[3])));
+                    v_cut = fmaxf(v_cut, -block_max(-mn, redv, 4));
                     __syncthreads();
                 }
             }
@@ -972,16 +955,7 @@ __global__ __launch_bounds__(256) void k_sample(const SamplingParams p, float* c
             pr = fv[sel];
         }
         if (threadIdx.x == 0) {
-            *out_id = id;
-            if (p.return_cum_log_probs) {
-                const float lp = logf(pr);
-                if (p.cum_log_probs) {
-                    p.cum_log_probs[b] += lp;
-                }
-                store_output_log_prob(p, step, b, lp);
-            }
-            p.seq_len[b] += 1;
-            p.finished[b] = (id == p.end_id);
+            commit_pick(p, step, b, out_id, id, pr, nullptr);
         }
     }
 }
@@ -1063,19 +1037,6 @@ __global__ void k_decode_finish(const SamplingParams p)
     decode_finish_body(p, p.state->step);
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// The tail of an all-greedy step, run by the ONE workgroup (256 threads) that drew the launch's last ticket (k_greedy_decode,
-// k_lm_head_greedy): every row's token from the slices' partials part[B][nsl][4] = {best value, its id, slice max, slice sum of
-// exponentials} exactly as k_sample does for k = 1 (sampling_topk_kernels.cu:210-311: probability of the best token under the
-// row's soft-max, the uniform draw consumed, cum_log_probs, sequence length, finished), the step's bookkeeping
-// (decode_finish_body) and the NEXT token's prologue (k_step_prologue: decoding_kernels.cu:145-191 embedding lookup + the
-// step's rotary table).  Everything here is a chain of dependent memory round trips on the token's critical path (this tail
-// was 10 of k_greedy_decode's 17 us): a row's state is requested together with its partials, the embedding row as soon as the
-// token is known, the pinned host flags are the last stores.
-// ---------------------------------------------------------------------------------------------------------------------
-// TAGGED: the partials are granules {tag, value} (part: [B][nsl][4] 8-byte words, the value in the low half) written by
-// workgroups that may still be running: a batch of partials is re-read until every tag is `tag` (bounded: a give-up sets
-// p.h_flags[2] and the step is finished on what is there).
 // The tail of a step behind the picks, by the workgroup (256 threads) that made them: the NEXT token's prologue (k_step_prologue:
 // decoding_kernels.cu:145-191 embedding lookup + the step's rotary table), the step's bookkeeping (decode_finish_body) and the
 // host flags.  s_ids: the tokens of rows 0..7 in LDS (the others are re-read from output_ids).
@@ -1137,6 +1098,49 @@ __device__ __forceinline__ void decode_step_tail(const SamplingParams& p, const 
     decode_publish_host(p, step, all);
 }
 
+// Four waves' {best, max, sum of exponentials} of a row -> the workgroup's: v / i / m / s hold wave w's entry at [w * stride].
+// Returns the best; row_max / tot: the maximum and the sum rescaled to it, added with w ascending.
+__device__ __forceinline__ VI merge_waves(const float* v, const int* i, const float* m, const float* s, const int stride, float& row_max,
+                                          float& tot)
+{
+    VI r{v[0], i[0]};
+    row_max = m[0];
+#pragma unroll
+    for (int w = 1; w < 4; w++) {
+        if (better(v[w * stride], i[w * stride], r.v, r.i)) {
+            r.v = v[w * stride];
+            r.i = i[w * stride];
+        }
+        row_max = fmaxf(row_max, m[w * stride]);
+    }
+    tot = 0.f;
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+        tot += s[w * stride] * __expf(m[w * stride] - row_max);
+    }
+    return r;
+}
+
+// the ticket of a launch of `total` workgroups on state->pad, drawn by ONE thread: true for the last one, which re-arms the counter
+__device__ __forceinline__ bool last_ticket(DecodeState* state, const int total)
+{
+    const int  t    = __hip_atomic_fetch_add(&state->pad, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const bool last = t == total - 1;
+    if (last) {
+        __hip_atomic_store(&state->pad, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-armed for the next token
+    }
+    return last;
+}
+
+// The picks of an all-greedy step and its tail, run by ONE workgroup (256 threads) behind the launch's partials (k_greedy_decode,
+// k_lm_head_greedy): part[B][nsl][4] = {best value, its id, slice max, slice sum of exponentials}.  A row's token is the top-k layer's
+// for k = 1 (sampling_topk_kernels.cu:210-311): the probability of the best token under the row's soft-max, the uniform draw
+// consumed (:283 draws for k = 1 too).  Everything here is a chain of dependent memory round trips on the token's critical path
+// (this tail was 10 of k_greedy_decode's 17 us): a row's state is requested together with its partials, the embedding row as soon
+// as the token is known, the pinned host flags are the last stores.
+// TAGGED: the partials are granules {tag, value} (part: [B][nsl][4] 8-byte words, the value in the low half) written by
+// workgroups that may still be running: a batch of partials is re-read until every tag is `tag` (bounded: a give-up sets
+// p.h_flags[2] and the step is finished on what is there).
 constexpr int GREEDY_MAXQ = 4;  // partials of a row a thread requests together
 constexpr int GREEDY_SPINS = 1 << 20;
 template<bool TAGGED = false>
@@ -1152,6 +1156,27 @@ __device__ __forceinline__ void greedy_finish(const SamplingParams& p, const flo
     if (threadIdx.x == 0) {
         steps_done = p.state->steps_done;
     }
+    // the owning thread's view of a row's state {draw counter, cum_log_probs, seq_len} travels with the partials
+    struct RowState {
+        uint64_t draws;
+        float    cum;
+        int      slen;
+    };
+    auto load_state = [&](const int row, RowState& st) {
+        st.draws = p.draw_counter[row];
+        st.slen  = p.seq_len[row];
+        if (p.return_cum_log_probs && p.cum_log_probs) {
+            st.cum = p.cum_log_probs[row];
+        }
+    };
+    auto commit = [&](const int row, int* out_id, const VI r, const float row_max, const float tot, const RowState& st) {
+        float prob = 1.f;
+        if (p.return_cum_log_probs) {
+            prob = __expf(r.v - row_max) / (tot + 1e-6f);
+        }
+        p.draw_counter[row] = st.draws + 1;
+        commit_pick(p, step, row, out_id, r.i, prob, st.cum, st.slen, s_ids);
+    };
     int picked = 0;
     // batches of more than four rows (k_greedy_decode's 32 slices per row): ONE WAVE per row, four rows at a time -- no workgroup
     // barrier per row (16 rows took 70 us one after the other; the same picks, the same arithmetic per row)
@@ -1161,22 +1186,13 @@ __device__ __forceinline__ void greedy_finish(const SamplingParams& p, const flo
             int* out_id = p.output_ids + (size_t)step * p.B + row;
             if (p.finished[row]) {
                 if (lane == 0) {
-                    *out_id = p.end_id;  // sampling_topk_kernels.cu:239-242
-                    if (row < 8) {
-                        s_ids[row] = p.end_id;
-                    }
+                    finished_row_step(p, out_id, row, s_ids);
                 }
                 continue;
             }
-            uint64_t draws = 0;
-            float    cum   = 0.f;
-            int      slen  = 0;
+            RowState st{0, 0.f, 0};
             if (lane == 0) {
-                draws = p.draw_counter[row];
-                slen  = p.seq_len[row];
-                if (p.return_cum_log_probs && p.cum_log_probs) {
-                    cum = p.cum_log_probs[row];
-                }
+                load_state(row, st);
             }
             const gu32* q = (const gu32*)(part + (size_t)row * nsl * 4);
             VI          cand{-INFINITY, 0x7fffffff};
@@ -1191,28 +1207,7 @@ __device__ __forceinline__ void greedy_finish(const SamplingParams& p, const flo
             const float row_max = wave_max(mq);
             const float tot     = wave_sum(sq * __expf(mq - row_max));  // (lanes without a slice add 0 * exp(.) = 0)
             if (lane == 0) {
-                float prob = 1.f;
-                if (p.return_cum_log_probs) {
-                    prob = __expf(r.v - row_max) / (tot + 1e-6f);
-                }
-                p.draw_counter[row] = draws + 1;
-                int id = r.i;
-                if (id == 0x7fffffff || id < 0) {
-                    id = 0;
-                }
-                *out_id = id;
-                if (p.return_cum_log_probs) {
-                    const float lp = logf(prob);
-                    if (p.cum_log_probs) {
-                        p.cum_log_probs[row] = cum + lp;
-                    }
-                    store_output_log_prob(p, step, row, lp);
-                }
-                p.seq_len[row]  = slen + 1;
-                p.finished[row] = (id == p.end_id);
-                if (row < 8) {
-                    s_ids[row] = id;
-                }
+                commit(row, out_id, r, row_max, tot, st);
             }
         }
     }
@@ -1220,23 +1215,13 @@ __device__ __forceinline__ void greedy_finish(const SamplingParams& p, const flo
         int* out_id = p.output_ids + (size_t)step * p.B + row;
         if (p.finished[row]) {
             if (threadIdx.x == 0) {
-                *out_id = p.end_id;  // sampling_topk_kernels.cu:239-242
-                if (row < 8) {
-                    s_ids[row] = p.end_id;
-                }
+                finished_row_step(p, out_id, row, s_ids);
             }
             continue;
         }
-        // thread 0's view of the row's state travels with the partials
-        uint64_t draws = 0;
-        float    cum   = 0.f;
-        int      slen  = 0;
+        RowState st{0, 0.f, 0};
         if (threadIdx.x == 0) {
-            draws = p.draw_counter[row];
-            slen  = p.seq_len[row];
-            if (p.return_cum_log_probs && p.cum_log_probs) {
-                cum = p.cum_log_probs[row];
-            }
+            load_state(row, st);
         }
         const gu32* q = (const gu32*)(part + (size_t)row * nsl * 4);
         typedef __attribute__((address_space(1))) unsigned long long gu64;
@@ -1312,43 +1297,9 @@ __device__ __forceinline__ void greedy_finish(const SamplingParams& p, const flo
         }
         __syncthreads();
         if (threadIdx.x == 0) {
-            VI    r{x_v[pb][0], x_i[pb][0]};
-            float row_max = x_m[pb][0];
-#pragma unroll
-            for (int w = 1; w < 4; w++) {
-                if (better(x_v[pb][w], x_i[pb][w], r.v, r.i)) {
-                    r.v = x_v[pb][w];
-                    r.i = x_i[pb][w];
-                }
-                row_max = fmaxf(row_max, x_m[pb][w]);
-            }
-            float tot = 0.f;
-#pragma unroll
-            for (int w = 0; w < 4; w++) {
-                tot += x_s[pb][w] * __expf(x_m[pb][w] - row_max);
-            }
-            float prob = 1.f;
-            if (p.return_cum_log_probs) {
-                prob = __expf(r.v - row_max) / (tot + 1e-6f);
-            }
-            p.draw_counter[row] = draws + 1;  // (the top-k layer draws its uniform number for k = 1 too: sampling_topk_kernels.cu:283)
-            int id = r.i;
-            if (id == 0x7fffffff || id < 0) {
-                id = 0;
-            }
-            *out_id = id;
-            if (p.return_cum_log_probs) {
-                const float lp = logf(prob);
-                if (p.cum_log_probs) {
-                    p.cum_log_probs[row] = cum + lp;
-                }
-                store_output_log_prob(p, step, row, lp);
-            }
-            p.seq_len[row]  = slen + 1;  // :305-308
-            p.finished[row] = (id == p.end_id);
-            if (row < 8) {
-                s_ids[row] = id;
-            }
+            float    row_max, tot;
+            const VI r = merge_waves(x_v[pb], x_i[pb], x_m[pb], x_s[pb], 1, row_max, tot);
+            commit(row, out_id, r, row_max, tot, st);
         }
     }
     decode_step_tail(p, step, steps_done, s_ids, by_wave);
@@ -1361,9 +1312,7 @@ __device__ __forceinline__ void greedy_finish(const SamplingParams& p, const flo
 // reference's default request, and the headline's -- the same results come out of one: 32 slices per row keep their logits in
 // registers for the arg max (`better`: highest value, lowest id) and the soft-max statistics return_cum_log_probs needs
 // (sampling_topp_kernels.cu:1296-1345 addBiasSoftMax), write-through partials + a ticket, and the workgroup that draws the
-// last ticket picks every row's token exactly as k_sample does for k = 1 (sampling_topk_kernels.cu:210-311: probability of the
-// best token under the row's soft-max, the uniform draw consumed, cum_log_probs, sequence length, finished) and then runs the
-// step's bookkeeping (decode_finish_body: stop words, length criterion, padding counts, step counter).
+// last ticket picks every row's token and runs the step's tail (greedy_finish).
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int GREEDY_SLICES = 32;
 constexpr int GREEDY_MAXE   = 16;  // logits per thread: V <= 32 * 256 * 16 = 131072
@@ -1385,50 +1334,10 @@ __global__ __launch_bounds__(256) void k_greedy_decode(const SamplingParams p, f
         const float* l  = p.logits + (size_t)b * V + i0;
         // min_length (sampling_penalty_kernels.cu:485-520): end_id cannot be chosen yet
         const bool mask_end = p.min_length && (p.seq_len[b] + 1 - p.max_input_len < p.min_length[b]);
-        float      vals[GREEDY_MAXE];
-        const int  ne = n > (int)threadIdx.x ? (n - (int)threadIdx.x + 255) / 256 : 0;
-#pragma unroll
-        for (int j = 0; j < GREEDY_MAXE; j++) {
-            vals[j] = (j < ne) ? l[threadIdx.x + 256 * j] : -INFINITY;
-        }
-        VI    best{-INFINITY, 0x7fffffff};
-        float lmax = -FLT_MAX;
-#pragma unroll
-        for (int j = 0; j < GREEDY_MAXE; j++) {
-            if (j < ne) {
-                const int i = threadIdx.x + 256 * j;
-                if (mask_end && i0 + i == p.end_id) {
-                    vals[j] = -FLT_MAX;
-                }
-                const float v = vals[j];
-                lmax          = fmaxf(lmax, v);
-                if (best.i == 0x7fffffff || better(v, i, best.v, best.i)) {
-                    best.v = v;
-                    best.i = i;
-                }
-            }
-        }
-        lmax = wave_max(lmax);
-        if ((threadIdx.x & 63) == 0) {
-            redv[threadIdx.x >> 6] = lmax;
-        }
-        __syncthreads();
-        const float m = fmaxf(fmaxf(redv[0], redv[1]), fmaxf(redv[2], redv[3]));
-        __syncthreads();
-        float se = 0.f;
-#pragma unroll
-        for (int j = 0; j < GREEDY_MAXE; j++) {
-            if (j < ne) {
-                se += __expf(vals[j] - m);
-            }
-        }
-        se = wave_sum(se);
-        if ((threadIdx.x & 63) == 0) {
-            redv[threadIdx.x >> 6] = se;
-        }
-        __syncthreads();
-        const float sum = (redv[0] + redv[1]) + (redv[2] + redv[3]);
-        __syncthreads();
+        float      vals[GREEDY_MAXE], lmax, m;
+        const int  ne   = n > (int)threadIdx.x ? (n - (int)threadIdx.x + 255) / 256 : 0;
+        const VI   best = slice_load(vals, l, ne, mask_end ? p.end_id - i0 : -1, lmax);
+        const float sum = slice_stats(vals, ne, lmax, redv, m);
         const VI r = block_best(best, redv, redi);
         if (threadIdx.x == 0) {
             // {best value, its id, slice max, slice sum of exponentials}: write-through stores (the reader may sit on another XCD)
@@ -1443,12 +1352,7 @@ __global__ __launch_bounds__(256) void k_greedy_decode(const SamplingParams p, f
     // ---- ticket: the last workgroup of the launch finishes the step ----
     if (threadIdx.x == 0) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this workgroup's partial has been acknowledged (write-through)
-        const int total = GREEDY_SLICES * p.B;
-        const int t     = __hip_atomic_fetch_add(&p.state->pad, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last          = (t == total - 1) ? 1 : 0;
-        if (s_last) {
-            __hip_atomic_store(&p.state->pad, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-armed for the next token
-        }
+        s_last = last_ticket(p.state, GREEDY_SLICES * p.B) ? 1 : 0;
     }
     __syncthreads();
     if (!s_last) {
@@ -1464,9 +1368,9 @@ __global__ __launch_bounds__(256) void k_greedy_decode(const SamplingParams p, f
 // where the all-greedy step takes 12.  Same structure as k_greedy_decode: 32 slices per row keep their logits in registers (min_length
 // mask, soft-max statistics for return_cum_log_probs, the radix select of the slice's k best: slice_select), write-through
 // candidates + a ticket, and the workgroup that draws the last ticket merges every row's 32 candidate sets (union_topk), turns
-// the k best into probabilities and draws exactly as k_sample does (sampling_topk_kernels.cu:210-311), then runs the step's tail
-// (decode_step_tail).  Rows: top_k in [1, 64], no top-p row, temperature 1, no repetition penalty, no optional-token list,
-// at most TKD_MAXB rows (the finishing workgroup takes them one after the other).
+// the k best into probabilities and draws (topk_draw), then runs the step's tail (decode_step_tail).  Rows: top_k in [1, 64], no
+// top-p row, temperature 1, no repetition penalty, no optional-token list, at most TKD_MAXB rows (the finishing workgroup takes
+// them one after the other).
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int TKD_SLICES = 32;
 constexpr int TKD_MAXE   = 16;  // logits per thread: V <= 32 * 256 * 16 = 131072
@@ -1501,56 +1405,17 @@ __global__ __launch_bounds__(256) void k_topk_decode(const SamplingParams p, flo
         int*         oi = cand_i + ((size_t)b * TKD_SLICES + blk) * TKD_MAXK;
         // min_length (sampling_penalty_kernels.cu:485-520): end_id cannot be chosen yet
         const bool mask_end = p.min_length && (p.seq_len[b] + 1 - p.max_input_len < p.min_length[b]);
-        float      vals[TKD_MAXE];
-        const int  ne = n > (int)threadIdx.x ? (n - (int)threadIdx.x + 255) / 256 : 0;
-#pragma unroll
-        for (int j = 0; j < TKD_MAXE; j++) {
-            vals[j] = (j < ne) ? l[threadIdx.x + 256 * j] : -INFINITY;
-        }
-        VI    best{-INFINITY, 0x7fffffff};
-        float lmax = -FLT_MAX;
-#pragma unroll
-        for (int j = 0; j < TKD_MAXE; j++) {
-            if (j < ne) {
-                const int i = threadIdx.x + 256 * j;
-                if (mask_end && i0 + i == p.end_id) {
-                    vals[j] = -FLT_MAX;
-                }
-                const float v = vals[j];
-                lmax          = fmaxf(lmax, v);
-                if (best.i == 0x7fffffff || better(v, i, best.v, best.i)) {
-                    best.v = v;
-                    best.i = i;
-                }
-            }
-        }
-        if (p.return_cum_log_probs) {  // soft-max statistics of the slice: {max, sum of exp(v - max)}
-            lmax = wave_max(lmax);
-            if ((threadIdx.x & 63) == 0) {
-                redv[threadIdx.x >> 6] = lmax;
-            }
-            __syncthreads();
-            const float m = fmaxf(fmaxf(redv[0], redv[1]), fmaxf(redv[2], redv[3]));
-            __syncthreads();
-            float se = 0.f;
-#pragma unroll
-            for (int j = 0; j < TKD_MAXE; j++) {
-                if (j < ne) {
-                    se += __expf(vals[j] - m);
-                }
-            }
-            se = wave_sum(se);
-            if ((threadIdx.x & 63) == 0) {
-                redv[threadIdx.x >> 6] = se;
-            }
-            __syncthreads();
+        float      vals[TKD_MAXE], lmax;
+        const int  ne   = n > (int)threadIdx.x ? (n - (int)threadIdx.x + 255) / 256 : 0;
+        const VI   best = slice_load(vals, l, ne, mask_end ? p.end_id - i0 : -1, lmax);
+        if (p.return_cum_log_probs) {  // {max, sum of exp(v - max)} of the slice for the row's soft-max
+            float       m;
+            const float sum = slice_stats(vals, ne, lmax, redv, m);
             if (threadIdx.x == 0) {
                 gu32* st = (gu32*)(stats + ((size_t)b * TKD_SLICES + blk) * 2);
                 __hip_atomic_store(st + 0, __float_as_uint(n > 0 ? m : -FLT_MAX), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(st + 1, __float_as_uint(n > 0 ? ((redv[0] + redv[1]) + (redv[2] + redv[3])) : 0.f), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(st + 1, __float_as_uint(n > 0 ? sum : 0.f), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
-            __syncthreads();
         }
         const int ke = k < n ? k : n;  // candidates this slice can supply
         for (int i = ke + threadIdx.x; i < k; i += 256) {
@@ -1570,12 +1435,7 @@ __global__ __launch_bounds__(256) void k_topk_decode(const SamplingParams p, flo
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this thread's candidates have been acknowledged (write-through)
     __syncthreads();
     if (threadIdx.x == 0) {
-        const int total = TKD_SLICES * p.B;
-        const int t     = __hip_atomic_fetch_add(&p.state->pad, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last          = (t == total - 1) ? 1 : 0;
-        if (s_last) {
-            __hip_atomic_store(&p.state->pad, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-armed for the next token
-        }
+        s_last = last_ticket(p.state, TKD_SLICES * p.B) ? 1 : 0;
     }
     __syncthreads();
     if (!s_last) {
@@ -1595,10 +1455,7 @@ __global__ __launch_bounds__(256) void k_topk_decode(const SamplingParams p, flo
         int* out_id = p.output_ids + (size_t)step0 * p.B + row;
         if (p.finished[row]) {
             if (threadIdx.x == 0) {
-                *out_id = p.end_id;  // sampling_topk_kernels.cu:239-242
-                if (row < 8) {
-                    s_ids[row] = p.end_id;
-                }
+                finished_row_step(p, out_id, row, s_ids);
             }
             continue;
         }
@@ -1642,79 +1499,16 @@ __global__ __launch_bounds__(256) void k_topk_decode(const SamplingParams p, flo
         else if (k > 1) {
             bitonic_sort_best_first(sv, si, n2);
         }
-        else {  // one candidate per slice: the best of 32
-            __syncthreads();
-            VI best{-INFINITY, 0x7fffffff};
-            if (threadIdx.x < TKD_SLICES) {
-                best.v = sv[threadIdx.x];
-                best.i = si[threadIdx.x];
-            }
-            const VI r = block_best(best, redv, redi);
-            if (threadIdx.x == 0) {
-                sv[0] = r.v;
-                si[0] = r.i;
-            }
-            __syncthreads();
+        else {
+            best_of_slices(sv, si, TKD_SLICES, redv, redi);
         }
-        // ---- top-k layer (sampling_topk_kernels.cu:210-311): sv / si [0, k) are the row's k best ----
+        // ---- top-k layer: sv / si [0, k) are the row's k best ----
         if (threadIdx.x == 0) {
-            const float smax = sv[0];
-            float       ssum = 0.f;
-            float       row_max = 0.f, row_den = 1.f;
-            if (p.return_cum_log_probs) {  // addBiasSoftMax of the row (sampling_topp_kernels.cu:1296-1345) from the slice statistics
-                const gu32* st = (const gu32*)(stats + (size_t)row * TKD_SLICES * 2);
-                float       sm[TKD_SLICES], ss[TKD_SLICES];
-                row_max = -FLT_MAX;
-                for (int q = 0; q < TKD_SLICES; q++) {
-                    sm[q]   = __uint_as_float(__hip_atomic_load(st + 2 * q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                    ss[q]   = __uint_as_float(__hip_atomic_load(st + 2 * q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                    row_max = fmaxf(row_max, sm[q]);
-                }
-                float tot = 0.f;
-                for (int q = 0; q < TKD_SLICES; q++) {
-                    tot += ss[q] * __expf(sm[q] - row_max);
-                }
-                row_den = tot + 1e-6f;
-            }
-            for (int i = 0; i < k; i++) {
-                float u = sv[i];
-                if (!p.return_cum_log_probs) {
-                    u = __expf(u - smax);  // :271-275
-                }
-                else {
-                    u = __expf(u - row_max) / row_den;  // the probability the reference's in-place softmax leaves there
-                }
-                sv[i] = u;
-                ssum += u;
-            }
-            const float u01 = ftcf_uniform(p.random_seed[row], 0, p.draw_counter[row]);
-            p.draw_counter[row] += 1;
-            float rnd  = u01 * p.top_p_topk[row] * ssum;  // :283
-            int   pick = k - 1;
-            for (int i = 0; i < k; i++) {
-                rnd -= sv[i];
-                if (rnd <= 0.0f || i == k - 1) {
-                    pick = i;
-                    break;
-                }
-            }
-            int id = si[pick];
-            if (id == 0x7fffffff || id < 0) {
-                id = 0;
-            }
-            *out_id = id;
-            if (p.return_cum_log_probs) {
-                const float lp = logf(sv[pick]);
-                if (p.cum_log_probs) {
-                    p.cum_log_probs[row] += lp;
-                }
-                store_output_log_prob(p, step0, row, lp);
-            }
-            p.seq_len[row] += 1;  // :305-308
-            p.finished[row] = (id == p.end_id);
-            if (row < 8) {
-                s_ids[row] = id;
-            }
+            const gu32* st   = (const gu32*)(stats + (size_t)row * TKD_SLICES * 2);
+            const int   pick = topk_draw<TKD_SLICES>(p, row, k, sv, [&](const int i) {
+                return __uint_as_float(__hip_atomic_load(st + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+            });
+            commit_pick(p, step0, row, out_id, si[pick], sv[pick], s_ids);
         }
     }
     decode_step_tail(p, step0, steps_done, s_ids, false);
@@ -1794,21 +1588,8 @@ __global__ __launch_bounds__(256, 8) void k_lm_head_greedy(const f16* __restrict
         typedef __attribute__((address_space(1))) unsigned long long gu64;
 #pragma unroll
         for (int m = 0; m < M; m++) {
-            VI    r{w_v[0][m], w_i[0][m]};
-            float mx = w_m[0][m];
-#pragma unroll
-            for (int w = 1; w < 4; w++) {
-                if (better(w_v[w][m], w_i[w][m], r.v, r.i)) {
-                    r.v = w_v[w][m];
-                    r.i = w_i[w][m];
-                }
-                mx = fmaxf(mx, w_m[w][m]);
-            }
-            float sum = 0.f;
-#pragma unroll
-            for (int w = 0; w < 4; w++) {
-                sum += w_s[w][m] * __expf(w_m[w][m] - mx);
-            }
+            float    mx, sum;
+            const VI r = merge_waves(&w_v[0][m], &w_i[0][m], &w_m[0][m], &w_s[0][m], M, mx, sum);
             // granules {tag, value}, write-through (the reader sits on another XCD); a workgroup without a vocabulary row leaves
             // the neutral partial {-inf, no id, -FLT_MAX, 0}
             gu64*                    o  = (gu64*)(part + ((size_t)m * nb + blockIdx.x) * 4);
@@ -2007,417 +1788,5 @@ void launch_decode_init(uint8_t* finished, int* seq_len, float* cum_log_probs, i
     FTCF_HIP_CHECK(hipGetLastError());
 }
 
-// gatherTree with beam_width 1 and no prompts (decoding_kernels.cu:452-583) + the [time,batch] -> [batch,time] transpose
-__global__ void k_gather_tree(int* output_ids, int* sequence_lengths, const int* step_ids, const int* seq_len,
-                              const int* input_lengths, int B, int max_input_len, int total, int end_id)
-{
-    const int b = blockIdx.x;
-    if (threadIdx.x != 0) {
-        return;
-    }
-    const int tmp_len = seq_len[b] + 1;  // max_sequence_length_final_step = 1
-    sequence_lengths[b] = tmp_len;
-    const int max_len = tmp_len;
-    const int msl     = max_len < total ? max_len : total;
-    int*      beams   = output_ids + (size_t)b * total;
-    for (int t = 0; t < total; t++) {
-        beams[t] = 0;
-    }
-    if (msl <= 0) {
-        return;
-    }
-    const int in_len  = input_lengths[b];
-    const int pad_off = max_input_len - in_len;
-    beams[msl - 1 - pad_off] = step_ids[(size_t)(msl - 1) * B + b];
-    for (int level = msl - 2; level >= 0; level--) {
-        if (level >= in_len && level < max_input_len) {
-            continue;
-        }
-        const int tgt = level >= max_input_len ? level - pad_off : level;
-        beams[tgt]    = step_ids[(size_t)level * B + b];
-    }
-    for (int index = max_len - pad_off; index < total; index++) {
-        beams[index] = end_id;
-    }
-    bool fin = false;
-    for (int t = max_input_len; t < msl; t++) {
-        if (fin) {
-            beams[t] = end_id;
-        }
-        else if (beams[t] == end_id) {
-            fin = true;
-        }
-    }
-}
-
-void launch_gather_tree(int* output_ids, int* sequence_lengths, const int* step_ids, const int* seq_len,
-                        const int* input_lengths, int B, int max_input_len, int total, int end_id, hipStream_t s)
-{
-    hipLaunchKernelGGL(k_gather_tree, dim3(B), dim3(64), 0, s, output_ids, sequence_lengths, step_ids, seq_len,
-                       input_lengths, B, max_input_len, total, end_id);
-    FTCF_HIP_CHECK(hipGetLastError());
-}
-
-
-// ================================================================================================================
-// beam search (beam_width K > 1): OnlineBeamSearchLayer without BeamHypotheses
-//   layers/beam_search_layers/BaseBeamSearchLayer.cu:30-62,191-280, OnlineBeamSearchLayer.cu:25-166,
-//   kernels/beam_search_penalty_kernels.cu:89-262, kernels/online_softmax_beamsearch_kernels.cu:100-365,650-701.
-// Rows bb = batch * K + beam.  Three launches per token: rows (penalties + per-row top K of log-softmax + cum), batch
-// (K best of the K*K candidates, state / parents / cache-indirection update, stop words), then k_decode_finish.
-// ================================================================================================================
-__global__ __launch_bounds__(1024) void k_beam_rows(const BeamParams p, float* cand_v, int* cand_i, int* snap)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    __shared__ float red[64];
-    __shared__ int   redi[64];
-    __shared__ int   s_chosen[BEAM_MAX_K];
-    __shared__ int   s_cnt;
-    const int        bb = blockIdx.x, K = p.K, V = p.V;
-    const int        b = bb / K, k = bb % K, BK = p.B * K;
-    float*           l    = p.logits + (size_t)bb * V;
-    const int        step = p.state->step;
-    const int        tid = threadIdx.x, nt = blockDim.x;
-
-    if (p.optional_last_tokens && step == p.max_input_len) {  // select_optional_last_tokens.cu:22-85
-        uint32_t* bits  = reinterpret_cast<uint32_t*>(smem);
-        const int words = (V + 31) / 32;
-        for (int i = tid; i < words; i += nt) {
-            bits[i] = 0u;
-        }
-        __syncthreads();
-        for (int j = tid; j < p.optional_count; j += nt) {
-            const int t = p.optional_last_tokens[(size_t)b * p.optional_count + j];
-            if (t >= 0 && t < V) {
-                atomicOr(&bits[t >> 5], 1u << (t & 31));
-            }
-        }
-        __syncthreads();
-        for (int i = tid; i < V; i += nt) {
-            if (!((bits[i >> 5] >> (i & 31)) & 1u)) {
-                l[i] = -INFINITY;
-            }
-        }
-        __syncthreads();
-    }
-    const float temperature = p.temperature[b];
-    if (temperature != 1.0f) {  // beam_search_penalty_kernels.cu:171-262
-        const float inv = 1.0f / (temperature + 1e-6f);
-        for (int i = tid; i < V; i += nt) {
-            l[i] *= inv;
-        }
-        __syncthreads();
-    }
-    if (p.repetition_penalty && step > 0 && p.repetition_penalty[b] != 1.0f) {  // :89-153: history of THIS beam
-        float*      newv = reinterpret_cast<float*>(smem);
-        int*        idx  = reinterpret_cast<int*>(newv + p.total_len);
-        const float pen  = p.repetition_penalty[b];
-        if (tid == 0) {  // the walk along the parent chain is serial
-            const int in_len = p.input_lengths[bb];
-            int       cnt    = 0;
-            idx[cnt++]       = p.output_ids[(size_t)(step - 1) * BK + bb];
-            int parent       = k;
-            for (int i = step - 2; i >= 0; i--) {
-                if (i >= in_len && i < p.max_input_len) {
-                    continue;
-                }
-                parent     = p.parent_ids[(size_t)i * BK + b * K + parent];
-                idx[cnt++] = p.output_ids[(size_t)i * BK + b * K + parent];
-            }
-            s_cnt = cnt;
-        }
-        __syncthreads();
-        const int cnt = s_cnt;
-        for (int c = tid; c < cnt; c += nt) {
-            const float lg = l[idx[c]];
-            newv[c]        = lg > 0.0f ? lg / pen : lg * pen;
-        }
-        __syncthreads();
-        for (int c = tid; c < cnt; c += nt) {
-            l[idx[c]] = newv[c];
-        }
-        __syncthreads();
-    }
-    if (p.min_length && tid == 0) {  // :155-169
-        if (step - p.max_input_len < p.min_length[b] && p.seq_len[bb] + 1 - p.max_input_len < p.min_length[b]) {
-            l[p.end_id] = -FLT_MAX;
-        }
-    }
-    __syncthreads();
-    float* cv  = cand_v + (size_t)bb * K;
-    int*   ci  = cand_i + (size_t)bb * K;
-    const float cum = p.cum_log_probs[bb];
-    if (tid == 0) {  // pre-update length / finished of every row for the batch kernel (its workgroups overwrite them)
-        snap[bb]      = p.seq_len[bb];
-        snap[BK + bb] = p.finished[bb];
-    }
-    if (p.finished[bb]) {  // a finished beam offers its end token at cum + 0 and nothing else (:296-365)
-        for (int i = tid; i < K; i += nt) {
-            const int j = (i == 0) ? p.end_id : (i - 1 < p.end_id ? i - 1 : i);
-            cv[i]       = (i == 0) ? cum : -INFINITY;
-            ci[i]       = j + bb * V;
-        }
-        return;
-    }
-    float mx = -FLT_MAX;
-    for (int i = tid; i < V; i += nt) {
-        mx = fmaxf(mx, l[i]);
-    }
-    mx = wave_max(mx);
-    if ((tid & 63) == 0) {
-        red[tid >> 6] = mx;
-    }
-    __syncthreads();
-    mx = red[0];
-    for (int w = 1; w < (nt >> 6); w++) {
-        mx = fmaxf(mx, red[w]);
-    }
-    __syncthreads();
-    float sum = 0.f;
-    for (int i = tid; i < V; i += nt) {
-        sum += expf(l[i] - mx);
-    }
-    sum = wave_sum(sum);
-    if ((tid & 63) == 0) {
-        red[tid >> 6] = sum;
-    }
-    __syncthreads();
-    float tot = 0.f;
-    for (int w = 0; w < (nt >> 6); w++) {
-        tot += red[w];
-    }
-    __syncthreads();
-    const float logd = logf(tot);
-    // K rounds of block arg-best (ties: lower token id), skipping the tokens already taken
-    for (int r = 0; r < K; r++) {
-        VI best{-INFINITY, 0x7fffffff};
-        for (int i = tid; i < V; i += nt) {
-            const float v = l[i];
-            if (better(v, i, best.v, best.i)) {
-                bool taken = false;
-                for (int c = 0; c < r; c++) {
-                    taken |= (s_chosen[c] == i);
-                }
-                if (!taken) {
-                    best.v = v;
-                    best.i = i;
-                }
-            }
-        }
-        best = block_best(best, red, redi);
-        if (tid == 0) {
-            s_chosen[r] = best.i;
-            cv[r]       = (best.v - mx - logd) + cum;
-            ci[r]       = best.i + bb * V;
-        }
-        __syncthreads();
-    }
-}
-
-__global__ __launch_bounds__(256) void k_beam_batch(const BeamParams p, const float* cand_v, const int* cand_i,
-                                                    const int* snap)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    __shared__ float red[8];
-    __shared__ int   redi[8];
-    __shared__ int   s_parent[BEAM_MAX_K], s_word[BEAM_MAX_K], s_seq[BEAM_MAX_K], s_fin[BEAM_MAX_K];
-    __shared__ float s_cum[BEAM_MAX_K];
-    const int        b = blockIdx.x, K = p.K, V = p.V, BK = p.B * K, KK = K * K;
-    const int        tid = threadIdx.x, nt = blockDim.x;
-    const int        step = p.state->step;
-    float*           sv   = reinterpret_cast<float*>(smem);  // [K*K] penalised scores
-    uint8_t*         tk   = reinterpret_cast<uint8_t*>(sv + KK);  // [K*K] taken
-    const float*     cy   = cand_v + (size_t)b * KK;
-    const int*       cx   = cand_i + (size_t)b * KK;
-    const float      len_pen = p.len_penalty[b], diversity = p.diversity_rate[b];
-    // batch_topk_kernel (online_softmax_beamsearch_kernels.cu:100-262, no beam hypotheses).  NB it indexes finished /
-    // sequence_lengths by the BATCH id, restated as written (only matters with len_penalty != 0).
-    const int* old_seq = snap;
-    const int* old_fin = snap + BK;
-    const int  length  = old_fin[b] ? old_seq[b] : old_seq[b] + 1;
-    for (int e = tid; e < KK; e += nt) {
-        float v = cy[e];
-        if (len_pen != 0.0f && length != 1) {
-            v = v / powf((float)length, len_pen);
-        }
-        v += diversity * (float)(e % K);
-        sv[e] = v;
-        tk[e] = 0;
-    }
-    __syncthreads();
-    for (int r = 0; r < K; r++) {
-        VI best{-INFINITY, 0x7fffffff};
-        for (int e = tid; e < KK; e += nt) {
-            if (!tk[e] && better(sv[e], e, best.v, best.i)) {
-                best.v = sv[e];
-                best.i = e;
-            }
-        }
-        best = block_best(best, red, redi);
-        if (tid == 0) {
-            const int e  = best.i;
-            tk[e]        = 1;
-            const int z  = cx[e];
-            const int pk = (z / V) % K;
-            s_parent[r]  = pk;
-            s_word[r]    = z % V;
-            s_cum[r]     = cy[e];
-            // update_kernel (OnlineBeamSearchLayer.cu:25-58): lengths follow the parent beam
-            const int pb = b * K + pk;
-            s_seq[r]     = old_fin[pb] ? old_seq[pb] : old_seq[pb] + 1;
-            s_fin[r]     = (z % V) == p.end_id;
-        }
-        __syncthreads();
-    }
-    if (tid < K) {
-        const int bb                         = b * K + tid;
-        p.seq_len[bb]                        = s_seq[tid];
-        p.finished[bb]                       = (uint8_t)s_fin[tid];
-        p.parent_ids[(size_t)step * BK + bb] = s_parent[tid];
-        p.output_ids[(size_t)step * BK + bb] = s_word[tid];
-        p.cum_log_probs[bb]                  = s_cum[tid];
-    }
-    // update_indir_cache_kernel (BaseBeamSearchLayer.cu:30-62): rows that just finished keep their stale entries
-    const size_t plane = (size_t)BK * p.s_max;
-    const int*   src   = p.cache_indir + (size_t)((step - p.max_input_len) & 1) * plane;
-    int*         tgt   = p.cache_indir + (size_t)(1 - ((step - p.max_input_len) & 1)) * plane;
-    const int    nts   = step + 1 < p.s_max ? step + 1 : p.s_max;
-    for (int i = tid; i < K * nts; i += nt) {
-        const int kk = i / nts, t = i % nts;
-        if (!s_fin[kk]) {
-            tgt[((size_t)b * K + kk) * p.s_max + t] = (t == step) ? kk : src[((size_t)b * K + s_parent[kk]) * p.s_max + t];
-        }
-    }
-    __threadfence_block();
-    __syncthreads();
-    if (p.stop_words && tid < K) {  // stop_criteria_kernels.cu:24-83 along the parent chain
-        const int  bb    = b * K + tid;
-        const int* words = p.stop_words + (size_t)b * 2 * p.stop_len;
-        const int* offs  = words + p.stop_len;
-        for (int id = 0; id < p.stop_len; id++) {
-            if (offs[id] < 0) {
-                continue;
-            }
-            const int item_end = offs[id], item_start = id > 0 ? offs[id - 1] : 0, item_size = item_end - item_start;
-            bool      stop = false;
-            if (step + 1 >= item_size) {
-                stop       = true;
-                int parent = tid;
-                for (int t = item_size - 1; t >= 0; t--) {
-                    const int ts  = step - (item_size - 1) + t;
-                    const int tok = p.output_ids[(size_t)ts * BK + b * K + parent];
-                    if (tok != words[item_start + t]) {
-                        stop = false;
-                        break;
-                    }
-                    parent = p.parent_ids[(size_t)ts * BK + b * K + parent];
-                }
-            }
-            if (stop) {
-                p.finished[bb] = 1;
-            }
-        }
-    }
-}
-
-size_t beam_workspace_bytes(int B, int K)
-{
-    return (size_t)B * K * K * (sizeof(float) + sizeof(int)) + (size_t)B * K * 2 * sizeof(int);
-}
-
-void launch_beam_search(const BeamParams& p, hipStream_t s)
-{
-    FTCF_CHECK_ARG(p.K >= 2 && p.K <= BEAM_MAX_K, "beam_width must be in [2, 64]");
-    float* cand_v = reinterpret_cast<float*>(p.ws);
-    int*   cand_i = reinterpret_cast<int*>(cand_v + (size_t)p.B * p.K * p.K);
-    int*   snap   = cand_i + (size_t)p.B * p.K * p.K;
-    size_t smem   = 0;
-    if (p.optional_last_tokens) {
-        smem = std::max(smem, (size_t)((p.V + 31) / 32) * 4);
-    }
-    if (p.repetition_penalty) {
-        smem = std::max(smem, (size_t)p.total_len * 8);
-    }
-    FTCF_CHECK_ARG(smem <= 60 * 1024, "sequence too long for the repetition-penalty staging buffer");
-    hipLaunchKernelGGL(k_beam_rows, dim3(p.B * p.K), dim3(1024), smem, s, p, cand_v, cand_i, snap);
-    hipLaunchKernelGGL(k_beam_batch, dim3(p.B), dim3(256), (size_t)p.K * p.K * 5, s, p, cand_v, cand_i, snap);
-    FTCF_HIP_CHECK(hipGetLastError());
-}
-
-// invokeTileGptInputs (gpt_kernels.cu:632-667)
-__global__ void k_tile_inputs(int* tiled_ids, int* tiled_len, const int* ids, const int* len, int K, int S)
-{
-    const int bb = blockIdx.x, b = bb / K;
-    if (threadIdx.x == 0) {
-        tiled_len[bb] = len[b];
-    }
-    for (int s2 = threadIdx.x; s2 < S; s2 += blockDim.x) {
-        tiled_ids[(size_t)bb * S + s2] = ids[(size_t)b * S + s2];
-    }
-}
-
-void launch_tile_inputs(int* tiled_ids, int* tiled_len, const int* ids, const int* len, int B, int K, int S, hipStream_t s)
-{
-    hipLaunchKernelGGL(k_tile_inputs, dim3(B * K), dim3(256), 0, s, tiled_ids, tiled_len, ids, len, K, S);
-    FTCF_HIP_CHECK(hipGetLastError());
-}
-
-// gatherTree with parents (decoding_kernels.cu:452-583) + the [time, batch*beam] -> [batch, beam, time] transpose
-__global__ void k_gather_tree_beam(int* output_ids, int* sequence_lengths, const int* step_ids, const int* parent_ids,
-                                   const int* seq_len, const int* input_lengths, int B, int K, int max_input_len,
-                                   int total, int end_id)
-{
-    const int bb = blockIdx.x, b = bb / K, BK = B * K;
-    if (threadIdx.x != 0) {
-        return;
-    }
-    int max_len = -1;
-    for (int j = 0; j < K; j++) {
-        const int tmp_len = seq_len[b * K + j] + 1;  // max_sequence_length_final_step = 1
-        max_len           = tmp_len > max_len ? tmp_len : max_len;
-    }
-    sequence_lengths[bb] = seq_len[bb] + 1;
-    const int msl        = max_len < total ? max_len : total;
-    int*      beams      = output_ids + (size_t)bb * total;
-    for (int t = 0; t < total; t++) {
-        beams[t] = 0;
-    }
-    if (msl <= 0) {
-        return;
-    }
-    const int in_len  = input_lengths[bb];
-    const int pad_off = max_input_len - in_len;
-    beams[msl - 1 - pad_off] = step_ids[(size_t)(msl - 1) * BK + bb];
-    int parent               = parent_ids[(size_t)(msl - 1) * BK + bb] % K;
-    for (int level = msl - 2; level >= 0; level--) {
-        if (level >= in_len && level < max_input_len) {
-            continue;
-        }
-        const int tgt = level >= max_input_len ? level - pad_off : level;
-        beams[tgt]    = step_ids[(size_t)level * BK + b * K + parent];
-        parent        = parent_ids[(size_t)level * BK + b * K + parent] % K;
-    }
-    for (int index = max_len - pad_off; index < total; index++) {
-        beams[index] = end_id;
-    }
-    bool fin = false;
-    for (int t = max_input_len; t < msl; t++) {
-        if (fin) {
-            beams[t] = end_id;
-        }
-        else if (beams[t] == end_id) {
-            fin = true;
-        }
-    }
-}
-
-void launch_gather_tree_beam(int* output_ids, int* sequence_lengths, const int* step_ids, const int* parent_ids,
-                             const int* seq_len, const int* input_lengths, int B, int K, int max_input_len, int total,
-                             int end_id, hipStream_t s)
-{
-    hipLaunchKernelGGL(k_gather_tree_beam, dim3(B * K), dim3(64), 0, s, output_ids, sequence_lengths, step_ids, parent_ids,
-                       seq_len, input_lengths, B, K, max_input_len, total, end_id);
-    FTCF_HIP_CHECK(hipGetLastError());
-}
 
 }  // namespace ftcf

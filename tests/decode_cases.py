@@ -1,4 +1,5 @@
-"""Crafted inputs of ONE dynamic-decode step / ONE beam-search step: the tie, mask and size edges of kernels_sampling.hip.
+"""Crafted inputs of ONE dynamic-decode step / ONE beam-search step: the tie, mask and size edges of kernels_sampling.hip
+and kernels_beam.hip.
 
 Shared by test_decode_step_reference.py (CPU: oracle against tests/decode_reference.py) and test_gpu_decode_step.py (GPU: the
 kernels against both).  Every logit family keeps different values well apart (a grid of 2**-10 or coarser) or exactly equal,

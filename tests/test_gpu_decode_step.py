@@ -1,4 +1,4 @@
-"""-m gpu: ONE dynamic-decode step and ONE beam-search step of kernels_sampling.hip on crafted logits (include/ftcf.h
+"""-m gpu: ONE dynamic-decode step of kernels_sampling.hip and ONE beam-search step of kernels_beam.hip on crafted logits (include/ftcf.h
 ftcf_dynamic_decode_step, ftcf_beam_search_step), against the CPU oracle and the float64 statement of the layer
 (tests/decode_reference.py), through every form a case is eligible for: the general four launches, k_topk_decode,
 k_greedy_decode.  The cases (tests/decode_cases.py) are the tie, mask and size edges a random model's logits never reach;

@@ -1,6 +1,7 @@
-"""Host checks of the per-token log-probability feature: the new fused LM-head kernel and the sampling translation unit that
-stores output_log_probs cross-compile for gfx950 without spills or scratch (the method of tests/test_kernel_resources.py), the
-fused greedy LM head keeps its register budget, and the ctypes ForwardArgs lays the two new fields out as the C header does."""
+"""Host checks of the per-token log-probability feature: the new fused LM-head kernel, the sampling translation unit that
+stores output_log_probs and the beam-search translation unit split off from it cross-compile for gfx950 without spills or
+scratch (the method of tests/test_kernel_resources.py), the fused greedy LM head keeps its register budget, and the ctypes
+ForwardArgs lays the two new fields out as the C header does."""
 import os
 import shutil
 import subprocess
@@ -23,7 +24,10 @@ def test_log_prob_kernel_compiles_without_spills(tmp_path):
 @pytest.mark.skipif(HIPCC is None, reason="no hipcc")
 def test_sampling_kernels_compile_without_new_spills_and_lm_head_greedy_keeps_its_budget(tmp_path):
     kernels = _resource_usage("kernels_sampling.hip", [], tmp_path)
-    for name in ("k_sample", "k_greedy_decode", "k_topk_decode", "k_lm_head_greedy"):
+    # (beam search and the gather tree were part of that translation unit and are held to the same: no spill, no scratch)
+    kernels.update(_resource_usage("kernels_beam.hip", [], tmp_path))
+    for name in ("k_sample", "k_greedy_decode", "k_topk_decode", "k_lm_head_greedy", "k_decode_prep", "k_topk_stage1", "k_beam_rows",
+                 "k_beam_batch", "k_tile_inputs", "k_gather_tree_beam"):
         assert any(name in k for k in kernels), name
     for k, r in kernels.items():
         if "k_lm_head_greedy" in k:
