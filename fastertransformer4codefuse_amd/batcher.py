@@ -113,9 +113,22 @@ class ContinuousBatcher:
         self._cb = capi.BATCHER_TOKEN_CALLBACK(lambda _user, rid, tok, fin: fn(int(rid), int(tok), bool(fin)))
         capi.check(capi.lib().ftcf_batcher_set_token_callback(self._h, self._cb, None))
 
-    def step(self):
-        """One scheduler iteration; returns [(request_id, token, finished), ...] in production order."""
+    def step(self, top_logprobs=None):
+        """One scheduler iteration; returns [(request_id, token, finished), ...] in production order.
+
+        top_logprobs = N in 1..20 (ftcf_batcher_step_top): the events are (request_id, token, finished, log_prob, top_ids,
+        top_log_probs) -- log_prob as step_ex returns it, then the N most likely tokens of the distribution the token was
+        drawn from, best first, and their log-probabilities (GptNeoXOp.forward's top_logprobs).  A beam request's event and
+        events of admissions made by a call without it carry ids of -1 and NaN."""
         n = C.c_int(0)
+        if top_logprobs:
+            N, cap = int(top_logprobs), 2 * self.max_batch
+            if not 1 <= N <= 20:
+                raise ValueError("top_logprobs must be in 1..20")
+            ids, lps = (C.c_int * (cap * N))(), (C.c_float * (cap * N))()
+            capi.check(capi.lib().ftcf_batcher_step_top(self._h, self._ids, self._tok, self._fin, self._lp, N, ids, lps, cap, C.byref(n)))
+            return [(int(self._ids[i]), int(self._tok[i]), bool(self._fin[i]), float(self._lp[i]), list(ids[i * N:(i + 1) * N]),
+                     list(lps[i * N:(i + 1) * N])) for i in range(n.value)]
         capi.check(capi.lib().ftcf_batcher_step(self._h, self._ids, self._tok, self._fin, 2 * self.max_batch, C.byref(n)))
         return [(int(self._ids[i]), int(self._tok[i]), bool(self._fin[i])) for i in range(n.value)]
 

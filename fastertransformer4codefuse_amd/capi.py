@@ -53,7 +53,9 @@ class ForwardArgs(C.Structure):
         ("callback", TOKEN_CALLBACK), ("callback_user", C.c_void_p),
         ("output_ids", C.c_void_p), ("sequence_lengths", C.c_void_p), ("cum_log_probs", C.c_void_p),
         ("debug_logits", C.c_void_p),
-        ("output_log_probs", C.c_void_p), ("context_log_probs", C.c_void_p),
+        ("output_log_probs", C.c_void_p),
+        ("top_logprobs", C.c_int), ("top_logprob_ids", C.c_void_p), ("top_logprob_values", C.c_void_p),
+        ("context_log_probs", C.c_void_p),
         ("speculative_tokens", C.c_int), ("speculative_ngram", C.c_int), ("draft_ids", C.c_void_p)]
 
 
@@ -80,7 +82,8 @@ class DynamicDecodeArgs(C.Structure):  # ftcf_dynamic_decode_args
         ("all_finished", C.POINTER(C.c_int)), ("next_step", C.POINTER(C.c_int)), ("form", C.POINTER(C.c_int))] + [
         (n, C.c_int) for n in (
             "n_top_k", "n_top_p", "n_temperature", "n_repetition_penalty", "n_min_length", "n_random_seed", "stop_len",
-            "optional_count", "B", "V", "step", "max_input_len", "total_len", "end_id", "return_cum_log_probs", "finish")]
+            "optional_count", "B", "V", "step", "max_input_len", "total_len", "end_id", "return_cum_log_probs", "finish")] + [
+        ("top_logprobs", C.c_int), ("top_ids", C.c_void_p), ("top_log_probs", C.c_void_p)]
 
 
 class BeamSearchArgs(C.Structure):  # ftcf_beam_search_args
@@ -121,7 +124,7 @@ EXPORTED = [
     "ftcf_comm_allgather", "ftcf_gptneox_create", "ftcf_gptneox_forward", "ftcf_gptneox_begin", "ftcf_gptneox_step", "ftcf_gptneox_finish",
     "ftcf_gptneox_get_stats",
     "ftcf_gptneox_set_profiling", "ftcf_gptneox_destroy",
-    "ftcf_batcher_create", "ftcf_batcher_create_ex", "ftcf_batcher_prefix_stats", "ftcf_batcher_clear_prefix_cache", "ftcf_batcher_submit", "ftcf_batcher_submit_ex", "ftcf_batcher_submit_beam", "ftcf_batcher_submit_beam_ex", "ftcf_batcher_beam_result", "ftcf_batcher_step", "ftcf_batcher_step_ex", "ftcf_batcher_set_token_callback", "ftcf_batcher_status", "ftcf_batcher_cancel", "ftcf_batcher_destroy"]
+    "ftcf_batcher_create", "ftcf_batcher_create_ex", "ftcf_batcher_prefix_stats", "ftcf_batcher_clear_prefix_cache", "ftcf_batcher_submit", "ftcf_batcher_submit_ex", "ftcf_batcher_submit_beam", "ftcf_batcher_submit_beam_ex", "ftcf_batcher_beam_result", "ftcf_batcher_step", "ftcf_batcher_step_ex", "ftcf_batcher_step_top", "ftcf_batcher_set_token_callback", "ftcf_batcher_status", "ftcf_batcher_cancel", "ftcf_batcher_destroy"]
 
 _lib = None
 

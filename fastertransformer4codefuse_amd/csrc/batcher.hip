@@ -175,6 +175,9 @@ struct ftcf_batcher {
     void*        beam_ws = nullptr;
     float *      d_ptopk = nullptr, *d_ptopp = nullptr, *d_temp = nullptr, *d_cum = nullptr, *d_rep = nullptr;
     float *      d_olp = nullptr, *d_polp = nullptr;  // log-probability of each slot's token of a decode step / of an admission's first
+    // ftcf_batcher_step_top: the same for the top_n (<= 20) alternatives, [slot][top_n] {id, log-probability}
+    int *        d_top_ids = nullptr, *d_ptop_ids = nullptr;
+    float *      d_top_lp = nullptr, *d_ptop_lp = nullptr;
     int*         d_hist = nullptr;  // [max_len + 1][max_batch] time-major token history of the slots (repetition penalty)
     int *        d_sw = nullptr;    // admission: stop words of the ragged batch, the reference's [n][2][Lw] layout
     uint64_t *   d_seed = nullptr, *d_draws = nullptr;
@@ -297,6 +300,10 @@ struct ftcf_batcher {
         d_cum = dmalloc<float>(B);
         d_olp = dmalloc<float>(B);
         d_polp = dmalloc<float>(B);
+        d_top_ids = dmalloc<int>(B * TOP_LOGPROBS_MAX);
+        d_ptop_ids = dmalloc<int>(B * TOP_LOGPROBS_MAX);
+        d_top_lp = dmalloc<float>(B * TOP_LOGPROBS_MAX);
+        d_ptop_lp = dmalloc<float>(B * TOP_LOGPROBS_MAX);
         d_rep = dmalloc<float>(B);
         d_hist = dmalloc<int>((size_t)(max_len + 2) * B);
         d_sw = dmalloc<int>(B * 2 * STOP_LW);
@@ -495,8 +502,12 @@ struct ftcf_batcher {
         long  id;
         int   token, finished;
         float log_prob = NAN;  // ftcf_batcher_step_ex: the token's log-probability (NaN: a beam request's event)
+        // ftcf_batcher_step_top: the step's top_n {id, log-probability} pairs (empty: none were taken -- reported as (-1, NaN))
+        std::vector<int>   top_ids;
+        std::vector<float> top_lp;
     };
     bool want_log_probs = false;  // inside ftcf_batcher_step_ex: admissions compute their first token's log-probability too
+    int  want_top = 0;            // inside ftcf_batcher_step_top: its top_n
     std::vector<Event>* hook_ev = nullptr;  // where the decode steps inside a chunked admission put their events
     std::deque<Event>   outbox;             // events of an iteration that did not fit the caller's arrays
     ftcf_token_callback_fn on_token = nullptr;  // called for every event the moment it exists (inside step())
@@ -621,6 +632,11 @@ struct ftcf_batcher {
         if (want_log_probs) {  // (the engine then runs the soft-max statistics as return_cum_log_probs = 1 does: the decode steps' setting)
             a.output_log_probs = d_polp;
         }
+        if (want_top > 0) {
+            a.top_logprobs       = want_top;
+            a.top_logprob_ids    = d_ptop_ids;  // [n, 1, 1, top_n]
+            a.top_logprob_values = d_ptop_lp;
+        }
         const int hit_tokens = hit ? (int)hit->size() * P : 0;
         if (hit_tokens > 0) {
             // the prompt phase starts at the first uncached token; first the cached pages go to cache row 0 (the engine's cache
@@ -653,6 +669,12 @@ struct ftcf_batcher {
         std::vector<float> first_lp((size_t)n, NAN);
         if (want_log_probs) {
             FTCF_HIP_CHECK(hipMemcpy(first_lp.data(), d_polp, (size_t)n * 4, hipMemcpyDeviceToHost));
+        }
+        std::vector<int>   first_top_ids((size_t)n * want_top);
+        std::vector<float> first_top_lp((size_t)n * want_top);
+        if (want_top > 0) {
+            FTCF_HIP_CHECK(hipMemcpy(first_top_ids.data(), d_ptop_ids, first_top_ids.size() * 4, hipMemcpyDeviceToHost));
+            FTCF_HIP_CHECK(hipMemcpy(first_top_lp.data(), d_ptop_lp, first_top_lp.size() * 4, hipMemcpyDeviceToHost));
         }
         const size_t row_kv = (size_t)e->nhl * (S + 1) * e->dh;  // one row of one layer of the engine's cache
         for (int i = 0; i < n; i++) {
@@ -701,6 +723,8 @@ struct ftcf_batcher {
             s.max_new = r.max_new;
             const int done = (first == e->cfg.end_id || s.generated >= s.max_new || hits_stop_word(s)) ? 1 : 0;
             ev.push_back(Event{r.id, first, done, first_lp[i]});  // (the token callback fires when the admission has succeeded: step())
+            ev.back().top_ids.assign(first_top_ids.begin() + (size_t)i * want_top, first_top_ids.begin() + (size_t)(i + 1) * want_top);
+            ev.back().top_lp.assign(first_top_lp.begin() + (size_t)i * want_top, first_top_lp.begin() + (size_t)(i + 1) * want_top);
             if (done) {
                 const uint8_t one8 = 1;
                 FTCF_HIP_CHECK(hipMemcpy(d_fin + si, &one8, 1, hipMemcpyHostToDevice));
@@ -1250,6 +1274,12 @@ struct ftcf_batcher {
         sp.seq_len = d_len;     // + 1 per sampled token: the slot's length
         sp.cum_log_probs = d_cum;
         sp.output_log_probs = d_olp;  // (row_len: one value per slot, written where cum_log_probs is)
+        const int top_n = want_top;
+        if (top_n > 0) {  // (row_len: one [B, top_n] row; only the slots that sample are written and read)
+            sp.top_logprobs       = top_n;
+            sp.top_logprob_ids    = d_top_ids;
+            sp.top_logprob_values = d_top_lp;
+        }
         sp.pad_count = d_zero;
         sp.state = d_state;     // step stays 0
         sp.ws = samp_ws;
@@ -1272,6 +1302,12 @@ struct ftcf_batcher {
         int                  gemm_err = 0;
         FTCF_HIP_CHECK(hipMemcpyAsync(tok.data(), d_tok, (size_t)B * 4, hipMemcpyDeviceToHost, st));
         FTCF_HIP_CHECK(hipMemcpyAsync(lp.data(), d_olp, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+        std::vector<int>   top_ids((size_t)B * top_n);
+        std::vector<float> top_lp((size_t)B * top_n);
+        if (top_n > 0) {
+            FTCF_HIP_CHECK(hipMemcpyAsync(top_ids.data(), d_top_ids, top_ids.size() * 4, hipMemcpyDeviceToHost, st));
+            FTCF_HIP_CHECK(hipMemcpyAsync(top_lp.data(), d_top_lp, top_lp.size() * 4, hipMemcpyDeviceToHost, st));
+        }
         FTCF_HIP_CHECK(hipMemcpyAsync(fin.data(), d_fin, (size_t)B, hipMemcpyDeviceToHost, st));
         if (smallm_ws) {  // sticky flag of the burst GEMMs' in-launch split-K reduction (the engine's finish() reads its own)
             FTCF_HIP_CHECK(hipMemcpyAsync(&gemm_err, reinterpret_cast<char*>(smallm_ws) + smallm_partial, sizeof(int),
@@ -1324,7 +1360,10 @@ struct ftcf_batcher {
             s.generated += 1;
             s.hist.push_back(tok[si]);
             const int done = (fin[si] || s.generated >= s.max_new || hits_stop_word(s)) ? 1 : 0;
-            emit(ev, Event{s.id, tok[si], done, lp[si]});
+            Event x{s.id, tok[si], done, lp[si]};
+            x.top_ids.assign(top_ids.begin() + (size_t)si * top_n, top_ids.begin() + (size_t)(si + 1) * top_n);
+            x.top_lp.assign(top_lp.begin() + (size_t)si * top_n, top_lp.begin() + (size_t)(si + 1) * top_n);
+            emit(ev, x);
             if (done) {
                 if (!fin[si]) {
                     const uint8_t one8 = 1;
@@ -1747,23 +1786,29 @@ extern "C" int ftcf_batcher_beam_result(ftcf_batcher_t b, long request_id, int* 
         b->beam_results.erase(it);
     });
 }
-static int batcher_step(ftcf_batcher_t b, long* request_ids, int* tokens, int* finished, float* log_probs, int capacity, int* n_events)
+static int batcher_step(ftcf_batcher_t b, long* request_ids, int* tokens, int* finished, float* log_probs, int capacity, int* n_events,
+                        int top_n = 0, int* top_ids = nullptr, float* top_log_probs = nullptr)
 {
     return guarded([&] {
         FTCF_CHECK_ARG(b && request_ids && tokens && finished && n_events, "NULL argument");
+        FTCF_CHECK_ARG(top_n >= 0 && top_n <= TOP_LOGPROBS_MAX, "top_n must be in [1, 20]");
+        FTCF_CHECK_ARG(top_n == 0 || (top_ids && top_log_probs), "NULL argument");
         FTCF_CHECK_ARG(capacity >= 2 * b->max_batch, "event arrays must hold 2 * max_batch entries");
         if (b->outbox.empty()) {  // (else: the rest of the previous iteration's events first)
             std::vector<ftcf_batcher::Event> ev;
             b->want_log_probs = log_probs != nullptr;
+            b->want_top       = top_n;
             try {
                 b->step(ev);
             }
             catch (...) {
                 b->want_log_probs = false;
+                b->want_top       = 0;
                 b->outbox.insert(b->outbox.end(), ev.begin(), ev.end());  // tokens of decode steps that did run are not lost
                 throw;
             }
             b->want_log_probs = false;
+            b->want_top       = 0;
             b->outbox.insert(b->outbox.end(), ev.begin(), ev.end());
         }
         int n = 0;
@@ -1773,6 +1818,14 @@ static int batcher_step(ftcf_batcher_t b, long* request_ids, int* tokens, int* f
             finished[n]    = b->outbox.front().finished;
             if (log_probs) {
                 log_probs[n] = b->outbox.front().log_prob;
+            }
+            if (top_n > 0) {  // (pairs taken with another top_n, or not at all: none)
+                const ftcf_batcher::Event& x  = b->outbox.front();
+                const bool                 ok = (int)x.top_ids.size() == top_n;
+                for (int j = 0; j < top_n; j++) {
+                    top_ids[(size_t)n * top_n + j]       = ok ? x.top_ids[j] : -1;
+                    top_log_probs[(size_t)n * top_n + j] = ok ? x.top_lp[j] : NAN;
+                }
             }
             b->outbox.pop_front();
         }
@@ -1790,6 +1843,14 @@ extern "C" int ftcf_batcher_step_ex(ftcf_batcher_t b, long* request_ids, int* to
         return guarded([&] { FTCF_CHECK_ARG(false, "NULL argument"); });
     }
     return batcher_step(b, request_ids, tokens, finished, log_probs, capacity, n_events);
+}
+extern "C" int ftcf_batcher_step_top(ftcf_batcher_t b, long* request_ids, int* tokens, int* finished, float* log_probs, int top_n,
+                                     int* top_ids, float* top_log_probs, int capacity, int* n_events)
+{
+    if (top_n < 1 || !top_ids || !top_log_probs) {
+        return guarded([&] { FTCF_CHECK_ARG(false, "top_n must be in [1, 20] with both arrays"); });
+    }
+    return batcher_step(b, request_ids, tokens, finished, log_probs, capacity, n_events, top_n, top_ids, top_log_probs);
 }
 extern "C" int ftcf_batcher_set_token_callback(ftcf_batcher_t b, ftcf_token_callback_fn fn, void* user)
 {

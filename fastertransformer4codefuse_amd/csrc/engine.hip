@@ -650,6 +650,9 @@ extern "C" int ftcf_dynamic_decode_step(const ftcf_dynamic_decode_args* a, void*
         FTCF_CHECK_ARG(!a->output_log_probs || a->row_len || a->step < a->total_len, "output_log_probs has no row for step == total_len");
         FTCF_CHECK_ARG(!a->stop_words || a->stop_len >= 1, "stop_words needs stop_len >= 1");
         FTCF_CHECK_ARG(!a->optional_last_tokens || a->optional_count >= 1, "optional_last_tokens needs optional_count >= 1");
+        FTCF_CHECK_ARG(a->top_logprobs >= 0 && a->top_logprobs <= TOP_LOGPROBS_MAX, "top_logprobs must be in [0, 20]");
+        FTCF_CHECK_ARG(a->top_logprobs == 0 || (a->top_ids && a->top_log_probs), "top_logprobs needs top_ids and top_log_probs");
+        FTCF_CHECK_ARG(a->top_logprobs == 0 || a->row_len || a->step < a->total_len, "top_logprobs has no row for step == total_len");
         auto top_k = broadcast_arg<int>(a->top_k, a->n_top_k, B, 0, "top_k");
         auto top_p = broadcast_arg<float>(a->top_p, a->n_top_p, B, 0.f, "top_p");
         auto temp  = broadcast_arg<float>(a->temperature, a->n_temperature, B, 1.f, "temperature");
@@ -680,12 +683,17 @@ extern "C" int ftcf_dynamic_decode_step(const ftcf_dynamic_decode_args* a, void*
         sp.stop_len             = a->stop_len;
         sp.optional_last_tokens = a->optional_last_tokens;
         sp.optional_count       = a->optional_count;
-        sp.return_cum_log_probs = (a->return_cum_log_probs || a->output_log_probs) ? 1 : 0;
+        sp.return_cum_log_probs = (a->return_cum_log_probs || a->output_log_probs || a->top_logprobs > 0) ? 1 : 0;
         sp.output_ids           = a->output_ids;
         sp.finished             = a->finished;
         sp.seq_len              = a->seq_len;
         sp.cum_log_probs        = a->cum_log_probs;
         sp.output_log_probs     = a->output_log_probs;
+        if (a->top_logprobs > 0) {
+            sp.top_logprobs       = a->top_logprobs;
+            sp.top_logprob_ids    = a->top_ids;
+            sp.top_logprob_values = a->top_log_probs;
+        }
         sp.row_len              = a->row_len;
         sp.pad_count            = a->pad_count;
         if (!sp.pad_count) {
@@ -822,6 +830,11 @@ void ftcf_gptneox::begin(const ftcf_forward_args& a)
                    "a prompt phase from a token offset needs one fp16 / int8 sequence without beams, longer than the offset");
     FTCF_CHECK_ARG(!a.output_log_probs || K == 1,
                    "output_log_probs is not supported with beam_width > 1 (the values would have to follow the beams' parents)");
+    FTCF_CHECK_ARG(a.top_logprobs >= 0 && a.top_logprobs <= TOP_LOGPROBS_MAX, "top_logprobs must be in [0, 20]");
+    FTCF_CHECK_ARG(a.top_logprobs == 0 || (a.top_logprob_ids && a.top_logprob_values),
+                   "top_logprobs needs top_logprob_ids and top_logprob_values");
+    FTCF_CHECK_ARG(a.top_logprobs == 0 || K == 1,
+                   "top_logprobs is not supported with beam_width > 1 (the pairs would have to follow the beams' parents)");
     FTCF_CHECK_ARG(!a.context_log_probs || !fp32, "context_log_probs needs an fp16 / int8 engine");
     FTCF_CHECK_ARG(!a.context_log_probs || prefill_begin == 0, "context_log_probs needs the whole prompt phase");
     FTCF_HIP_CHECK(hipSetDevice(cfg.device));
@@ -864,7 +877,7 @@ void ftcf_gptneox::begin(const ftcf_forward_args& a)
     FTCF_CHECK_ARG(a.speculative_ngram >= 0 && a.speculative_ngram <= 8, "speculative_ngram must be in [0, 8]");
     bool spec = a.speculative_tokens > 0 && batch == 1 && K == 1 && !fp32 && tpn == 1 && cfg.use_gptj_residual && prefill_begin == 0
                 && verify_attention_supported(nhl, dh, total) && H % 64 == 0 && hl % 64 == 0 && il % 64 == 0 && !a.callback && !a.return_cum_log_probs
-                && !a.output_log_probs && !a.debug_logits && !a.stop_words_list && !a.optional_last_tokens && a.n_min_length == 0
+                && !a.output_log_probs && a.top_logprobs == 0 && !a.debug_logits && !a.stop_words_list && !a.optional_last_tokens && a.n_min_length == 0
                 && (a.n_top_k == 0 || (a.top_k && a.top_k[0] <= 1)) && (a.n_top_p == 0 || (a.top_p && a.top_p[0] == 0.f))
                 && (a.n_repetition_penalty == 0 || (a.repetition_penalty && a.repetition_penalty[0] == 1.f));
     if (spec) {  // (the token history must be dense from position 0: a prompt as long as its row)
@@ -1032,6 +1045,23 @@ void ftcf_gptneox::begin(const ftcf_forward_args& a)
     if (a.output_log_probs) {
         FTCF_HIP_CHECK(hipMemsetAsync(olp, 0, (size_t)out_len * B * 4, stream));  // (steps after a row finished hold 0)
     }
+    if (a.top_logprobs > 0) {  // (steps after a row finished keep the pattern the buffers start with)
+        const size_t pairs = (size_t)out_len * B * a.top_logprobs;
+        if (pairs > tlp_pairs) {
+            comm_stream_sync(cfg.comm, stream);
+            if (tlp_ids) {
+                FTCF_HIP_CHECK(hipFree(tlp_ids));
+                FTCF_HIP_CHECK(hipFree(tlp_values));
+                tlp_ids    = nullptr;
+                tlp_values = nullptr;
+                tlp_pairs  = 0;
+            }
+            FTCF_HIP_CHECK(hipMalloc((void**)&tlp_ids, pairs * sizeof(int)));
+            FTCF_HIP_CHECK(hipMalloc((void**)&tlp_values, pairs * sizeof(float)));
+            tlp_pairs = pairs;
+        }
+        launch_fill_top_logprobs(tlp_ids, tlp_values, pairs, stream);
+    }
     FTCF_HIP_CHECK(hipEventRecord(e1, stream));
 
     SamplingParams sp{};
@@ -1056,12 +1086,17 @@ void ftcf_gptneox::begin(const ftcf_forward_args& a)
     sp.optional_last_tokens = a.optional_last_tokens;
     sp.optional_count = a.optional_last_tokens_count;
     // (output_log_probs needs the soft-max statistics: sampling_topk_kernels.cu:273 switches them on for either output)
-    sp.return_cum_log_probs = (a.return_cum_log_probs || a.output_log_probs) ? 1 : 0;
+    sp.return_cum_log_probs = (a.return_cum_log_probs || a.output_log_probs || a.top_logprobs > 0) ? 1 : 0;
     sp.output_ids = step_ids;
     sp.finished = finished;
     sp.seq_len = seq_len;
     sp.cum_log_probs = cum;
     sp.output_log_probs = a.output_log_probs ? olp : nullptr;
+    if (a.top_logprobs > 0) {  // (the step then takes the general form: kernels_sampling.hip dynamic_decode_is_*_fused)
+        sp.top_logprobs       = a.top_logprobs;
+        sp.top_logprob_ids    = tlp_ids;
+        sp.top_logprob_values = tlp_values;
+    }
     sp.pad_count = pad_count;
     sp.state = state;
     sp.h_flags = h_flags;
@@ -1465,6 +1500,10 @@ void ftcf_gptneox::finish()
     }
     if (a.output_log_probs) {
         launch_transpose_log_probs(a.output_log_probs, olp, ses.total - ses.S, ses.B, stream);
+    }
+    if (a.top_logprobs > 0) {
+        launch_transpose_top_logprobs(a.top_logprob_ids, a.top_logprob_values, tlp_ids, tlp_values, ses.total - ses.S, ses.B,
+                                      a.top_logprobs, stream);
     }
     int ps_error = 0, smallm_error = 0;
     if (pplan.ok) {

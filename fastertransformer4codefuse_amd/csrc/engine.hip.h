@@ -101,6 +101,10 @@ struct ftcf_gptneox {
     int *        seq_len = nullptr, *pad_count = nullptr, *step_ids = nullptr, *d_top_k = nullptr,
         *d_min_length = nullptr;
     float *   olp = nullptr;  // output_log_probs of the token loop, time-major [output_len, B]
+    // top_logprobs of the token loop, time-major [output_len, B, N]: allocated by the first request that asks, grown when needed
+    int*      tlp_ids = nullptr;
+    float*    tlp_values = nullptr;
+    size_t    tlp_pairs = 0;
     int*      ctx_tgt = nullptr;  // context_log_probs scratch: targets [B*S] ...
     float*    ctx_lp  = nullptr;  // ... and the log-probability of each hidden row's target [B*S]
     float *   cum = nullptr, *d_p_topk = nullptr, *d_p_topp = nullptr, *d_temp = nullptr, *d_rep = nullptr;
@@ -165,6 +169,10 @@ struct ftcf_gptneox {
         }
         if (tp_scratch) {
             (void)hipFree(tp_scratch);
+        }
+        if (tlp_ids) {
+            (void)hipFree(tlp_ids);
+            (void)hipFree(tlp_values);
         }
         if (stream) {
             (void)hipStreamDestroy(stream);

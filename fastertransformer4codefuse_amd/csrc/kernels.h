@@ -372,6 +372,11 @@ void   launch_context_log_probs(float* out, const f16* hidden_nrm, const f16* W_
                                 float* lp, int B, int S, int V, int H, hipStream_t s);
 // output_log_probs: the time-major [T, B] buffer of the token loop -> [B, T]
 void   launch_transpose_log_probs(float* out, const float* in, int T, int B, hipStream_t s);
+// top_logprobs: `pairs` {id, log-probability} pairs <- the pattern of a row that had finished before the step, (-1, 0.0f); the
+// time-major buffers of the token loop [T, B, N] -> [B, T, N]
+void   launch_fill_top_logprobs(int* ids, float* values, size_t pairs, hipStream_t s);
+void   launch_transpose_top_logprobs(int* out_ids, float* out_values, const int* ids, const float* values, int T, int B, int N,
+                                     hipStream_t s);
 
 // ---- dynamic decode : kernels_sampling.hip ----
 struct DecodeState {  // device resident, one per engine
@@ -420,7 +425,14 @@ struct SamplingParams {
     const f16*      wte;        // [V, H]
     float*          rot_table;  // [B, rot / 2, 2]
     int             H, rot;
+    // the top_logprobs (1..TOP_LOGPROBS_MAX) best {id, log-probability} pairs of every live row's processed distribution (the one
+    // output_log_probs is defined under), time-major [total_len - max_input_len, B, top_logprobs] at row (step - max_input_len)
+    // (row 0 with row_len), or 0 / NULL.  Needs return_cum_log_probs; the step then takes the general form.
+    int             top_logprobs;
+    int*            top_logprob_ids;
+    float*          top_logprob_values;
 };
+constexpr int TOP_LOGPROBS_MAX = 20;
 // does launch_dynamic_decode(p, s, finish) take the one-launch path of an all-greedy batch (k_greedy_decode)?
 bool dynamic_decode_is_fused(const SamplingParams& p, bool finish);
 // which form launch_dynamic_decode(p, s, finish) takes: 0 the general four launches, 1 k_topk_decode, 2 k_greedy_decode

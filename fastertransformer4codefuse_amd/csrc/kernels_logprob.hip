@@ -22,6 +22,7 @@
 #include "ftcf_common.h"
 #include "kernels.h"
 
+#include <algorithm>
 #include <map>
 #include <mutex>
 
@@ -295,6 +296,47 @@ void launch_context_log_probs(float* out, const f16* hidden_nrm, const f16* W_nk
 void launch_transpose_log_probs(float* out, const float* in, int T, int B, hipStream_t s)
 {
     hipLaunchKernelGGL(k_transpose_log_probs, dim3((B * T + 255) / 256), dim3(256), 0, s, out, in, T, B);
+    FTCF_HIP_CHECK(hipGetLastError());
+}
+
+// top_logprobs: the pairs of a row that had finished before the step
+__global__ void k_fill_top_logprobs(int* ids, float* values, size_t pairs)
+{
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < pairs; i += (size_t)gridDim.x * blockDim.x) {
+        ids[i]    = -1;
+        values[i] = 0.f;
+    }
+}
+// [T, B, N] time-major -> [B, T, N]
+__global__ void k_transpose_top_logprobs(int* out_ids, float* out_values, const int* ids, const float* values, int T, int B, int N)
+{
+    const size_t total = (size_t)B * T * N;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int    j   = (int)(i % N);
+        const size_t bt  = i / N;
+        const int    b   = (int)(bt / T), t = (int)(bt % T);
+        const size_t src = ((size_t)t * B + b) * N + j;
+        out_ids[i]    = ids[src];
+        out_values[i] = values[src];
+    }
+}
+
+void launch_fill_top_logprobs(int* ids, float* values, size_t pairs, hipStream_t s)
+{
+    if (pairs == 0) {
+        return;
+    }
+    const int grid = (int)std::min<size_t>((pairs + 255) / 256, 2048);
+    hipLaunchKernelGGL(k_fill_top_logprobs, dim3(grid), dim3(256), 0, s, ids, values, pairs);
+    FTCF_HIP_CHECK(hipGetLastError());
+}
+
+void launch_transpose_top_logprobs(int* out_ids, float* out_values, const int* ids, const float* values, int T, int B, int N,
+                                   hipStream_t s)
+{
+    const size_t total = (size_t)B * T * N;
+    const int    grid  = (int)std::min<size_t>((total + 255) / 256, 2048);
+    hipLaunchKernelGGL(k_transpose_top_logprobs, dim3(grid), dim3(256), 0, s, out_ids, out_values, ids, values, T, B, N);
     FTCF_HIP_CHECK(hipGetLastError());
 }
 

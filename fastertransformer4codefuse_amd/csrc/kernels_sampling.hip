@@ -960,6 +960,153 @@ __global__ __launch_bounds__(256) void k_sample(const SamplingParams p, float* c
     }
 }
 
+// ---- top_logprobs: the N best {id, log-probability} pairs of every live row (two launches between steps 1 and 2) ---------------
+// The row k_decode_prep leaves is only READ: logits after the optional-token mask, temperature, repetition penalty and the
+// min-length mask -- or, for a row of the top-p layer, the probabilities of its soft-max.  Stage A: 32 slices per row (the geometry
+// of k_topk_decode) keep their logits in registers and put out the slice's N best as a set (slice_select) with the slice's {max,
+// sum of exponentials}; stage B: one workgroup per row builds the row's soft-max from the 32 statistics (the order and the + 1e-6f
+// of topk_draw), sorts the 32 x N candidates best first (`better`: value descending, id ascending) and stores the first N.
+// MASKED entries -- a logit of -inf or <= -FLT_MAX, a probability of 0 -- read as -inf from the load on: `better` then puts them
+// behind every other entry and orders them by id, and their log-probability is -inf.  No atomics on floats, no dependence on the
+// order workgroups run in: two runs are bit-identical.
+constexpr int TLP_SLICES = 32;
+constexpr int TLP_MAXE   = 16;  // logits per thread: V <= 32 * 256 * 16 = 131072
+
+__global__ __launch_bounds__(256) void k_top_logprobs_slices(const SamplingParams p, float* cand_v, int* cand_i, float* stats)
+{
+    if (p.state->all_finished) {
+        return;  // a token of a multi-token graph behind the request's last one (engine.hip step()): nothing to do
+    }
+    __shared__ float redv[4];
+    __shared__ int   redi[4];
+    __shared__ int   hist[256];
+    __shared__ int   hist8[8][257];
+    __shared__ int   s_sel[4];
+    const int        b = blockIdx.y, blk = blockIdx.x, V = p.V, N = p.top_logprobs;
+    if (p.finished[b]) {
+        return;  // (the state BEFORE the step: k_sample runs behind this launch)
+    }
+    const bool   topp  = p.top_k[b] == 0;  // the row holds probabilities
+    const int    slice = (V + TLP_SLICES - 1) / TLP_SLICES;
+    const int    i0    = blk * slice;
+    const int    n     = max(0, min(slice, V - i0));
+    const float* l     = p.logits + (size_t)b * V + i0;
+    float*       ov    = cand_v + ((size_t)b * TLP_SLICES + blk) * TOP_LOGPROBS_MAX;
+    int*         oi    = cand_i + ((size_t)b * TLP_SLICES + blk) * TOP_LOGPROBS_MAX;
+    float        vals[TLP_MAXE], lmax;
+    const int    ne   = n > (int)threadIdx.x ? (n - (int)threadIdx.x + 255) / 256 : 0;
+    const VI     best = slice_load(vals, l, ne, -1, lmax);
+    if (!topp) {  // {max, sum of exp(v - max)} of the slice, as k_topk_stage1 takes them
+        float       m;
+        const float sum = slice_stats(vals, ne, lmax, redv, m);
+        if (threadIdx.x == 0) {
+            float* st = stats + ((size_t)b * TLP_SLICES + blk) * 2;
+            st[0]     = n > 0 ? m : -FLT_MAX;
+            st[1]     = n > 0 ? sum : 0.f;
+        }
+    }
+    int live = 0;
+#pragma unroll
+    for (int j = 0; j < TLP_MAXE; j++) {
+        if (j < ne) {
+            if (topp ? !(vals[j] > 0.f) : !(vals[j] > -FLT_MAX)) {
+                vals[j] = -INFINITY;
+            }
+            else {
+                live++;
+            }
+        }
+    }
+    int cnt = 0;  // entries of the slice that are not masked
+    (void)block_excl_scan(live, redi, cnt);
+    const int ke = N < n ? N : n;        // candidates this slice supplies: [0, ku) not masked, [ku, ke) masked
+    const int ku = ke < cnt ? ke : cnt;
+    if (ku == 1) {  // (an entry that is not masked beats every masked one as it was loaded, too: the arg max of the load pass)
+        const VI r = block_best(best, redv, redi);
+        if (threadIdx.x == 0) {
+            ov[0] = r.v;
+            oi[0] = i0 + r.i;
+        }
+    }
+    else if (ku > 1) {
+        // (the ku-th best is not masked, so a tie at the threshold re-reads entries that are in memory what they are in vals)
+        slice_select<TLP_MAXE, false>(vals, ne, n, ku, l, i0, ov, oi, hist8, hist, s_sel, redi, false, -1);
+    }
+    // fewer live entries than places: the masked entries with the lowest ids follow (thread t holds ids t, t + 256, ...)
+    int base = 0;
+#pragma unroll
+    for (int j = 0; j < TLP_MAXE; j++) {
+        if (ku + base < ke) {  // (the same in every thread)
+            const bool msk = j < ne && vals[j] == -INFINITY;
+            int        tot = 0;
+            const int  pos = ku + base + block_excl_scan(msk ? 1 : 0, redi, tot);
+            if (msk && pos < ke) {
+                ov[pos] = -INFINITY;
+                oi[pos] = i0 + (int)threadIdx.x + 256 * j;
+            }
+            base += tot;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_top_logprobs_merge(const SamplingParams p, const float* cand_v, const int* cand_i,
+                                                            const float* stats)
+{
+    if (p.state->all_finished) {
+        return;
+    }
+    __shared__ float sv[TLP_SLICES * 32];  // 32 x N <= 640 pairs, padded to a power of two
+    __shared__ int   si[TLP_SLICES * 32];
+    const int        b = blockIdx.x, V = p.V, N = p.top_logprobs;
+    if (p.finished[b]) {
+        return;
+    }
+    const bool topp  = p.top_k[b] == 0;
+    const int  slice = (V + TLP_SLICES - 1) / TLP_SLICES;
+    int        n2    = 2;
+    while (n2 < TLP_SLICES * N) {
+        n2 <<= 1;
+    }
+    for (int c = threadIdx.x; c < n2; c += 256) {
+        const int  q = c / N, j = c - q * N;
+        const int  nq = q < TLP_SLICES ? max(0, min(slice, V - q * slice)) : 0;  // what stage A wrote: min(N, nq) pairs of slice q
+        const bool ok = j < nq;
+        sv[c]         = ok ? cand_v[((size_t)b * TLP_SLICES + q) * TOP_LOGPROBS_MAX + j] : -INFINITY;
+        si[c]         = ok ? cand_i[((size_t)b * TLP_SLICES + q) * TOP_LOGPROBS_MAX + j] : 0x7fffffff;
+    }
+    bitonic_sort_best_first(sv, si, n2);
+    if ((int)threadIdx.x < N) {
+        // the row's soft-max from the slice statistics: addBiasSoftMax (sampling_topp_kernels.cu:1296-1345) as topk_draw builds it
+        float row_max = 0.f, log_den = 0.f;
+        if (!topp) {
+            const float* st = stats + (size_t)b * TLP_SLICES * 2;
+            row_max         = -FLT_MAX;
+            for (int q = 0; q < TLP_SLICES; q++) {
+                row_max = fmaxf(row_max, st[2 * q]);
+            }
+            float tot = 0.f;
+            for (int q = 0; q < TLP_SLICES; q++) {
+                tot += st[2 * q + 1] * __expf(st[2 * q] - row_max);
+            }
+            log_den = logf(tot + 1e-6f);
+        }
+        const float v  = sv[threadIdx.x];
+        int         id = si[threadIdx.x];
+        float       lp = -INFINITY;
+        if (id == 0x7fffffff) {
+            id = -1;  // V < N
+        }
+        else if (v != -INFINITY) {
+            lp = topp ? logf(v) : (v - row_max) - log_den;  // (top-p rows: what commit_pick stores for such a row)
+        }
+        // the DEVICE step, as store_output_log_prob: a captured step replays correctly
+        const size_t t   = p.row_len ? 0 : (size_t)(p.state->step - p.max_input_len);
+        const size_t o   = (t * p.B + b) * N + threadIdx.x;
+        p.top_logprob_ids[o]    = id;
+        p.top_logprob_values[o] = lp;
+    }
+}
+
 // ---- step 4: stop words, length criterion, bookkeeping (single block) -----------------------------------------
 // DEFER_HOST: the caller writes the pinned host flags itself, as the launch's last stores (decode_publish_host)
 template<bool DEFER_HOST = false>
@@ -1671,7 +1818,7 @@ static bool dynamic_decode_is_topk_fused(const SamplingParams& p, bool finish)
     const int on = getenv("FTCF_TOPK_FUSED") ? atoi(getenv("FTCF_TOPK_FUSED")) : 1;  // (read per call: the tests switch the forms)
     return on && finish && p.max_top_k >= 2 && p.max_top_k <= TKD_MAXK && !p.any_top_p && !p.apply_temperature
            && !p.apply_repetition && !p.optional_last_tokens && !p.row_len && p.V <= TKD_SLICES * 256 * TKD_MAXE && p.B <= TKD_MAXB
-           && p.rot / 2 <= 256
+           && p.rot / 2 <= 256 && !p.top_logprob_ids
            && (size_t)p.B * TKD_SLICES * (TKD_MAXK * 8 + 8) <= sampling_workspace_bytes(p.B, p.V);
 }
 
@@ -1680,7 +1827,7 @@ static bool dynamic_decode_is_greedy_fused(const SamplingParams& p, bool finish)
 {
     const int greedy_on = getenv("FTCF_GREEDY_FUSED") ? atoi(getenv("FTCF_GREEDY_FUSED")) : 1;  // (read per call: the tests switch the forms)
     return greedy_on && finish && p.max_top_k == 1 && !p.any_top_p && !p.apply_temperature && !p.apply_repetition && !p.optional_last_tokens
-           && !p.row_len && p.V <= GREEDY_SLICES * 256 * GREEDY_MAXE && p.B <= 1024 && p.rot / 2 <= 256
+           && !p.row_len && p.V <= GREEDY_SLICES * 256 * GREEDY_MAXE && p.B <= 1024 && p.rot / 2 <= 256 && !p.top_logprob_ids
            && (size_t)p.B * GREEDY_SLICES * 16 <= sampling_workspace_bytes(p.B, p.V);
 }
 
@@ -1720,6 +1867,20 @@ void launch_dynamic_decode(const SamplingParams& p, hipStream_t s, bool finish)
     hipLaunchKernelGGL(k_decode_prep, dim3(p.B), dim3(1024), prep_smem, s, p);
     const int slice = (p.V + TOPK_BLOCKS - 1) / TOPK_BLOCKS;
     FTCF_CHECK_ARG(slice <= 256 * STAGE1_MAXE, "vocabulary too large: a stage-1 slice holds 256 x 60 logits in registers (V <= 122880)");
+    if (p.top_logprob_ids) {
+        // the row as k_decode_prep leaves it is read before stage 1 takes the workspace: candidates [B][32][20] values, then ids,
+        // then {max, sum of exponentials} per slice
+        FTCF_CHECK_ARG(p.top_logprobs >= 1 && p.top_logprobs <= TOP_LOGPROBS_MAX && p.top_logprob_values && p.return_cum_log_probs,
+                       "top_logprobs must be in [1, 20] with both buffers and the soft-max statistics");
+        FTCF_CHECK_ARG((size_t)p.B * TLP_SLICES * (TOP_LOGPROBS_MAX * 8 + 8) <= sampling_workspace_bytes(p.B, p.V)
+                           && p.V <= TLP_SLICES * 256 * TLP_MAXE,
+                       "top_logprobs: workspace too small");
+        float* tv = reinterpret_cast<float*>(p.ws);
+        int*   ti = reinterpret_cast<int*>(tv + (size_t)p.B * TLP_SLICES * TOP_LOGPROBS_MAX);
+        float* ts = reinterpret_cast<float*>(ti + (size_t)p.B * TLP_SLICES * TOP_LOGPROBS_MAX);
+        hipLaunchKernelGGL(k_top_logprobs_slices, dim3(TLP_SLICES, p.B), dim3(256), 0, s, p, tv, ti, ts);
+        hipLaunchKernelGGL(k_top_logprobs_merge, dim3(p.B), dim3(256), 0, s, p, tv, ti, ts);
+    }
     hipLaunchKernelGGL(k_topk_stage1, dim3(TOPK_BLOCKS, p.B), dim3(256), 0, s, p, cand_v, cand_i, slice);
     // stage 2 sorts the union of the slices' candidate sets in LDS: the next power of two above 8 * k pairs
     int kc = std::max(1, std::min(p.max_top_k, TOPK_MAX));

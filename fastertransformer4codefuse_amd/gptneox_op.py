@@ -190,11 +190,16 @@ class GptNeoXOp:
                 beam_search_diversity_rate=None, temperature=None, len_penalty=None, repetition_penalty=None,
                 random_seed=None, stop_words_list=None, optional_last_tokens=None, return_cum_log_probs=None,
                 callback=None, _debug_logits=None, return_output_log_probs=None, return_context_log_probs=None,
-                speculative_tokens=None, speculative_ngram=None, draft_ids=None):
+                speculative_tokens=None, speculative_ngram=None, draft_ids=None, top_logprobs=None):
         """Returns [output_ids, sequence_lengths], then cum_log_probs [B, beam], output_log_probs [B, beam, output_len]
         (GptNeoX.cc:967-987: each generated token's log-probability, 0 after a row has finished) and context_log_probs
         [B, max_input_len] (log P(input_ids[b, t] | input_ids[b, < t]) at t >= 1, 0 at t = 0 and in the padding), each
         only when it was asked for.
+
+        top_logprobs = N in 1..20 appends top_logprob_ids [B, beam, output_len, N] int32 and top_logprob_values (fp32): the N
+        most likely tokens of every step, best first, with their log-probabilities under the distribution output_log_probs
+        is defined under (include/ftcf.h); (-1, 0) after a row has finished.  The tokens do not change; beam_width > 1 is
+        refused.
 
         speculative_tokens = K in 1..15 switches speculative greedy decoding on: up to K tokens are
         drafted per step -- by prompt lookup over the last speculative_ngram tokens (default 3), or taken from draft_ids (int32
@@ -222,6 +227,11 @@ class GptNeoXOp:
         output_log_probs = (torch.empty((B, beam_width, int(output_len)), dtype=torch.float32, device=dev)
                             if return_output_log_probs else None)
         context_log_probs = torch.empty((B, S), dtype=torch.float32, device=dev) if return_context_log_probs else None
+        top_n = int(top_logprobs) if top_logprobs else 0
+        top_ids = top_values = None
+        if top_n:
+            top_ids = torch.empty((B, beam_width, int(output_len), max(top_n, 0)), dtype=torch.int32, device=dev)
+            top_values = torch.empty(top_ids.shape, dtype=torch.float32, device=dev)
 
         keep = []
 
@@ -273,9 +283,11 @@ class GptNeoXOp:
         a.speculative_tokens, a.speculative_ngram = spec_k, spec_n
         if draft_ids is not None:
             a.draft_ids = draft_ids.data_ptr()
+        if top_n:
+            a.top_logprobs, a.top_logprob_ids, a.top_logprob_values = top_n, top_ids.data_ptr(), top_values.data_ptr()
         capi.check(capi.lib().ftcf_gptneox_forward(self._h, C.byref(a)))
         out = [output_ids, sequence_lengths]
-        for t in (cum_log_probs, output_log_probs, context_log_probs):
+        for t in (cum_log_probs, output_log_probs, context_log_probs, top_ids, top_values):
             if t is not None:
                 out.append(t)
         return out

@@ -243,7 +243,12 @@ int ftcf_gather_pages_to_kv(void* k_cache, void* v_cache, const void* k_pool, co
  * bookkeeping (stop words, length criterion, padding count) follows, and *all_finished / *next_step (host, may be NULL) receive
  * the state it leaves; finish == 0 is the batcher's form (no bookkeeping: *all_finished 0, *next_step = step).  *form (host,
  * may be NULL): 0 the general four launches, 1 the one-launch top-k step, 2 the one-launch greedy step.  Synchronises the
- * stream.  V > 122880 on the general path and a repetition penalty with total_len > 7680 are FTCF_ERR_INVALID_ARG. */
+ * stream.  V > 122880 on the general path and a repetition penalty with total_len > 7680 are FTCF_ERR_INVALID_ARG.
+ * top_logprobs = N in 1..20 (appended; 0 = off): top_ids / top_log_probs, time-major [total_len - max_input_len, B, N] int32 / fp32,
+ * receive at row step - max_input_len (row 0 with row_len) the N best (id, log-probability) pairs of every row that was not
+ * finished before the step, as top_logprobs of ftcf_forward_args defines them; the pairs of a finished row are not written.  The
+ * step then takes the general form and the soft-max statistics are on.  N outside 0..20, or N > 0 with a NULL buffer, is
+ * FTCF_ERR_INVALID_ARG. */
 typedef struct {
     float*          logits;
     int*            output_ids;
@@ -269,6 +274,9 @@ typedef struct {
     int n_top_k, n_top_p, n_temperature, n_repetition_penalty, n_min_length, n_random_seed;
     int stop_len, optional_count;
     int B, V, step, max_input_len, total_len, end_id, return_cum_log_probs, finish;
+    int    top_logprobs;
+    int*   top_ids;
+    float* top_log_probs;
 } ftcf_dynamic_decode_args;
 int ftcf_dynamic_decode_step(const ftcf_dynamic_decode_args* args, void* stream);
 /* ONE step of the beam-search layer (OnlineBeamSearchLayer without beam hypotheses: penalties, per-row top K of log-softmax +
@@ -412,6 +420,27 @@ typedef struct {
      *   logits never reach memory; ftcf_lm_head_log_probs); beam requests score the prompt once, the values equal beam_width 1's.
      *   fp32 engines are refused. */
     float* output_log_probs;
+    /* The top-N alternative tokens of every step (0 / NULL = off: no kernel is launched and every bit is as before).  The three
+     * fields sit with the log-probability outputs, in front of context_log_probs: the speculative fields stay the struct's last
+     * ones, so a caller built against an earlier header is rebuilt (callers that zero-initialise and set fields by name are
+     * unchanged).
+     * With top_logprobs = N in 1..20, top_logprob_ids (int32) and top_logprob_values (fp32), both device [B, 1, output_len, N],
+     * receive for every generated position the N best (id, log-probability) pairs of the distribution output_log_probs is
+     * defined under: the row after the optional-token mask, temperature, repetition penalty and min-length mask, before top-k /
+     * top-p truncation.  Order: log-probability descending, equal values by id ascending (+0.0 and -0.0 are one value).  Value:
+     * (v - row_max) - logf(sum of exp(v - row_max) + 1e-6f); for a row of the top-p layer logf of the fp32 probability its
+     * soft-max left, which is what output_log_probs holds for the emitted token.  Masked entries (a processed logit of -inf or
+     * <= -FLT_MAX, a probability of 0) come after every other entry, by id ascending, with -inf.  With fewer than N tokens in the
+     * vocabulary the trailing pairs are (-1, -inf).  Positions after a row has finished hold (-1, 0.0f).  Asking for it switches
+     * the soft-max statistics on exactly as return_cum_log_probs = 1 does and changes nothing else: tokens are those of the
+     * request with output_log_probs alone.  A greedy row's pair 0 is the emitted token; a top_k = k row's token is among the
+     * pairs when N >= k.  Every step takes the general decode form (the one-launch greedy / top-k steps do not produce the
+     * pairs): cum_log_probs and output_log_probs are bit for bit those of that form, which may differ in the last bit from the
+     * one-launch steps' (another summation order of the soft-max statistics).  beam_width > 1, N outside 0..20 and N > 0 with a NULL buffer are
+     * FTCF_ERR_INVALID_ARG; a speculative request that asks for it runs unspeculated. */
+    int    top_logprobs;
+    int*   top_logprob_ids;
+    float* top_logprob_values;
     float* context_log_probs;
     /* Speculative greedy decoding (appended, 0 / NULL = off and every bit as before).  With
      * speculative_tokens = K in 1..15 a step drafts up to K tokens -- the continuation of the most recent earlier occurrence of
@@ -548,6 +577,12 @@ int ftcf_batcher_step(ftcf_batcher_t b, long* request_ids, int* tokens, int* fin
  * NaN.  log_probs holds `capacity` floats. */
 int ftcf_batcher_step_ex(ftcf_batcher_t b, long* request_ids, int* tokens, int* finished, float* log_probs, int capacity,
                          int* n_events);
+/* The same with each event's top_n (1..20) alternatives: top_ids / top_log_probs hold capacity * top_n entries, event i's pairs at
+ * [i * top_n, (i + 1) * top_n), as top_logprobs of ftcf_forward_args defines them (the distribution the event's token was drawn
+ * from).  Per call, like log_probs: an admission inside this call reports the pairs of its first token; a beam request's event
+ * and events of admissions made by another step call carry (-1, NaN) pairs.  log_probs may be NULL. */
+int ftcf_batcher_step_top(ftcf_batcher_t b, long* request_ids, int* tokens, int* finished, float* log_probs, int top_n, int* top_ids,
+                          float* top_log_probs, int capacity, int* n_events);
 /* Streaming (the reference's token callback, GptNeoX.cc:362-375, 1023 `token_generated_cb_`, per request here): `fn` is called
  * from inside ftcf_batcher_step, on the calling thread, for every event the moment its token is on the host -- i.e. between
  * the chunks of a long admission as well -- and the same events are returned by the step call afterwards.  NULL unsets. */
