@@ -1,10 +1,9 @@
 // Continuous batching over a paged K/V cache (include/ftcf.h `ftcf_batcher_*`): split out of engine.hip in round 4.
 #include "engine.hip.h"
 #include "attn_device.hip.h"  // rotary_coef (the rows kernel's rotary table of a step)
-#include "prefix_index.h"
+#include "batcher_sched.h"
 
 #include <chrono>
-#include <set>
 
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -106,56 +105,17 @@ __global__ void k_batcher_beam_advance(int* tok, int* len, const int* out_row, i
     }
 }
 
-struct ftcf_batcher {
-    struct Request {
-        long             id;
-        std::vector<int> prompt;
-        int              max_new, top_k;
-        float            top_p, temperature, repetition_penalty = 1.f;
-        uint64_t         seed;
-        std::vector<std::vector<int>> stop;  // stop sequences (token ids)
-        int              beam_width = 1;     // > 1: a beam group (submit_beam)
-        float            diversity = 0.f, len_penalty = 0.f;
-        int              min_length = 0;     // beam requests: the end token is held back for this many new tokens
-    };
-    struct Slot {
-        bool             active = false;
-        long             id = 0;
-        int              len = 0, generated = 0, max_new = 0;
-        std::vector<int> pages;
-        // the request's own token history (prompt + generated) and stop sequences: the stop criterion
-        // (stop_criteria_kernels.cu:24-83: finished AFTER the sequence has been emitted) is the scheduler's, on the host,
-        // which sees every token anyway
-        std::vector<int>              hist;
-        std::vector<std::vector<int>> stop;
-        float                         repetition_penalty = 1.f;
-        int                           group = -1;  // a beam of the group whose first slot this is (-1: an ordinary sequence)
-    };
-    // Beam search inside the batcher (round 4; the reference's serving layer runs beam requests through the same decoder:
-    // triton_backend/gptneox/GptNeoXTritonModelInstance.cc).  A request of beam width K lives in K CONSECUTIVE slots -- its
-    // beams ride in the same batched GEMMs as everybody else's rows -- and is scored by the engine's own beam kernels
-    // (launch_beam_search with batch 1: OnlineBeamSearchLayer semantics, kernels_beam.hip) on per-group state.  The cache
-    // indirection of the reference (BaseBeamSearchLayer.cu:30-62: which beam's cache row holds position t) is replaced by what a
-    // paged cache is for: after every step beam k's page list becomes a copy of its parent's (pages are reference counted),
-    // and only the page the next token will be appended to is copied when it is shared (copy-on-write, all layers, one launch
-    // per step); the attention kernel is the ordinary paged one.  The prompt's pages are written once and shared by all beams.
-    struct BeamGroup {
-        long id = 0;
-        int  si = 0, K = 0, n = 0, max_new = 0, generated = 0, budget = 0;
-        bool penalised = false;  // repetition_penalty != 1
-        bool has_stop = false, has_min = false;
-        std::vector<std::vector<int>> lists;  // page list of every beam
-    };
+static_assert(BatcherSched::MAX_BEAM_WIDTH == BEAM_MAX_K, "the scheduler's beam width limit is the beam kernels'");
+
+// the scheduler's host state (batcher_sched.h: queue, slots, pages, admission policy) + the device side
+struct ftcf_batcher : BatcherSched {
     struct BeamResult {
         int                K = 0, total = 0;
         std::vector<int>   ids, lens;
         std::vector<float> cum;
     };
-    std::map<int, BeamGroup>   groups;        // by first slot
     std::map<long, BeamResult> beam_results;  // finished beam requests until they are fetched
-    std::vector<int>           page_ref;      // references to a page (ordinary sequences: 1)
     ftcf_gptneox* e = nullptr;
-    int           max_batch = 0, P = 0, num_pages = 0, max_pages = 0, max_len = 0;
     size_t        pool_layer_elems = 0;
     // device
     f16 *kpool = nullptr, *vpool = nullptr;
@@ -185,9 +145,6 @@ struct ftcf_batcher {
     void*        samp_ws = nullptr;
     float*       smallm_ws = nullptr;
     float*       tiled_ws  = nullptr;  // split-K workspace of the tiled GEMM (decode steps of 17..768 rows)
-    // chunked admission: with slots running, a prompt longer than this is prefilled alone, `prefill_chunk` tokens at a time, one
-    // decode step of the running slots between two chunks (FTCF_BATCHER_PREFILL_CHUNK; 0 = whole prompts)
-    int prefill_chunk = 512;
     // the decode step's layers as ONE launch of the rows kernel (kernels_rows.hip, paged K/V form): tensor_para_size 1, at most 16
     // slots, page_tokens a multiple of the kernel's attention block (FTCF_BATCHER_ROWS=0: the per-GEMM launches)
     RowsPlan      rplan{};
@@ -201,18 +158,6 @@ struct ftcf_batcher {
     unsigned     smallm_seq = 0;
     long         gemm_steps = 0;
     std::vector<void*> owned;
-    // host
-    std::vector<Slot>   slots;
-    std::deque<Request> waiting;
-    std::vector<int>    free_pages;
-    // prefix cache: the index holds one reference to each of its pages; `deferred` = slots of an admission whose
-    // request finished with its first token, released only after the admission's prompts have been inserted
-    bool             prefix_on = false;
-    PrefixIndex      pindex;
-    std::vector<int> deferred;
-    long             px_lookups = 0, px_prompt_tokens = 0, px_hit_tokens = 0, px_computed_tokens = 0, px_evictions = 0;
-    long                next_id = 1;
-    int                 max_prompt = 0;
 
     template<typename T>
     T* dmalloc(size_t n, bool zero = true)
@@ -239,7 +184,6 @@ struct ftcf_batcher {
                            || ftcf_gptneox::chunked_supported(e->fp32, e->cfg.tensor_para_size, e->cfg.use_gptj_residual, e->H),
                        "the prefix cache needs an fp16 / int8 engine with tensor_para_size 1, parallel residual and a hidden size "
                        "with the dual LayerNorm (a prompt phase from a token offset)");
-        prefix_on = prefix_cache;
         FTCF_CHECK_ARG(!e->fp32 && e->cfg.use_gptj_residual && (e->dh == 64 || e->dh == 128),
                        "the batcher serves fp16 / int8 engines with parallel residual and size_per_head 64 / 128");
         FTCF_CHECK_ARG(mb >= 1 && mb <= 64 && page_tokens >= 8 && pages >= 1 && max_seq_len >= 2, "bad batcher geometry");
@@ -247,12 +191,7 @@ struct ftcf_batcher {
         if (const char* c = getenv("FTCF_BATCHER_PREFILL_CHUNK")) {
             prefill_chunk = std::max(0, atoi(c));
         }
-        max_batch = mb;
-        P         = page_tokens;
-        num_pages = pages;
-        max_pages = (max_seq_len + P - 1) / P;
-        max_len   = max_pages * P;
-        max_prompt = max_seq_len - 1;
+        init_sched(mb, page_tokens, pages, max_seq_len, e->V, prefix_cache);
         FTCF_CHECK_ARG(mmha_paged_smem_bytes(e->dh, max_pages, max_len) <= 64 * 1024, "max_seq_len too large for the paged attention");
         const int    H = e->H, hl = e->hl, il = e->il, L = e->L, V = e->V;
         const size_t B = (size_t)max_batch;
@@ -327,28 +266,7 @@ struct ftcf_batcher {
                     d_rlayers = dmalloc<PersistLayer>(L);
                     d_rot     = dmalloc<float>(B * std::max(1, e->cfg.rotary_embedding_dim));
                     d_rstep   = dmalloc<int>(1);
-                    std::vector<PersistLayer> pl(L);
-                    for (int l = 0; l < L; l++) {
-                        const LayerWeights& w = e->layers[l];
-                        PersistLayer&       r = pl[l];
-                        r.ln1_g = w.ln1_g;
-                        r.ln1_b = w.ln1_b;
-                        r.ln2_g = w.ln2_g;
-                        r.ln2_b = w.ln2_b;
-                        r.w_qkv = w.qkv.kernel;
-                        r.w_ffn1 = w.ffn1.kernel;
-                        r.w_out = w.attn_out.kernel;
-                        r.w_ffn2 = w.ffn2.kernel;
-                        r.s_qkv = w.qkv.scale;
-                        r.s_ffn1 = w.ffn1.scale;
-                        r.s_out = w.attn_out.scale;
-                        r.s_ffn2 = w.ffn2.scale;
-                        r.b_qkv = w.qkv.bias;
-                        r.b_ffn1 = w.ffn1.bias;
-                        r.b_res = w.ffn2.bias;
-                        r.k_cache = kpool + (size_t)l * pool_layer_elems;
-                        r.v_cache = vpool + (size_t)l * pool_layer_elems;
-                    }
+                    const std::vector<PersistLayer> pl = persist_layer_table(e->layers, kpool, vpool, pool_layer_elems);
                     FTCF_HIP_CHECK(hipMemcpy(d_rlayers, pl.data(), sizeof(PersistLayer) * L, hipMemcpyHostToDevice));
                     use_rows = true;
                 }
@@ -369,133 +287,6 @@ struct ftcf_batcher {
         }
         std::vector<uint8_t> fin(max_batch, 1);
         FTCF_HIP_CHECK(hipMemcpy(d_fin, fin.data(), max_batch, hipMemcpyHostToDevice));
-        slots.assign(max_batch, Slot{});
-        free_pages.resize(num_pages);
-        for (int i = 0; i < num_pages; i++) {
-            free_pages[i] = num_pages - 1 - i;
-        }
-        page_ref.assign(num_pages, 0);
-        pindex = PrefixIndex(P);
-    }
-    int take_page()
-    {
-        if (free_pages.empty() && prefix_on) {  // a cached page only the index holds makes room (LRU, leaves first)
-            const int pg = pindex.evict_one(page_ref);
-            if (pg >= 0) {
-                px_evictions++;
-                drop_page(pg);
-            }
-        }
-        if (free_pages.empty()) {
-            throw Error(-2, "batcher: the page pool is exhausted (a reservation was wrong)");
-        }
-        const int pg = free_pages.back();
-        free_pages.pop_back();
-        page_ref[pg] = 1;
-        return pg;
-    }
-    void drop_page(const int pg)
-    {
-        if (--page_ref[pg] == 0) {
-            free_pages.push_back(pg);
-        }
-    }
-    // pages promised to running beam groups but not yet taken (a group takes its pages as its beams diverge: at most
-    // budget = K * pages of one full-length sequence)
-    int reserved_pages() const
-    {
-        int r = 0;
-        for (const auto& kv : groups) {
-            std::set<int> held;
-            for (const auto& l : kv.second.lists) {
-                held.insert(l.begin(), l.end());
-            }
-            r += std::max(0, kv.second.budget - (int)held.size());
-        }
-        return r;
-    }
-
-    static constexpr int STOP_LW = 64;  // total stop-word tokens per request (the [2][Lw] word list of the admission)
-    long submit(const int* ids, int n, int max_new, int top_k, float top_p, float temperature, uint64_t seed,
-                float repetition_penalty = 1.f, const int* stop_words = nullptr, int stop_len = 0)
-    {
-        FTCF_CHECK_ARG(repetition_penalty > 0.f, "repetition_penalty must be positive");
-        FTCF_CHECK_ARG(stop_len >= 0 && stop_len <= STOP_LW && (stop_len == 0 || stop_words), "bad stop word list");
-        // (the decode step stages total_len = max_len + 2 history entries: the same bound as launch_dynamic_decode's)
-        FTCF_CHECK_ARG(((size_t)max_len + 2) * 8 <= 60 * 1024 || repetition_penalty == 1.f,
-                       "max_seq_len too large for the repetition-penalty staging buffer");
-        FTCF_CHECK_ARG(ids && n >= 1 && max_new >= 1, "empty prompt or max_new_tokens < 1");
-        FTCF_CHECK_ARG(n + max_new <= max_len && n <= max_prompt, "prompt + max_new_tokens exceed the batcher's max_seq_len");
-        FTCF_CHECK_ARG((n + max_new + P - 1) / P <= num_pages, "the request needs more pages than the pool has");
-        FTCF_CHECK_ARG(top_k >= 0 && top_k <= 1024 && top_p >= 0.f && top_p <= 1.f && temperature > 0.f, "bad sampling parameters");
-        for (int i = 0; i < n; i++) {
-            FTCF_CHECK_ARG(ids[i] >= 0 && ids[i] < e->V, "token id out of range");
-        }
-        Request r;
-        r.id = next_id++;
-        r.prompt.assign(ids, ids + n);
-        r.max_new = max_new;
-        r.top_k = top_k;
-        r.top_p = top_p;
-        r.temperature = temperature;
-        r.seed = seed;
-        r.repetition_penalty = repetition_penalty;
-        // to_word_list_format (codefuse_example.py:26-53): [0][..] flat ids, [1][..] cumulative end offsets, -1 padded
-        for (int i = 0, start = 0; i < stop_len; i++) {
-            const int end = stop_words[stop_len + i];
-            if (end < 0) {
-                break;
-            }
-            FTCF_CHECK_ARG(end > start && end <= stop_len, "bad stop word offsets");
-            r.stop.emplace_back(stop_words + start, stop_words + end);
-            start = end;
-        }
-        waiting.push_back(std::move(r));
-        return waiting.back().id;
-    }
-
-    // a beam-search request (GptNeoXOp.forward with beam_width > 1: OnlineBeamSearchLayer): K consecutive slots; one event when
-    // it has finished (token = -1), the K hypotheses through beam_result()
-    long submit_beam(const int* ids, int n, int max_new, int beam_width, float diversity, float len_penalty, float temperature,
-                     float repetition_penalty, int min_length = 0, const int* stop_words = nullptr, int stop_len = 0)
-    {
-        FTCF_CHECK_ARG(min_length >= 0, "min_length must not be negative");
-        FTCF_CHECK_ARG(stop_len >= 0 && stop_len <= STOP_LW && (stop_len == 0 || stop_words), "bad stop word list");
-        FTCF_CHECK_ARG(beam_width >= 2 && beam_width <= BEAM_MAX_K && beam_width <= max_batch,
-                       "beam_width must be in [2, 64] and fit the batcher's slots");
-        FTCF_CHECK_ARG(repetition_penalty > 0.f && temperature > 0.f, "repetition_penalty and temperature must be positive");
-        FTCF_CHECK_ARG(((size_t)max_len + 2) * 8 <= 60 * 1024 || repetition_penalty == 1.f,
-                       "max_seq_len too large for the repetition-penalty staging buffer");
-        FTCF_CHECK_ARG(ids && n >= 1 && max_new >= 1, "empty prompt or max_new_tokens < 1");
-        FTCF_CHECK_ARG(n + max_new <= max_len && n <= max_prompt, "prompt + max_new_tokens exceed the batcher's max_seq_len");
-        FTCF_CHECK_ARG(beam_width * ((n + max_new + P - 1) / P) <= num_pages, "the request needs more pages than the pool has");
-        for (int i = 0; i < n; i++) {
-            FTCF_CHECK_ARG(ids[i] >= 0 && ids[i] < e->V, "token id out of range");
-        }
-        Request r;
-        r.id = next_id++;
-        r.prompt.assign(ids, ids + n);
-        r.max_new = max_new;
-        r.top_k = 1;
-        r.top_p = 0.f;
-        r.temperature = temperature;
-        r.seed = 0;
-        r.repetition_penalty = repetition_penalty;
-        r.beam_width = beam_width;
-        r.diversity = diversity;
-        r.len_penalty = len_penalty;
-        r.min_length = min_length;
-        for (int i = 0, start = 0; i < stop_len; i++) {  // to_word_list_format (codefuse_example.py:26-53), as submit()
-            const int end = stop_words[stop_len + i];
-            if (end < 0) {
-                break;
-            }
-            FTCF_CHECK_ARG(end > start && end <= stop_len, "bad stop word offsets");
-            r.stop.emplace_back(stop_words + start, stop_words + end);
-            start = end;
-        }
-        waiting.push_back(std::move(r));
-        return waiting.back().id;
     }
 
     struct Event {
@@ -522,45 +313,49 @@ struct ftcf_batcher {
 
     // the first tokens of an admission reach the callback only when the admission is known to have succeeded: a failed one is
     // rolled back and retried, and a streaming consumer must not see its first tokens twice
-    void fire(const std::vector<Event>& ev, const size_t from)
+    void fire(const std::vector<Event>& ev)
     {
         if (on_token) {
-            for (size_t i = from; i < ev.size(); i++) {
-                on_token(on_token_user, ev[i].id, ev[i].token, ev[i].finished);
+            for (const Event& x : ev) {
+                on_token(on_token_user, x.id, x.token, x.finished);
             }
         }
     }
 
-    // stop_criteria_kernels.cu:24-83: does the history END with one of the request's stop sequences?
-    static bool hits_stop_word(const Slot& s)
+    // the slot's sequence leaves: its pages back to the pool, `finished` set on the device (device_knows: a kernel set it already)
+    hipError_t retire(const int si, const bool device_knows = false)
     {
-        for (const auto& wd : s.stop) {
-            if (!wd.empty() && s.hist.size() >= wd.size() && std::equal(wd.begin(), wd.end(), s.hist.end() - wd.size())) {
-                return true;
-            }
-        }
-        return false;
+        release(slots[si]);
+        const uint8_t one8 = 1;
+        return device_knows ? hipSuccess : hipMemcpy(d_fin + si, &one8, 1, hipMemcpyHostToDevice);
     }
-    void release(Slot& s)
-    {
-        for (int pg : s.pages) {
-            drop_page(pg);
+    // the engine's prompt phase from a token offset, for one forward()
+    struct PrefillFrom {
+        ftcf_gptneox* e;
+        PrefillFrom(ftcf_gptneox* eng, int begin, std::function<void()> prefix): e(eng)
+        {
+            e->prefill_begin  = begin;
+            e->prefill_prefix = std::move(prefix);
         }
-        s.pages.clear();
-        s.active = false;
-    }
+        ~PrefillFrom()
+        {
+            e->prefill_begin  = 0;
+            e->prefill_prefix = nullptr;
+        }
+    };
 
     // prompts -> ONE ragged batch through the engine's context path (+ first tokens) -> pages of their slots
     // hit (one request only): the cached pages of its first prompt blocks (pinned here: the slot's page list owns one reference)
-    void admit(const std::vector<int>& sis, const std::vector<Request>& rs, std::vector<Event>& ev, const std::vector<int>* hit = nullptr)
+    // (the first n of rs, into the first n of sis)
+    void admit(const std::vector<int>& sis, const std::vector<Request>& rs, const int n, std::vector<Event>& ev,
+               const std::vector<int>* hit = nullptr)
     {
         Range        rg("ftcf.batcher.admit");
         deferred.clear();
         hipStream_t  st = e->stream;
-        const int    n  = (int)sis.size();
         int          S  = 0;
-        for (const Request& r : rs) {
-            S = std::max(S, (int)r.prompt.size());
+        for (int i = 0; i < n; i++) {
+            S = std::max(S, (int)rs[i].prompt.size());
         }
         std::vector<int>      ids((size_t)n * S, e->cfg.end_id), lens(n), topk(n);
         std::vector<float>    topp(n), temp(n), rep(n);
@@ -576,32 +371,11 @@ struct ftcf_batcher {
             temp[i] = r.temperature;
             rep[i]  = r.repetition_penalty;
             seed[i] = r.seed;
-            {  // the request's stop sequences in the reference's word-list layout (the engine samples the FIRST token)
-                int* ids_row = sw.data() + (size_t)i * 2 * STOP_LW;
-                int* off_row = ids_row + STOP_LW;
-                std::fill(off_row, off_row + STOP_LW, -1);
-                int pos = 0, k = 0;
-                for (const auto& wd : r.stop) {
-                    std::copy(wd.begin(), wd.end(), ids_row + pos);
-                    pos += (int)wd.size();
-                    off_row[k++] = pos;
-                    any_stop = true;
-                }
-            }
-            Slot&     s = slots[sis[i]];
-            const int need = (lens[i] + r.max_new + P - 1) / P;
-            s.pages.clear();
-            if (hit) {
-                FTCF_CHECK_ARG(n == 1, "batcher: a prefix hit is admitted alone");
-                s.pages = *hit;
-                for (const int pg : *hit) {
-                    page_ref[pg]++;
-                }
-                pindex.touch(r.prompt.data(), (int)hit->size());
-            }
-            for (int k = (int)s.pages.size(); k < need; k++) {
-                s.pages.push_back(take_page());
-            }
+            // the request's stop sequences in the reference's word-list layout (the engine samples the FIRST token)
+            build_word_list(r.stop, sw.data() + (size_t)i * 2 * STOP_LW);
+            any_stop |= !r.stop.empty();
+            FTCF_CHECK_ARG(!hit || n == 1, "batcher: a prefix hit is admitted alone");
+            take_slot_pages(sis[i], r, hit);
         }
         FTCF_HIP_CHECK(hipMemcpy(d_prompt, ids.data(), ids.size() * 4, hipMemcpyHostToDevice));
         FTCF_HIP_CHECK(hipMemcpy(d_plen, lens.data(), (size_t)n * 4, hipMemcpyHostToDevice));
@@ -645,21 +419,11 @@ struct ftcf_batcher {
             std::vector<int> row(max_pages, 0);
             std::copy(slots[si].pages.begin(), slots[si].pages.end(), row.begin());
             FTCF_HIP_CHECK(hipMemcpy(d_pt + (size_t)si * max_pages, row.data(), (size_t)max_pages * 4, hipMemcpyHostToDevice));
-            e->prefill_begin  = hit_tokens;
-            e->prefill_prefix = [this, si, S, hit_tokens] {
+            PrefillFrom from(e, hit_tokens, [this, si, S, hit_tokens] {
                 launch_gather_pages_to_kv(e->k_cache, e->v_cache, kpool, vpool, d_pt + (size_t)si * max_pages, e->L, e->nhl, e->dh, S + 1,
                                           hit_tokens, P, pool_layer_elems, e->stream);
-            };
-            try {
-                e->forward(a);
-            }
-            catch (...) {
-                e->prefill_begin  = 0;
-                e->prefill_prefix = nullptr;
-                throw;
-            }
-            e->prefill_begin  = 0;
-            e->prefill_prefix = nullptr;
+            });
+            e->forward(a);
         }
         else {
             e->forward(a);  // host synchronous: K/V of row i, positions [0, len_i), are in the engine's cache [L][n][nh][S + 1][dh]
@@ -692,23 +456,20 @@ struct ftcf_batcher {
                                        d_pt + (size_t)si * max_pages + hit_tokens / P, e->L, e->nhl, e->dh, S + 1, len - hit_tokens, P,
                                        pool_layer_elems, st, (size_t)n * row_kv);
             // per-slot state of the decode steps
-            const int      keff = (r.top_k == 0 && r.top_p == 0.f) ? 1 : std::min(r.top_k, 1024);  // BaseSamplingLayer: (0, 0) = greedy
+            const int      k_eff = keff(r.top_k, r.top_p);
             const float    ptk = (r.top_p == 0.f) ? 1.f : r.top_p;
             const uint8_t  zero8 = 0;
             const uint64_t one = 1;
             const float    zf = 0.f;
             FTCF_HIP_CHECK(hipMemcpyAsync(d_len + si, &len, 4, hipMemcpyHostToDevice, st));
             FTCF_HIP_CHECK(hipMemcpyAsync(d_tok + si, &first, 4, hipMemcpyHostToDevice, st));
-            FTCF_HIP_CHECK(hipMemcpyAsync(d_topk + si, &keff, 4, hipMemcpyHostToDevice, st));
+            FTCF_HIP_CHECK(hipMemcpyAsync(d_topk + si, &k_eff, 4, hipMemcpyHostToDevice, st));
             FTCF_HIP_CHECK(hipMemcpyAsync(d_ptopk + si, &ptk, 4, hipMemcpyHostToDevice, st));
             FTCF_HIP_CHECK(hipMemcpyAsync(d_ptopp + si, &r.top_p, 4, hipMemcpyHostToDevice, st));
             FTCF_HIP_CHECK(hipMemcpyAsync(d_temp + si, &r.temperature, 4, hipMemcpyHostToDevice, st));
             FTCF_HIP_CHECK(hipMemcpyAsync(d_rep + si, &r.repetition_penalty, 4, hipMemcpyHostToDevice, st));
             // the slot's token history, time-major column si: prompt, then the first token
-            s.hist.assign(r.prompt.begin(), r.prompt.end());
-            s.hist.push_back(first);
-            s.stop = r.stop;
-            s.repetition_penalty = r.repetition_penalty;
+            const int done = start_slot(si, r, first, e->cfg.end_id) ? 1 : 0;
             FTCF_HIP_CHECK(hipMemcpy2DAsync(d_hist + si, (size_t)max_batch * 4, s.hist.data(), 4, 4, s.hist.size(),
                                             hipMemcpyHostToDevice, st));
             FTCF_HIP_CHECK(hipMemcpyAsync(d_seed + si, &r.seed, 8, hipMemcpyHostToDevice, st));
@@ -716,52 +477,14 @@ struct ftcf_batcher {
             FTCF_HIP_CHECK(hipMemcpyAsync(d_cum + si, &zf, 4, hipMemcpyHostToDevice, st));
             FTCF_HIP_CHECK(hipMemcpyAsync(d_fin + si, &zero8, 1, hipMemcpyHostToDevice, st));
             FTCF_HIP_CHECK(hipStreamSynchronize(st));  // the host temporaries above die here
-            s.active = true;
-            s.id = r.id;
-            s.len = len;
-            s.generated = 1;
-            s.max_new = r.max_new;
-            const int done = (first == e->cfg.end_id || s.generated >= s.max_new || hits_stop_word(s)) ? 1 : 0;
             ev.push_back(Event{r.id, first, done, first_lp[i]});  // (the token callback fires when the admission has succeeded: step())
             ev.back().top_ids.assign(first_top_ids.begin() + (size_t)i * want_top, first_top_ids.begin() + (size_t)(i + 1) * want_top);
             ev.back().top_lp.assign(first_top_lp.begin() + (size_t)i * want_top, first_top_lp.begin() + (size_t)(i + 1) * want_top);
             if (done) {
                 const uint8_t one8 = 1;
                 FTCF_HIP_CHECK(hipMemcpy(d_fin + si, &one8, 1, hipMemcpyHostToDevice));
-                if (prefix_on) {
-                    deferred.push_back(si);  // (its prompt pages are inserted first: commit())
-                }
-                else {
-                    release(s);
-                }
+                end_with_first_token(si);  // (prefix cache: its prompt pages are inserted first, commit())
             }
-        }
-    }
-    // a successful admission of ordinary requests: their full prompt blocks enter the index (first writer wins), then the slots
-    // whose request ended with its first token are released
-    void commit(const std::vector<int>& sis, const std::vector<Request>& rs, int hit_tokens = 0)
-    {
-        if (!prefix_on) {
-            return;
-        }
-        for (size_t i = 0; i < sis.size(); i++) {
-            const Request& r = rs[i];
-            const int      S = (int)r.prompt.size();
-            pindex.insert(r.prompt.data(), S / P, slots[sis[i]].pages, page_ref);
-            px_lookups++;
-            px_prompt_tokens += S;
-            px_hit_tokens += hit_tokens;
-            px_computed_tokens += S - hit_tokens;
-        }
-        for (const int si : deferred) {
-            release(slots[si]);
-        }
-        deferred.clear();
-    }
-    void clear_prefix_cache()
-    {
-        for (int pg; (pg = pindex.evict_one(page_ref)) >= 0;) {
-            drop_page(pg);
         }
     }
 
@@ -779,23 +502,7 @@ struct ftcf_batcher {
     // of the shared one otherwise
     void prepare_append(BeamGroup& g, const int pos, const std::vector<uint8_t>& fin, hipStream_t st)
     {
-        std::vector<int> pairs;
-        for (int k = 0; k < g.K; k++) {
-            if (fin[k]) {
-                continue;  // (a finished beam appends nothing: it keeps what it shares)
-            }
-            std::vector<int>& l = g.lists[k];
-            if (pos / P >= (int)l.size()) {
-                l.push_back(take_page());
-            }
-            else if (page_ref[l[pos / P]] > 1) {
-                const int old = l[pos / P], pg = take_page();
-                pairs.push_back(old);
-                pairs.push_back(pg);
-                drop_page(old);
-                l[pos / P] = pg;
-            }
-        }
+        const std::vector<int> pairs = take_append_pages(g, pos, fin);
         if (!pairs.empty()) {
             FTCF_HIP_CHECK(hipMemcpyAsync(d_pairs, pairs.data(), pairs.size() * 4, hipMemcpyHostToDevice, st));
             const size_t page_elems = (size_t)e->nhl * P * e->dh;
@@ -808,22 +515,13 @@ struct ftcf_batcher {
     }
     void release_group(const int si)
     {
-        auto it = groups.find(si);
-        if (it == groups.end()) {
+        const int K = drop_group(si);
+        if (K == 0) {
             return;
         }
-        BeamGroup&           g = it->second;
-        std::vector<uint8_t> ones(g.K, 1), zeros(g.K, 0);
-        for (int k = 0; k < g.K; k++) {
-            for (int pg : g.lists[k]) {
-                drop_page(pg);
-            }
-            slots[si + k].active = false;
-            slots[si + k].group  = -1;
-        }
-        (void)hipMemcpy(d_fin + si, ones.data(), g.K, hipMemcpyHostToDevice);
-        (void)hipMemcpy(d_isbeam + si, zeros.data(), g.K, hipMemcpyHostToDevice);
-        groups.erase(it);
+        std::vector<uint8_t> ones(K, 1), zeros(K, 0);
+        (void)hipMemcpy(d_fin + si, ones.data(), K, hipMemcpyHostToDevice);
+        (void)hipMemcpy(d_isbeam + si, zeros.data(), K, hipMemcpyHostToDevice);
     }
     // gatherTree over the group's steps (decoding_kernels.cu:452-583, as GptNeoXOp.forward returns its beams: [K][n + max_new]
     // ids padded with end_id, lengths, cum_log_probs), the result parked until it is fetched, the slots and pages freed
@@ -866,15 +564,8 @@ struct ftcf_batcher {
     {
         Range       rg("ftcf.batcher.admit_beam");
         hipStream_t st = e->stream;
-        const int   K = r.beam_width, n = (int)r.prompt.size(), need = (n + r.max_new + P - 1) / P;
-        BeamGroup   g;
-        g.id      = r.id;
-        g.si      = si;
-        g.K       = K;
-        g.n       = n;
-        g.max_new = r.max_new;
-        g.budget  = K * need;
-        g.penalised = r.repetition_penalty != 1.f;
+        const int   K = r.beam_width, n = (int)r.prompt.size();
+        const bool  has_min = r.min_length > 0, has_stop = !r.stop.empty();
         FTCF_HIP_CHECK(hipMemcpy(d_prompt, r.prompt.data(), (size_t)n * 4, hipMemcpyHostToDevice));
         FTCF_HIP_CHECK(hipMemcpy(d_plen, &n, 4, hipMemcpyHostToDevice));
         ftcf_forward_args a{};
@@ -894,47 +585,20 @@ struct ftcf_batcher {
         a.n_len_penalty = 1;
         a.output_ids = d_pout;
         a.sequence_lengths = d_pseq;
-        g.has_min  = r.min_length > 0;
-        g.has_stop = !r.stop.empty();
-        if (g.has_min) {
+        if (has_min) {
             a.min_length = &r.min_length;
             a.n_min_length = 1;
             FTCF_HIP_CHECK(hipMemcpy(d_bmin + si, &r.min_length, 4, hipMemcpyHostToDevice));
         }
-        if (g.has_stop) {  // the group's stop words stay on the device for its beam steps (checked along the parent chain there)
-            std::vector<int> sw(2 * STOP_LW, 0);
-            std::fill(sw.begin() + STOP_LW, sw.end(), -1);
-            int pos = 0, k = 0;
-            for (const auto& wd : r.stop) {
-                std::copy(wd.begin(), wd.end(), sw.begin() + pos);
-                pos += (int)wd.size();
-                sw[STOP_LW + k++] = pos;
-            }
+        if (has_stop) {  // the group's stop words stay on the device for its beam steps (checked along the parent chain there)
+            std::vector<int> sw(2 * STOP_LW);
+            build_word_list(r.stop, sw.data());
             FTCF_HIP_CHECK(hipMemcpy(d_bsw + (size_t)si * 2 * STOP_LW, sw.data(), sw.size() * 4, hipMemcpyHostToDevice));
             a.stop_words_list = d_bsw + (size_t)si * 2 * STOP_LW;
             a.stop_words_len = STOP_LW;
         }
         e->forward(a);  // host synchronous; the engine's buffers keep the request's state: step_ids / parent_ids [n + 1][K], ...
-        // the prompt's pages, shared by every beam
-        std::vector<int> shared;
-        try {
-            for (int i = 0; i < (n + P - 1) / P; i++) {
-                shared.push_back(take_page());
-            }
-        }
-        catch (...) {  // (no group owns them yet: step()'s release_group(si) would not find them)
-            for (int pg : shared) {
-                page_ref[pg] = 1;
-                drop_page(pg);
-            }
-            throw;
-        }
-        g.lists.assign(K, shared);
-        for (int pg : shared) {
-            page_ref[pg] = K;
-        }
-        groups[si] = g;
-        BeamGroup& G = groups[si];
+        BeamGroup& G = open_group(si, r);  // the prompt's pages, shared by every beam
         upload_group_tables(G, st);
         const size_t row_kv = (size_t)e->nhl * (n + 1) * e->dh;
         launch_scatter_kv_to_pages(e->k_cache, e->v_cache, kpool, vpool, d_pt + (size_t)si * max_pages, e->L, e->nhl, e->dh, n + 1, n, P,
@@ -949,14 +613,11 @@ struct ftcf_batcher {
         std::vector<int>     lens(K, n), first(K);
         std::vector<uint8_t> ones(K, 1), fin(K, 0);
         FTCF_HIP_CHECK(hipMemcpy(first.data(), e->step_ids + (size_t)n * K, (size_t)K * 4, hipMemcpyDeviceToHost));
+        std::vector<int> hist(r.prompt);  // (stop_criteria_kernels.cu:24-83 on prompt + first token: every beam's parent is the prompt)
+        hist.push_back(0);
         for (int k = 0; k < K; k++) {
-            fin[k] = first[k] == e->cfg.end_id ? 1 : 0;
-            for (const auto& wd : r.stop) {  // (stop_criteria_kernels.cu:24-83 on prompt + first token: every beam's parent is the prompt)
-                if (!wd.empty() && (int)wd.size() <= n + 1 && wd.back() == first[k]
-                    && std::equal(wd.begin(), wd.end() - 1, r.prompt.end() - (wd.size() - 1))) {
-                    fin[k] = 1;
-                }
-            }
+            hist.back() = first[k];
+            fin[k]      = (first[k] == e->cfg.end_id || ends_with_stop(r.stop, hist)) ? 1 : 0;
         }
         FTCF_HIP_CHECK(hipMemcpyAsync(d_fin + si, fin.data(), (size_t)K, hipMemcpyHostToDevice, st));
         FTCF_HIP_CHECK(hipMemcpyAsync(d_len + si, lens.data(), (size_t)K * 4, hipMemcpyHostToDevice, st));
@@ -967,18 +628,7 @@ struct ftcf_batcher {
         FTCF_HIP_CHECK(hipMemcpyAsync(d_bdiv + si, &r.diversity, 4, hipMemcpyHostToDevice, st));
         FTCF_HIP_CHECK(hipMemcpyAsync(d_blen + si, &r.len_penalty, 4, hipMemcpyHostToDevice, st));
         FTCF_HIP_CHECK(hipStreamSynchronize(st));
-        for (int k = 0; k < K; k++) {
-            Slot& s  = slots[si + k];
-            s.active = true;
-            s.group  = si;
-            s.id     = r.id;
-            s.len    = n;
-            s.pages.clear();
-            s.hist.clear();
-            s.stop.clear();
-            s.repetition_penalty = 1.f;  // (the beam kernels apply the request's penalty themselves)
-        }
-        G.generated = 1;
+        start_group_slots(G);
         bool all_fin = true;
         for (int k = 0; k < K; k++) {
             all_fin &= fin[k] != 0;
@@ -1050,20 +700,7 @@ struct ftcf_batcher {
             std::vector<int> parent(g.K);
             FTCF_HIP_CHECK(hipMemcpy(parent.data(), d_bpar + (size_t)si * (max_len + 2) + (size_t)step * g.K, (size_t)g.K * 4,
                                      hipMemcpyDeviceToHost));
-            std::vector<std::vector<int>> nl(g.K);
-            for (int k = 0; k < g.K; k++) {
-                nl[k] = g.lists[parent[k] % g.K];
-                for (int pg : nl[k]) {
-                    page_ref[pg]++;
-                }
-            }
-            for (int k = 0; k < g.K; k++) {
-                for (int pg : g.lists[k]) {
-                    drop_page(pg);
-                }
-            }
-            g.lists = std::move(nl);
-            g.generated += 1;
+            reparent_group(g, parent);
             std::vector<uint8_t> fin(fin_all.begin() + si, fin_all.begin() + si + g.K);
             bool                 all_fin = true;
             for (int k = 0; k < g.K; k++) {
@@ -1365,11 +1002,7 @@ struct ftcf_batcher {
             x.top_lp.assign(top_lp.begin() + (size_t)si * top_n, top_lp.begin() + (size_t)(si + 1) * top_n);
             emit(ev, x);
             if (done) {
-                if (!fin[si]) {
-                    const uint8_t one8 = 1;
-                    FTCF_HIP_CHECK(hipMemcpy(d_fin + si, &one8, 1, hipMemcpyHostToDevice));
-                }
-                release(s);
+                FTCF_HIP_CHECK(retire(si, fin[si] != 0));
             }
         }
         if (!groups.empty()) {
@@ -1377,289 +1010,79 @@ struct ftcf_batcher {
         }
     }
 
-    int  host_max_top_k = 1, host_any_top_p = 0;
-    bool host_any_temperature = false, host_any_repetition = false;
-    std::vector<int>   slot_topk;
-    std::vector<float> slot_temp;
+    // ONE admission as plan_admission() described it: the prompt phase (with the chunk hook when the plan says so: a decode step
+    // of the running slots after every chunk, whose events are final whatever happens to the admission and reach the callback at
+    // once), then commit -- or, when anything throws, the rollback by kind (batcher_sched.h: Admission).  The admission's own
+    // events reach `ev` and the callback only when it has succeeded: a failed one is retried, and nobody sees a first token twice.
+    void run_admission(Admission& a, std::vector<Event>& ev)
+    {
+        std::vector<Event> own, between;
+        const int          n = a.kind == Kind::chunked_one ? 1 : (int)a.requests.size();
+        try {
+            if (a.install_hook) {
+                hook_ev          = &between;
+                e->prefill_chunk = prefill_chunk;
+                // (any_active() where the beam admission once asked "an ordinary slot is active, or a group exists": the same
+                //  set, since `slot.group >= 0 && slot.active` <=> the group is in `groups` whenever a hook can run -- groups
+                //  enter the map after the admission's forward() and leave it with their slots, drop_group)
+                e->prefill_hook = [this] {
+                    if (any_active()) {
+                        refresh_host_flags();
+                        decode(*hook_ev);
+                    }
+                };
+            }
+            if (a.kind == Kind::beam) {
+                admit_beam(a.slots[0], a.requests[0], own);
+            }
+            else {
+                admit(a.slots, a.requests, n, own, a.kind == Kind::hit ? &a.hit : nullptr);
+            }
+        }
+        catch (...) {
+            // pages to the pool, slots free, the requests back at the head of the queue in their order, the admission's own
+            // events dropped (the caller sees the exception, not half an admission)
+            e->prefill_hook = nullptr;
+            hook_ev         = nullptr;
+            (void)hipDeviceSynchronize();
+            (void)hipGetLastError();
+            const long id = a.requests[0].id;
+            rollback(
+                a, [this](int si) { (void)retire(si); },
+                [this, id](int si) {
+                    release_group(si);
+                    beam_results.erase(id);
+                });
+            ev.insert(ev.end(), between.begin(), between.end());
+            throw;
+        }
+        e->prefill_hook = nullptr;
+        hook_ev         = nullptr;
+        if (a.kind != Kind::beam) {  // (beam requests neither read nor populate the prefix cache)
+            commit(a.slots, a.requests, n, (int)a.hit.size() * P);
+        }
+        ev.insert(ev.end(), between.begin(), between.end());
+        ev.insert(ev.end(), own.begin(), own.end());
+        fire(own);
+    }
 
     void step(std::vector<Event>& ev)
     {
         FTCF_HIP_CHECK(hipSetDevice(e->cfg.device));
-        if (slot_topk.empty()) {
-            slot_topk.assign(max_batch, 1);
-            slot_temp.assign(max_batch, 1.f);
-        }
         // the running slots first (a request admitted in this iteration has its first token already)
-        bool any = false;
-        for (const Slot& s : slots) {
-            any |= s.active;
-        }
+        const bool any = any_active();
         if (any) {
             decode(ev);
         }
-        // admissions: as many of the queue's head requests as there are free slots and pages, prefilled as ONE ragged batch
-        std::vector<int>     sis;
-        std::vector<Request> rs;
-        // (prefix cache: the cached pages nobody else holds count as free -- take_page evicts them when the free list runs dry)
-        int                  pages_left = (int)free_pages.size() - reserved_pages() + (prefix_on ? pindex.evictable(page_ref) : 0);
-        std::vector<int>     hit;  // a request with a prefix hit: its cached pages (it is admitted alone)
-        if (!waiting.empty() && waiting.front().beam_width > 1) {
-            // a beam request at the head of the queue: K consecutive free slots and the group's whole page budget, admitted alone
-            const Request& r    = waiting.front();
-            const int      K    = r.beam_width, need = K * (((int)r.prompt.size() + r.max_new + P - 1) / P);
-            int            si0  = -1;
-            for (int si = 0, run = 0; si < max_batch && si0 < 0; si++) {
-                run = slots[si].active ? 0 : run + 1;
-                if (run == K) {
-                    si0 = si - K + 1;
-                }
-            }
-            if (si0 >= 0 && pages_left >= need) {
-                Request rq = std::move(waiting.front());
-                waiting.pop_front();
-                for (int k = 0; k < K; k++) {
-                    slot_topk[si0 + k] = 1;
-                    slot_temp[si0 + k] = 1.f;
-                }
-                // slots are running and the prompt is long: its prompt phase in chunks, a decode step of the running slots after every
-                // chunk (as for a sampled request below; the events of those steps are final whatever happens to the admission)
-                bool running = false;
-                for (const Slot& s : slots) {
-                    running |= s.active;
-                }
-                const bool         chunked = running && prefill_chunk > 0 && (int)rq.prompt.size() > prefill_chunk;
-                std::vector<Event> own, between;
-                try {
-                    if (chunked) {
-                        hook_ev          = &between;
-                        e->prefill_chunk = prefill_chunk;
-                        e->prefill_hook  = [this] {
-                            bool live = false;
-                            for (const Slot& s : slots) {
-                                live |= s.active && s.group < 0;
-                            }
-                            if (live || !groups.empty()) {
-                                refresh_host_flags();
-                                decode(*hook_ev);
-                            }
-                        };
-                    }
-                    admit_beam(si0, rq, own);
-                    e->prefill_hook = nullptr;
-                    hook_ev         = nullptr;
-                }
-                catch (...) {
-                    e->prefill_hook = nullptr;
-                    hook_ev         = nullptr;
-                    (void)hipDeviceSynchronize();
-                    (void)hipGetLastError();
-                    release_group(si0);
-                    beam_results.erase(rq.id);
-                    waiting.push_front(std::move(rq));
-                    ev.insert(ev.end(), between.begin(), between.end());
-                    throw;
-                }
-                ev.insert(ev.end(), between.begin(), between.end());
-                ev.insert(ev.end(), own.begin(), own.end());
-                fire(own, 0);  // (the admission's own events reach the callback only now)
-            }
-            refresh_host_flags();
-            return;
-        }
-        for (int si = 0; si < max_batch && !waiting.empty(); si++) {
-            if (slots[si].active) {
-                continue;
-            }
-            const Request& r    = waiting.front();
-            if (r.beam_width > 1) {
-                break;  // (admitted alone, by the next iteration)
-            }
-            int            need = ((int)r.prompt.size() + r.max_new + P - 1) / P;
-            if (prefix_on) {
-                // at most floor((S - 1) / P) blocks: the last prompt token is always computed (its logits give the first token)
-                // and decode never writes into a cached page
-                std::vector<int> h = pindex.lookup(r.prompt.data(), ((int)r.prompt.size() - 1) / P);
-                if (!h.empty()) {
-                    if (!sis.empty()) {
-                        break;  // (admitted alone, by the next iteration)
-                    }
-                    // the budget without the pages this hit pins: they are in use, not evictable
-                    for (const int pg : h) {
-                        page_ref[pg]++;
-                    }
-                    const int avail = (int)free_pages.size() - reserved_pages() + pindex.evictable(page_ref);
-                    for (const int pg : h) {
-                        page_ref[pg]--;
-                    }
-                    need -= (int)h.size();
-                    if (avail < need) {
-                        break;
-                    }
-                    const int keff = (r.top_k == 0 && r.top_p == 0.f) ? 1 : std::min(r.top_k, 1024);
-                    slot_topk[si]  = keff;
-                    slot_temp[si]  = r.temperature;
-                    sis.push_back(si);
-                    rs.push_back(std::move(waiting.front()));
-                    waiting.pop_front();
-                    hit = std::move(h);
-                    break;
-                }
-            }
-            if (pages_left < need) {
-                break;  // FIFO: nobody overtakes the head of the queue
-            }
-            pages_left -= need;
-            const int keff = (r.top_k == 0 && r.top_p == 0.f) ? 1 : std::min(r.top_k, 1024);
-            slot_topk[si]  = keff;
-            slot_temp[si]  = r.temperature;
-            sis.push_back(si);
-            rs.push_back(std::move(waiting.front()));
-            waiting.pop_front();
-        }
-        if (!hit.empty()) {
-            // a prefix hit, alone: the tail's prompt phase from the hit offset, in chunks with decode steps of the running slots
-            // between them when it is long (as a chunked admission below)
-            const int          hit_tokens = (int)hit.size() * P;
-            std::vector<Event> own, between;
-            try {
-                if (any && prefill_chunk > 0 && (int)rs[0].prompt.size() - hit_tokens > prefill_chunk) {
-                    hook_ev          = &between;
-                    e->prefill_chunk = prefill_chunk;
-                    e->prefill_hook  = [this] {
-                        bool live = false;
-                        for (const Slot& s : slots) {
-                            live |= s.active;
-                        }
-                        if (live) {
-                            refresh_host_flags();
-                            decode(*hook_ev);
-                        }
-                    };
-                }
-                admit(sis, rs, own, &hit);
-                e->prefill_hook = nullptr;
-                hook_ev         = nullptr;
-            }
-            catch (...) {
-                // the hit's references go with the slot's page list; nothing is inserted
-                e->prefill_hook = nullptr;
-                hook_ev         = nullptr;
-                (void)hipDeviceSynchronize();
-                (void)hipGetLastError();
-                ev.insert(ev.end(), between.begin(), between.end());
-                release(slots[sis[0]]);
-                const uint8_t one8 = 1;
-                (void)hipMemcpy(d_fin + sis[0], &one8, 1, hipMemcpyHostToDevice);
-                waiting.push_front(std::move(rs[0]));
-                throw;
-            }
-            commit(sis, rs, hit_tokens);
-            ev.insert(ev.end(), between.begin(), between.end());
-            ev.insert(ev.end(), own.begin(), own.end());
-            fire(own, 0);
-            refresh_host_flags();
-            return;
-        }
-        bool any_long = false;
-        for (const Request& r : rs) {
-            any_long |= prefill_chunk > 0 && (int)r.prompt.size() > prefill_chunk;
-        }
-        if (!sis.empty() && any && any_long) {
-            // slots are running and a long prompt arrives: one request at a time, its prompt phase in chunks with a decode step of
-            // the running slots after every chunk (events of those steps are final whatever happens to the admission)
-            while (!sis.empty()) {
-                const std::vector<int>     one_si{sis.front()};
-                const std::vector<Request> one_r{rs.front()};
-                std::vector<Event>         own, between;
-                bool                       running = false;
-                for (const Slot& s : slots) {
-                    running |= s.active;
-                }
-                try {
-                    if (running) {
-                        hook_ev          = &between;
-                        e->prefill_chunk = prefill_chunk;
-                        e->prefill_hook  = [this] {
-                            bool live = false;
-                            for (const Slot& s : slots) {
-                                live |= s.active;
-                            }
-                            if (live) {
-                                refresh_host_flags();
-                                decode(*hook_ev);
-                            }
-                        };
-                    }
-                    admit(one_si, one_r, own);
-                    e->prefill_hook = nullptr;
-                    hook_ev         = nullptr;
-                }
-                catch (...) {
-                    e->prefill_hook = nullptr;
-                    hook_ev         = nullptr;
-                    (void)hipDeviceSynchronize();
-                    (void)hipGetLastError();
-                    ev.insert(ev.end(), between.begin(), between.end());
-                    for (const int si : sis) {  // this request and the ones not yet admitted go back to the queue's head
-                        release(slots[si]);
-                        const uint8_t one8 = 1;
-                        (void)hipMemcpy(d_fin + si, &one8, 1, hipMemcpyHostToDevice);
-                    }
-                    for (size_t i = rs.size(); i-- > 0;) {
-                        waiting.push_front(std::move(rs[i]));
-                    }
-                    throw;
-                }
-                commit(one_si, one_r);
-                ev.insert(ev.end(), between.begin(), between.end());
-                ev.insert(ev.end(), own.begin(), own.end());
-                fire(own, 0);
-                sis.erase(sis.begin());
-                rs.erase(rs.begin());
-            }
-        }
-        if (!sis.empty()) {
-            const size_t ev0 = ev.size();
-            try {
-                admit(sis, rs, ev);
-            }
-            catch (...) {
-                // the whole admission is rolled back: pages to the pool, slots free, the requests back at the head of the
-                // queue in their order, their events dropped (the caller sees the exception, not half an admission)
-                (void)hipDeviceSynchronize();
-                (void)hipGetLastError();
-                for (const int si : sis) {
-                    release(slots[si]);
-                    const uint8_t one8 = 1;
-                    (void)hipMemcpy(d_fin + si, &one8, 1, hipMemcpyHostToDevice);
-                }
-                for (size_t i = rs.size(); i-- > 0;) {
-                    waiting.push_front(std::move(rs[i]));
-                }
-                ev.resize(ev0);
-                throw;
-            }
-            commit(sis, rs);
-            fire(ev, ev0);
+        // then what plan_admission() finds room for: a beam request or a prefix hit alone, else the queue's head requests as one
+        // ragged batch -- or, with slots running and a long prompt among them, one after the other
+        Admission a = plan_admission(any);
+        if (a.kind != Kind::none) {
+            do {
+                run_admission(a, ev);
+            } while (a.kind == Kind::chunked_one && next_chunked(a));
         }
         refresh_host_flags();
-    }
-    // host view of the running slots' sampling parameters (kernel selection and LDS sizing of the sampling kernels): after every
-    // admission, and before a decode step that runs inside an admission (a request admitted a moment ago is already running)
-    void refresh_host_flags()
-    {
-        host_max_top_k = 1;
-        host_any_top_p = 0;
-        host_any_temperature = false;
-        host_any_repetition = false;
-        for (int si = 0; si < max_batch; si++) {
-            if (slots[si].active) {
-                host_any_repetition |= (slots[si].repetition_penalty != 1.f);
-                host_max_top_k = std::max(host_max_top_k, slot_topk[si]);
-                host_any_top_p |= (slot_topk[si] == 0);
-                host_any_temperature |= (slot_temp[si] != 1.f);
-            }
-        }
     }
 };
 
@@ -1901,9 +1324,7 @@ extern "C" int ftcf_batcher_cancel(ftcf_batcher_t b, long request_id, int* found
             }
             if (s.active && s.id == request_id) {
                 FTCF_HIP_CHECK(hipSetDevice(b->e->cfg.device));
-                const uint8_t one8 = 1;
-                FTCF_HIP_CHECK(hipMemcpy(b->d_fin + si, &one8, 1, hipMemcpyHostToDevice));
-                b->release(s);
+                FTCF_HIP_CHECK(b->retire(si));
                 hit = 1;
             }
         }

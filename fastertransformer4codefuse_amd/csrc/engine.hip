@@ -946,29 +946,7 @@ void ftcf_gptneox::begin(const ftcf_forward_args& a)
         FTCF_HIP_CHECK(hipMemsetAsync(spec_ndraft, 0, 4 * sizeof(int), stream));
     }
     if (pplan.ok || rplan.ok) {
-        const size_t cache_l = (size_t)B * nhl * s_max * dh;
-        std::vector<PersistLayer> pl(L);
-        for (int l = 0; l < L; l++) {
-            const LayerWeights& w = layers[l];
-            PersistLayer&       r = pl[l];
-            r.ln1_g = w.ln1_g;
-            r.ln1_b = w.ln1_b;
-            r.ln2_g = w.ln2_g;
-            r.ln2_b = w.ln2_b;
-            r.w_qkv = w.qkv.kernel;
-            r.w_ffn1 = w.ffn1.kernel;
-            r.w_out = w.attn_out.kernel;
-            r.w_ffn2 = w.ffn2.kernel;
-            r.s_qkv = w.qkv.scale;
-            r.s_ffn1 = w.ffn1.scale;
-            r.s_out = w.attn_out.scale;
-            r.s_ffn2 = w.ffn2.scale;
-            r.b_qkv = w.qkv.bias;
-            r.b_ffn1 = w.ffn1.bias;
-            r.b_res = w.ffn2.bias;
-            r.k_cache = k_cache + l * cache_l;
-            r.v_cache = v_cache + l * cache_l;
-        }
+        const std::vector<PersistLayer> pl = persist_layer_table(layers, k_cache, v_cache, (size_t)B * nhl * s_max * dh);
         FTCF_HIP_CHECK(hipMemcpyAsync(d_players, pl.data(), sizeof(PersistLayer) * L, hipMemcpyHostToDevice, stream));
         if (rplan.ok) {  // the rows kernel's flags are monotone tags of (step, layer): steps repeat from request to request
             FTCF_HIP_CHECK(hipMemsetAsync(rows_ws, 0, rows_flag_bytes(rplan, B, nhl), stream));

@@ -6,8 +6,9 @@
 #include <float.h>
 #include <stdio.h>
 
-#include <stdexcept>
 #include <string>
+
+#include "ftcf_error.h"  // ftcf::Error, FTCF_CHECK_ARG
 
 namespace ftcf {
 
@@ -33,24 +34,12 @@ constexpr int TILE_K_I8     = 64;
 constexpr int TILE_K_F16    = 32;
 constexpr int TILE_BYTES    = 1024;
 
-struct Error : public std::runtime_error {
-    int code;
-    Error(int c, const std::string& s): std::runtime_error(s), code(c) {}
-};
-
 #define FTCF_HIP_CHECK(expr)                                                                                           \
     do {                                                                                                               \
         hipError_t _e = (expr);                                                                                        \
         if (_e != hipSuccess) {                                                                                        \
             throw ::ftcf::Error(-2, std::string("HIP error ") + hipGetErrorString(_e) + " at " + __FILE__ + ":"       \
                                         + std::to_string(__LINE__) + " (" #expr ")");                                  \
-        }                                                                                                              \
-    } while (0)
-
-#define FTCF_CHECK_ARG(cond, msg)                                                                                      \
-    do {                                                                                                               \
-        if (!(cond)) {                                                                                                 \
-            throw ::ftcf::Error(-1, std::string("invalid argument: ") + (msg) + " [" #cond "]");                       \
         }                                                                                                              \
     } while (0)
 

@@ -16,6 +16,7 @@
 // per-stage GEMV launches -- cut ACROSS these units on purpose and stay in engine.hip.
 #pragma once
 #include <functional>
+#include <vector>
 
 #include "kernels.h"
 
@@ -30,6 +31,34 @@ struct LayerWeights {  // models/gptneox/GptNeoXDecoderLayerWeight.h
     const f16 *ln1_g, *ln1_b, *ln2_g, *ln2_b;
     DenseWeight qkv, attn_out, ffn1, ffn2;
 };
+// the layers as the persistent / rows kernels read them; layer l's K/V at k_base / v_base + l * layer_stride
+inline std::vector<PersistLayer> persist_layer_table(const std::vector<LayerWeights>& layers, f16* k_base, f16* v_base,
+                                                     size_t layer_stride)
+{
+    std::vector<PersistLayer> pl(layers.size());
+    for (size_t l = 0; l < layers.size(); l++) {
+        const LayerWeights& w = layers[l];
+        PersistLayer&       r = pl[l];
+        r.ln1_g = w.ln1_g;
+        r.ln1_b = w.ln1_b;
+        r.ln2_g = w.ln2_g;
+        r.ln2_b = w.ln2_b;
+        r.w_qkv = w.qkv.kernel;
+        r.w_ffn1 = w.ffn1.kernel;
+        r.w_out = w.attn_out.kernel;
+        r.w_ffn2 = w.ffn2.kernel;
+        r.s_qkv = w.qkv.scale;
+        r.s_ffn1 = w.ffn1.scale;
+        r.s_out = w.attn_out.scale;
+        r.s_ffn2 = w.ffn2.scale;
+        r.b_qkv = w.qkv.bias;
+        r.b_ffn1 = w.ffn1.bias;
+        r.b_res = w.ffn2.bias;
+        r.k_cache = k_base + l * layer_stride;
+        r.v_cache = v_base + l * layer_stride;
+    }
+    return pl;
+}
 
 // C[m, n] = epilogue(A[m, k] x W) on stream s; `slot` names the workspace region of the burst GEMM this call may use
 // (0 QKV, 1 FFN1, 2 out-proj, 3 FFN2: the four GEMMs of a layer may be in flight together on two streams).  The engine

@@ -802,3 +802,56 @@ def test_the_decode_step_runs_the_rows_kernel_over_paged_kv(gh, monkeypatch, mod
                 raise AssertionError((form, k, got[k], ref[k]))
         assert np.array_equal(beam[0], b_ref[0]) and np.array_equal(beam[1], b_ref[1]), form
         np.testing.assert_allclose(beam[2], b_ref[2], rtol=5e-3, atol=5e-3)
+
+
+def test_the_four_admission_kinds_in_one_batcher_lifetime(gh, monkeypatch):
+    """One batcher with the prefix cache, chunks of 4 and pages of 8 runs every kind of admission of batcher_sched.h through the one
+    guarded path of step(): a ragged pair into the empty batcher, a long prompt in chunks while the pair decodes, a repeat of the
+    first prompt (a prefix hit of two pages whose 7-token tail is chunked too) and a beam request of width 2 (chunked as well).
+    Every greedy stream is the engine's alone, token exact; the beam hypotheses are the engine's own; the token callback sees
+    exactly the concatenation of what the step() calls return -- no first token twice; after clear_prefix_cache the pool is whole."""
+    from fastertransformer4codefuse_amd.batcher import ContinuousBatcher
+    monkeypatch.setenv("FTCF_BATCHER_PREFILL_CHUNK", "4")
+    cfg, w, z = load_tiny()
+    V, end_id = cfg["vocab_size"], cfg["end_id"]
+    op = gh.make_op(cfg, w)
+    rng = np.random.RandomState(29)
+    p23, p13, p9 = (rng.randint(3, V, size=n).tolist() for n in (23, 13, 9))
+    reqs = [(p23, 16), (z["prompt_b"].tolist(), 14), (p13, 6), (p23, 5)]
+    alone = {id(p): _alone(gh, op, p, max(n for q, n in reqs if q is p), V, end_id)[0] for p, _ in reqs}
+    ref = [alone[id(p)][:n] for p, n in reqs]
+    b_ref = _beam_alone(gh, op, p9, 6, V, 2)
+    cb = ContinuousBatcher(op, max_batch=6, page_tokens=8, num_pages=40, max_seq_len=64, prefix_cache=True)
+    ids, got, per_step, streamed, returned, bid = {}, {}, [], [], [], None
+    cb.set_token_callback(lambda rid, tok, fin: streamed.append((rid, tok, fin)))
+    arrivals = {0: [0, 1], 2: [2], 3: [3], 4: ["beam"]}
+    it = 0
+    while arrivals or cb.busy():
+        for k in arrivals.pop(it, []):
+            if k == "beam":
+                bid = cb.submit_beam(p9, 6, 2, 0.0, 0.0, 1.0, 1.0)
+            else:
+                ids[cb.submit(reqs[k][0], reqs[k][1])] = k
+        evs = cb.step()
+        returned += evs
+        per_step.append([ids.get(rid, "beam") for rid, _, _ in evs])
+        for rid, tok, fin in evs:
+            if rid != bid:
+                got.setdefault(ids[rid], []).append(tok)
+        it += 1
+        assert it < 1000
+    for k in range(len(reqs)):
+        assert got[k] == ref[k], (k, got[k], ref[k])
+    assert streamed == returned
+    assert [e for e in returned if e[0] == bid] == [(bid, -1, True)]
+    # call 0: the pair as one ragged batch; call 2: the 13-token prompt in chunks of 4, 4, 4, 1 -- the pair decodes once before it and
+    # once after each of the first three chunks; call 3: the repeat takes its two cached pages and computes 7 tokens as 4 + 3
+    assert per_step[0] == [0, 1] and per_step[2] == [0, 1] * 4 + [2], per_step[:4]
+    assert per_step[3] == [0, 1, 2] * 2 + [3], per_step[:4]
+    st = cb.prefix_stats()
+    assert st["hit_tokens"] == 16 and st["lookups"] == 4, st
+    out, lens, _ = cb.beam_result(bid)
+    assert np.array_equal(out, b_ref[0]) and np.array_equal(lens, b_ref[1]), (out, b_ref[0])
+    cb.set_token_callback(None)
+    cb.clear_prefix_cache()
+    assert cb.status() == {"waiting": 0, "running": 0, "free_pages": 40}
