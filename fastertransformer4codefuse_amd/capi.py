@@ -115,7 +115,8 @@ EXPORTED = [
     "ftcf_fpA_intB_gemm", "ftcf_fp16_gemm", "ftcf_lm_head", "ftcf_lm_head_layernorm", "ftcf_lm_head_log_probs",
     "ftcf_gemm_smallm_group", "ftcf_gemm_smallm_workspace_bytes", "ftcf_gemm_smallm_ticket_bytes",
     "ftcf_residual_dual_layernorm", "ftcf_add_bias_residual", "ftcf_ln_gemv", "ftcf_residual_gemv", "ftcf_residual_gemv_workspace_bytes", "ftcf_layernorm", "ftcf_add_bias_attn_ffn_residual",
-    "ftcf_masked_multihead_attention", "ftcf_masked_multihead_attention_workspace", "ftcf_context_attention",
+    "ftcf_masked_multihead_attention", "ftcf_masked_multihead_attention_workspace", "ftcf_masked_multihead_attention_beams",
+    "ftcf_context_attention",
     "ftcf_verify_attention", "ftcf_verify_attention_workspace", "ftcf_ngram_draft",
     "ftcf_paged_attention", "ftcf_scatter_kv_to_pages", "ftcf_gather_pages_to_kv",
     "ftcf_dynamic_decode_step", "ftcf_beam_search_step",

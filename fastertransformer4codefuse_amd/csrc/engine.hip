@@ -383,6 +383,41 @@ extern "C" size_t ftcf_masked_multihead_attention_workspace(int B, int nh, int d
 {
     return mmha_workspace_bytes(B, nh, dh, mmha_pick_nsplit(B, nh, s_max));
 }
+// fills the parameters of one stand-alone fp16 launch (cache_indir NULL: no beams), clears the granules and launches
+static void abi_launch_mmha(const void* qkv, const void* qkv_bias, void* k_cache, void* v_cache, const int* seq_len,
+                            const int* pad_count, const uint8_t* masked_tokens, const uint8_t* finished, const int* cache_indir,
+                            int beam_width, int max_input_len, int B, int nh, int dh, int rot, int s_max, int step, int nsplit,
+                            void* ctx, void* workspace, size_t workspace_bytes, hipStream_t stream)
+{
+    MmhaParams p{};
+    p.qkv = (const f16*)qkv;
+    p.qkv_bias = (const f16*)qkv_bias;
+    p.k_cache = (f16*)k_cache;
+    p.v_cache = (f16*)v_cache;
+    p.seq_len = seq_len;
+    p.pad_count = pad_count;
+    p.masked_tokens = masked_tokens;
+    p.finished = finished;
+    p.d_step = nullptr;
+    p.step = step;
+    p.B = B;
+    p.nh = nh;
+    p.dh = dh;
+    p.rot = rot;
+    p.s_max = s_max;
+    p.ctx = (f16*)ctx;
+    p.gran = (unsigned long long*)workspace;
+    p.layer = 0;
+    p.nsplit = nsplit;
+    p.cache_indir = cache_indir;
+    p.beam_width = beam_width;
+    p.max_input_len = max_input_len;
+    p.indir_plane = (size_t)B * s_max;
+    FTCF_CHECK_ARG(workspace_bytes >= mmha_workspace_bytes(B, nh, dh, p.nsplit), "MMHA workspace too small");
+    // the granule tags must not match anything left from an earlier call
+    FTCF_HIP_CHECK(hipMemsetAsync(p.gran, 0, mmha_workspace_bytes(B, nh, dh, p.nsplit), stream));
+    launch_mmha(p, stream);
+}
 extern "C" int ftcf_masked_multihead_attention(const void* qkv, const void* qkv_bias, void* k_cache, void* v_cache,
                                                const int* seq_len, const int* pad_count, const uint8_t* masked_tokens,
                                                const uint8_t* finished, int B, int nh, int dh, int rot, int s_max,
@@ -391,30 +426,66 @@ extern "C" int ftcf_masked_multihead_attention(const void* qkv, const void* qkv_
 {
     return guarded([&] {
         require_device();
-        MmhaParams p{};
-        p.qkv = (const f16*)qkv;
-        p.qkv_bias = (const f16*)qkv_bias;
-        p.k_cache = (f16*)k_cache;
-        p.v_cache = (f16*)v_cache;
-        p.seq_len = seq_len;
-        p.pad_count = pad_count;
-        p.masked_tokens = masked_tokens;
-        p.finished = finished;
-        p.d_step = nullptr;
-        p.step = step;
-        p.B = B;
-        p.nh = nh;
-        p.dh = dh;
-        p.rot = rot;
-        p.s_max = s_max;
-        p.ctx = (f16*)ctx;
-        p.gran = (unsigned long long*)workspace;
-        p.layer = 0;
-        p.nsplit = mmha_pick_nsplit(B, nh, s_max);
-        FTCF_CHECK_ARG(workspace_bytes >= mmha_workspace_bytes(B, nh, dh, p.nsplit), "MMHA workspace too small");
-        // the granule tags must not match anything left from an earlier call
-        FTCF_HIP_CHECK(hipMemsetAsync(p.gran, 0, mmha_workspace_bytes(B, nh, dh, p.nsplit), (hipStream_t)stream));
-        launch_mmha(p, (hipStream_t)stream);
+        abi_launch_mmha(qkv, qkv_bias, k_cache, v_cache, seq_len, pad_count, masked_tokens, finished, nullptr, 0, 0, B, nh, dh, rot,
+                        s_max, step, mmha_pick_nsplit(B, nh, s_max), ctx, workspace, workspace_bytes, (hipStream_t)stream);
+    });
+}
+// the launch with the beam-search arguments and an explicit split count (0: the launcher's choice), fp16 or fp32
+extern "C" int ftcf_masked_multihead_attention_beams(ftcf_dtype dtype, const void* qkv, const void* qkv_bias, void* k_cache,
+                                                     void* v_cache, const int* seq_len, const int* pad_count,
+                                                     const uint8_t* masked_tokens, const uint8_t* finished, const int* cache_indir,
+                                                     int beam_width, int max_input_len, int B, int nh, int dh, int rot, int s_max,
+                                                     int step, int nsplit, void* ctx, void* workspace, size_t workspace_bytes,
+                                                     void* stream)
+{
+    return guarded([&] {
+        require_device();
+        FTCF_CHECK_ARG(dtype == FTCF_FP16 || dtype == FTCF_FP32, "MMHA with beams: dtype fp16 or fp32");
+        FTCF_CHECK_ARG(qkv && k_cache && v_cache && seq_len && ctx, "NULL tensor");
+        FTCF_CHECK_ARG(B >= 1 && nh >= 1 && s_max >= 1 && mmha_head_size_supported(dh) && rot >= 0 && rot % 2 == 0
+                           && rot <= dh,
+                       "MMHA with beams: bad geometry");
+        FTCF_CHECK_ARG(nsplit >= 0 && nsplit <= 16, "MMHA with beams: nsplit 0..16");
+        if (cache_indir) {
+            FTCF_CHECK_ARG(beam_width > 1 && B % beam_width == 0 && max_input_len >= 0,
+                           "cache indirection needs beam_width > 1 and rows = batch * beam_width");
+        }
+        if (dtype == FTCF_FP32) {
+            FTCF_CHECK_ARG((size_t)(3 * dh + s_max + 1 + 8) * sizeof(float) <= ABI_MAX_DYNAMIC_LDS,
+                           "fp32 MMHA: a row's scores do not fit the LDS");
+            Mmha32Params p{};
+            p.qkv = (const float*)qkv;
+            p.qkv_bias = (const float*)qkv_bias;
+            p.k_cache = (float*)k_cache;
+            p.v_cache = (float*)v_cache;
+            p.seq_len = seq_len;
+            p.pad_count = pad_count;
+            p.masked_tokens = masked_tokens;
+            p.finished = finished;
+            p.B = B;
+            p.nh = nh;
+            p.dh = dh;
+            p.rot = rot;
+            p.s_max = s_max;
+            p.ctx = (float*)ctx;
+            p.cache_indir = cache_indir;
+            p.beam_width = beam_width;
+            p.max_input_len = max_input_len;
+            p.indir_plane = (size_t)B * s_max;
+            // k32_mmha reads the step from the device: one word of this call's own, released once the launch has drained
+            DeviceBuffer d_step;
+            d_step.reserve(sizeof(int));
+            FTCF_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)d_step.ptr, step, 1, (hipStream_t)stream));
+            p.d_step = (const int*)d_step.ptr;
+            launch32_mmha(p, (hipStream_t)stream);
+            FTCF_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+            return;
+        }
+        const int ns = nsplit ? nsplit : mmha_pick_nsplit(B, nh, s_max);
+        FTCF_CHECK_ARG(workspace != nullptr, "NULL workspace");
+        FTCF_CHECK_ARG(mmha_smem_bytes(dh, s_max, ns) <= ABI_MAX_DYNAMIC_LDS, "MMHA: a split's scores do not fit the LDS");
+        abi_launch_mmha(qkv, qkv_bias, k_cache, v_cache, seq_len, pad_count, masked_tokens, finished, cache_indir, beam_width,
+                        max_input_len, B, nh, dh, rot, s_max, step, ns, ctx, workspace, workspace_bytes, (hipStream_t)stream);
     });
 }
 // speculative decoding's kernels, one call each (the engine launches them through the same launchers)

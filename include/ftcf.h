@@ -189,6 +189,21 @@ int ftcf_masked_multihead_attention(const void* qkv, const void* qkv_bias, void*
                                     const uint8_t* finished, int B, int nh, int dh, int rot, int s_max, int step,
                                     void* ctx, void* workspace, size_t workspace_bytes, void* stream);
 size_t ftcf_masked_multihead_attention_workspace(int B, int nh, int dh, int s_max);
+/* The same step with beam search's arguments and an explicit split count.  dtype FTCF_FP16 or FTCF_FP32 (qkv, qkv_bias, caches
+ * and ctx all of that type).  cache_indir [2][B][s_max] int32 or NULL: the key / value of time t < seq_len[b] of row b is read from
+ * cache row (b / beam_width) * beam_width + cache_indir[(step - max_input_len) & 1][b][t]; the new key / value goes to row b's own
+ * line.  Every entry of both planes, over all s_max positions, must be in [0, beam_width): the kernel may dereference entries
+ * beyond seq_len[b].  B = batch * beam_width rows; NULL launches the form without beams (beam_width, max_input_len unused).
+ * fp16: nsplit = 0 takes the launcher's own split count (that of ftcf_masked_multihead_attention_workspace), 1..16 forces one;
+ * workspace_bytes >= B * nh * nsplit * (dh + 2) * 8 (one 8-byte granule per partial element), and a split's scores
+ * (roundup16(ceil(s_max / nsplit)) floats) must fit 64 KiB of LDS beside 22 * dh + 32 bytes.  fp32: nsplit and workspace are ignored
+ * (one workgroup per (row, head)); the call returns after the launch has finished.  A bad argument is an error return, never a
+ * failed launch. */
+int ftcf_masked_multihead_attention_beams(ftcf_dtype dtype, const void* qkv, const void* qkv_bias, void* k_cache, void* v_cache,
+                                          const int* seq_len, const int* pad_count, const uint8_t* masked_tokens,
+                                          const uint8_t* finished, const int* cache_indir, int beam_width, int max_input_len, int B,
+                                          int nh, int dh, int rot, int s_max, int step, int nsplit, void* ctx, void* workspace,
+                                          size_t workspace_bytes, void* stream);
 /* Speculative decoding's verify attention (no counterpart in the reference): decode attention for R
  * consecutive NEW tokens of ONE sequence.  qkv [R, 3*nh*dh] fp16 are the tokens of positions len .. len + R - 1 of the sequence in
  * row `cache_row` of k_cache / v_cache [rows, nh, s_max, dh], whose positions [0, len) are cached.  Row i: bias, NeoX rotary at

@@ -1705,7 +1705,7 @@ void orc_gather_tree_beam(const int* ids, const int* parents, const int* seq_len
  * B*K rows, cum_log_probs of beams > 0 start at -1e20 so that the first step expands beam 0 only. */
 int orc_generate_beam(const orc_config* c, const orc_weights* w, const int* input_ids, const int* input_lengths, int B,
                       int S, int out_len, int K, const orc_beam_params* bp, int* output_ids, int* sequence_lengths,
-                      float* cum_log_probs_out)
+                      float* cum_log_probs_out, float* dbg_logits)
 {
     const int H = c->head_num * c->size_per_head, nhl = c->head_num / c->tp_size;
     const int V = c->vocab_size, L = c->num_layer, fp16 = c->fp16;
@@ -1773,6 +1773,9 @@ int orc_generate_beam(const orc_config* c, const orc_weights* w, const int* inpu
         }
         orc_layernorm(hid_out, w->final_ln_g, w->final_ln_b, BK, H, 1e-5f, nrm, fp16);
         orc_lm_head(nrm, BK, H, V, w->lm_head, logits);
+        if (dbg_logits) {
+            memcpy(dbg_logits + (size_t)(step - max_input_length) * BK * V, logits, sizeof(float) * (size_t)BK * V);
+        }
         orc_beam_search_step(logits, B, K, V, step, max_input_length, t_len, bp, c->end_id, ids, parents, finished, seq_len,
                              cum, indir[src], indir[tgt], s_max);
         int all = 1;

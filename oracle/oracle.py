@@ -341,8 +341,9 @@ class Model:
             res["logits"] = dbg
         return res
 
-    def generate_beam(self, input_ids, input_lengths, out_len, beam_width, beam_params=None):
-        """Beam search (beam_width > 1): output_ids [B, K, S+out_len], sequence_lengths [B, K], cum_log_probs [B, K]."""
+    def generate_beam(self, input_ids, input_lengths, out_len, beam_width, beam_params=None, return_logits=False):
+        """Beam search (beam_width > 1): output_ids [B, K, S+out_len], sequence_lengths [B, K], cum_log_probs [B, K];
+        return_logits: "logits" [out_len, B*K, V], the raw logits of every step (zeros for steps after every beam finished)."""
         input_ids = np.ascontiguousarray(input_ids, dtype=np.int32)
         B, S = input_ids.shape
         K = int(beam_width)
@@ -351,10 +352,14 @@ class Model:
         out = np.zeros((B, K, S + out_len), dtype=np.int32)
         sl = np.zeros((B, K), dtype=np.int32)
         cum = np.zeros((B, K), dtype=np.float32)
+        dbg = np.zeros((out_len, B * K, self.c.vocab_size), dtype=np.float32) if return_logits else None
         n = lib().orc_generate_beam(C.byref(self.c), C.byref(self.w), _ptr(input_ids), _ptr(input_lengths), C.c_int(B),
                                     C.c_int(S), C.c_int(out_len), C.c_int(K), C.byref(bp.struct), _ptr(out), _ptr(sl),
-                                    _ptr(cum))
-        return {"output_ids": out, "sequence_lengths": sl, "cum_log_probs": cum, "steps": n}
+                                    _ptr(cum), _ptr(dbg))
+        res = {"output_ids": out, "sequence_lengths": sl, "cum_log_probs": cum, "steps": n}
+        if return_logits:
+            res["logits"] = dbg
+        return res
 
     def decoder_step(self, x, k_cache, v_cache, seq_len, pad_count, masked_tokens, finished, step):
         """k_cache/v_cache float32 [L, B, nhl, S_max, dh] in place."""

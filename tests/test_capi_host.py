@@ -55,6 +55,8 @@ def test_engine_form_entry_points_fail_loudly_without_a_gpu():
         lambda: L.ftcf_residual_gemv(C.byref(res), 1, 1, 2, None, C.c_size_t(0), None, 0, 0, None),
         lambda: L.ftcf_dynamic_decode_step(C.byref(dec), None),
         lambda: L.ftcf_beam_search_step(C.byref(beam), None),
+        lambda: L.ftcf_masked_multihead_attention_beams(1, None, None, None, None, None, None, None, None, None, 2, 1, 2, 1, 64, 16, 64, 2, 1,
+                                                        None, None, C.c_size_t(0), None),
     ]
     for call in calls:
         assert call() == -5 and b"no HIP device" in L.ftcf_last_error()

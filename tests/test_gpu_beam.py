@@ -87,7 +87,8 @@ def test_tiny_beams_finish_on_end_id_and_follow_runtime_args(gh, tiny, kw):
 
 def _replay(cfg, ids, lens, n_new, K, gpu_logits, bp):
     """The GPU's own raw logits of every step pushed through the oracle's beam-search layer: what the device kernels must
-    have produced from them (no model noise in the comparison)."""
+    have produced from them (no model noise in the comparison).  Also returns the trace of the search: per executed step the
+    tokens and parents it selected ("ids", "parents" [steps, B*K]) and the state it started from ("finished", "cum")."""
     B, S = ids.shape
     total, BK = S + n_new, B * K
     out = np.zeros((total, BK), np.int32)
@@ -99,13 +100,18 @@ def _replay(cfg, ids, lens, n_new, K, gpu_logits, bp):
     cum = np.where(np.arange(BK) % K == 0, 0.0, -1e20).astype(np.float32)
     ind = [np.zeros((B, K, total), np.int32), np.zeros((B, K, total), np.int32)]
     tl = np.repeat(np.asarray(lens, np.int32), K)
+    trace = dict(ids=[], parents=[], finished=[], cum=[])
     for t in range(n_new):
         lg = np.ascontiguousarray(gpu_logits[t], dtype=np.float32).copy()
+        trace["finished"].append(fin.copy())
+        trace["cum"].append(cum.copy())
         orc.beam_search_step(lg, K, S + t, S, tl, bp, cfg["end_id"], out, par, fin, seq, cum, ind[t % 2], ind[1 - t % 2])
+        trace["ids"].append(out[S + t].copy())
+        trace["parents"].append(par[S + t].copy())
         if fin.all():
             break
     o_ids, o_len = orc.gather_tree_beam(out, par, seq, tl, K, S, cfg["end_id"])
-    return o_ids, o_len, cum.reshape(B, K)
+    return o_ids, o_len, cum.reshape(B, K), {k: np.stack(v) for k, v in trace.items()}
 
 
 @pytest.mark.parametrize("kw", [
@@ -124,7 +130,7 @@ def test_beam_search_kernels_are_exact_given_the_same_logits(gh, tiny, kw):
     r = gh.run_op_beam(op, ids, lens, n_new, cfg["vocab_size"], K, return_logits=True, stop_words=stop, **kw)
     okw = {k: v for k, v in kw.items() if k != "beam_search_diversity_rate"}
     bp = orc.BeamParams(ids.shape[0], diversity_rate=kw.get("beam_search_diversity_rate"), stop_words=stop, **okw)
-    o_ids, o_len, o_cum = _replay(cfg, ids, lens, n_new, K, r["logits"], bp)
+    o_ids, o_len, o_cum, _ = _replay(cfg, ids, lens, n_new, K, r["logits"], bp)
     assert r["output_ids"].tolist() == o_ids.tolist()
     assert r["sequence_lengths"].tolist() == o_len.tolist()
     np.testing.assert_allclose(r["cum_log_probs"], o_cum, rtol=1e-5, atol=1e-4)
@@ -177,7 +183,7 @@ def test_mid_model_beam_search_follows_oracle(gh, B, K, int8_mode):
     o = orc.Model(dict(cfg, fp16=1, int8_mode=int8_mode), layers, glob).generate_beam(ids, lens, out, K)
     np.testing.assert_allclose(r["cum_log_probs"], o["cum_log_probs"], rtol=2e-2, atol=6e-2)
     assert r["sequence_lengths"].tolist() == o["sequence_lengths"].tolist()
-    p_ids, p_len, p_cum = _replay(cfg, ids, lens, out, K, r["logits"], orc.BeamParams(B))
+    p_ids, p_len, p_cum, _ = _replay(cfg, ids, lens, out, K, r["logits"], orc.BeamParams(B))
     assert r["output_ids"].tolist() == p_ids.tolist()  # exact given the GPU's own logits
     np.testing.assert_allclose(r["cum_log_probs"], p_cum, rtol=1e-5, atol=1e-4)
     agree = (r["output_ids"] == o["output_ids"]).mean()
@@ -206,7 +212,7 @@ def test_wide_beams_are_exact_given_the_same_logits(gh, tiny, B, K, out):
     r = gh.run_op_beam(op, ids, lens, out, cfg["vocab_size"], K, return_logits=True, repetition_penalty=1.2,
                        beam_search_diversity_rate=-0.1)
     bp = orc.BeamParams(B, repetition_penalty=1.2, diversity_rate=-0.1)
-    p_ids, p_len, p_cum = _replay(cfg, ids, lens, out, K, r["logits"], bp)
+    p_ids, p_len, p_cum, _ = _replay(cfg, ids, lens, out, K, r["logits"], bp)
     assert r["output_ids"].tolist() == p_ids.tolist()
     assert r["sequence_lengths"].tolist() == p_len.tolist()
     np.testing.assert_allclose(r["cum_log_probs"], p_cum, rtol=1e-4, atol=1e-3)

@@ -358,7 +358,7 @@ def test_one_engine_serves_requests_of_changing_shape(gh, tiny):
                 ids[b, :lens[b]] = rng.randint(3, V, size=lens[b])
         if K > 1:
             r = gh.run_op_beam(op, ids, lens, out, V, K, return_logits=True)
-            p_ids, _, _ = _replay(cfg, ids, lens, out, K, r["logits"], orc.BeamParams(B))
+            p_ids, _, _, _ = _replay(cfg, ids, lens, out, K, r["logits"], orc.BeamParams(B))
             assert r["output_ids"].tolist() == p_ids.tolist(), (B, S, out, K)
             continue
         r = gh.run_op(op, ids, lens, out, V, top_k=1)

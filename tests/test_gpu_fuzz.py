@@ -55,7 +55,7 @@ def test_random_configuration_follows_the_oracle(gh, seed):
     if K > 1:
         from tests.test_gpu_beam import _replay
         r = gh.run_op_beam(op, ids, lens, out, V, K, return_logits=True)
-        p_ids, p_len, p_cum = _replay(cfg, ids, lens, out, K, r["logits"], orc.BeamParams(B))
+        p_ids, p_len, p_cum, _ = _replay(cfg, ids, lens, out, K, r["logits"], orc.BeamParams(B))
         assert r["output_ids"].tolist() == p_ids.tolist(), what  # exact given the GPU's own logits
         np.testing.assert_allclose(r["cum_log_probs"], p_cum, rtol=1e-4, atol=1e-3, err_msg=what)
         o = m.generate_beam(ids, lens, out, K)

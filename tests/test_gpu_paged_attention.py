@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests.attention_reference import CTX_FLOOR, CTX_ULPS, K_ULPS, _half, _rotary, _sentinel, _ulps
 from tests.helpers import PAGED_LDS as LDS
 from tests.helpers import longest_paged_len as longest
 from tests.helpers import paged_smem_bytes as smem_bytes
@@ -31,38 +32,6 @@ def _lib():
 
 def sp():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-# Errors are counted in half-precision ulps (see _ulps): the context at max(|ctx|, CTX_FLOOR x the size of the terms it averages),
-# the appended key at max(|k|, the size of the rotated pair).  Measured on MI355X over every case below: worst context error
-# 4.00 ulp (a 49-key slot, dh 128, full rotary, P 48), worst appended-key error 1.38 ulp (position 14,751, full rotary).
-CTX_FLOOR = 1 / 64
-CTX_ULPS = 6
-K_ULPS = 2
-
-
-def _sentinel(rng, n):
-    """n random fp16 bit patterns, all finite (bit 10 clear: the exponent is never all ones), as uint16."""
-    return (rng.randint(0, 1 << 16, size=n).astype(np.uint16) & np.uint16(0xFBFF))
-
-
-def _half(x):
-    return np.asarray(x, dtype=np.float64).astype(np.float16)
-
-
-def _rotary(x, pos, rot):
-    """NeoX rotary of half vectors x [..., dh] at position pos, rounded as the kernel rounds it (rotary_coef / rotary_apply)."""
-    if rot == 0:
-        return x
-    j = np.arange(rot // 2, dtype=np.float32)
-    den = (10000.0 ** ((2 * j) / np.float32(rot)).astype(np.float64)).astype(np.float32)  # powf, correctly rounded
-    ang = (np.float32(pos) / den).astype(np.float64)  # an fp32 quotient
-    cs, sn = np.cos(ang), np.sin(ang)
-    a, b = x[..., :rot // 2].astype(np.float64), x[..., rot // 2:rot].astype(np.float64)
-    out = x.copy()
-    out[..., :rot // 2] = _half(cs * a - sn * b)
-    out[..., rot // 2:rot] = _half(cs * b + sn * a)
-    return out
 
 
 def reference_step(qkv, bias, kpool, vpool, pt, lens, fin, nh, dh, rot, P):
@@ -91,16 +60,6 @@ def reference_step(qkv, bias, kpool, vpool, pt, lens, fin, nh, dh, rot, P):
         k_mag[b] = xk.copy()
         k_mag[b][:, :rot // 2] = k_mag[b][:, rot // 2:rot] = xk[:, :rot // 2] + xk[:, rot // 2:rot]
     return ctx, k_new, v_new, c_mag, k_mag
-
-
-def _ulps(got, ref, mag):
-    """|got - ref| (ref already rounded to half) in half-precision ulps at max(|ref|, mag).  The context: mag = CTX_FLOOR x the
-    size of the terms it averages, so that an output that cancels to near zero is not counted at a subnormal ulp, while over
-    thousands of keys (|ctx| ~ 0.01, a single key weighing 1 / len) one dropped key still costs tens of ulps.  The appended key:
-    mag = the size of the rotated pair, the scale at which a rotation by an fp32 angle errs (the angle's own ulp is 1e-3 rad near
-    position 15000)."""
-    m = np.maximum(np.maximum(np.abs(ref.astype(np.float64)), mag), 2.0 ** -14).astype(np.float16)
-    return np.abs(got.astype(np.float64) - ref.astype(np.float64)) / np.spacing(m).astype(np.float64)
 
 
 def _layout(rng, lens, P, share, extra):

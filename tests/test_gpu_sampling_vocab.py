@@ -199,7 +199,7 @@ def test_beam_search_kernels_at_the_headline_vocabulary(gh, model):
     r = gh.run_op_beam(op, ids, lens, out, V, K, return_logits=True, **kw)
     okw = {k: v for k, v in kw.items() if k != "beam_search_diversity_rate"}
     bp = orc.BeamParams(B, diversity_rate=kw["beam_search_diversity_rate"], **okw)
-    o_ids, o_len, o_cum = beam_replay(CFG, ids, lens, out, K, r["logits"], bp)
+    o_ids, o_len, o_cum, _ = beam_replay(CFG, ids, lens, out, K, r["logits"], bp)
     assert r["output_ids"].tolist() == o_ids.tolist()
     assert r["sequence_lengths"].tolist() == o_len.tolist()
     np.testing.assert_allclose(r["cum_log_probs"], o_cum, rtol=1e-4, atol=1e-3)

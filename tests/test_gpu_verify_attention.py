@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.test_gpu_paged_attention import CTX_FLOOR, _half, _rotary, _sentinel, _ulps
+from tests.attention_reference import CTX_FLOOR, _half, _rotary, _sentinel, _ulps
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(900)]
 
@@ -32,7 +32,7 @@ def sp():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-# The project's own bounds for these rounding points and this metric (tests/test_gpu_paged_attention.py: CTX_ULPS = 6,
+# The project's own bounds for these rounding points and this metric (tests/attention_reference.py: CTX_ULPS = 6,
 # K_ULPS = 2).  The kernel keeps the dot2 / fp32 arithmetic of the decode attention (no MFMA accumulation order), so they
 # are kept as they are.  Measured on MI355X over every case below: worst context error 2.00 ulp (R 16, len 3000, dh 64, full
 # rotary, row 11; the decode attention run step by step on the same case: 2.00), worst appended-key error 1.00 ulp (len 1023 and

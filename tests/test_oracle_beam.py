@@ -51,6 +51,28 @@ def test_beam_width_one_is_greedy(tiny):
     assert np.array_equal(r1["output_ids"][:, 0], r0["output_ids"])
 
 
+def test_return_logits_gives_the_raw_logits_of_every_step(tiny):
+    """K = 2: every beam of step 0 sees the prompt alone, so row 0 of step 0 equals greedy generation's step-0 logits; the search
+    itself is unchanged by the request for logits, and replaying them through the beam search layer gives the same tokens."""
+    cfg, layers, glob, g = tiny
+    m = _model(cfg, layers, glob, fp16=1)
+    ids, lens = g["ids_c"], g["lens_c"]
+    B, K, n_new = ids.shape[0], 2, 5
+    r = m.generate_beam(ids, lens, n_new, K, return_logits=True)
+    assert r["logits"].shape == (n_new, B * K, cfg["vocab_size"]) and np.abs(r["logits"][-1]).max() > 0
+    r0 = m.generate(ids, lens, 1, return_logits=True)
+    for b in range(B):
+        assert np.array_equal(r["logits"][0, b * K], r0["logits"][0, b])
+        assert np.array_equal(r["logits"][0, b * K + 1], r0["logits"][0, b])
+    plain = m.generate_beam(ids, lens, n_new, K)
+    assert "logits" not in plain and np.array_equal(plain["output_ids"], r["output_ids"])
+    assert np.array_equal(plain["cum_log_probs"], r["cum_log_probs"])
+    from tests.test_gpu_beam import _replay
+    p_ids, p_len, p_cum, trace = _replay(cfg, ids, lens, n_new, K, r["logits"], orc.BeamParams(B))
+    assert p_ids.tolist() == r["output_ids"].tolist() and p_len.tolist() == r["sequence_lengths"].tolist()
+    assert trace["ids"].shape == (n_new, B * K) and trace["parents"].shape == (n_new, B * K)
+
+
 def _state(B, K, V, total, s_max, seed=0):
     rng = np.random.RandomState(seed)
     return dict(logits=rng.randn(B * K, V).astype(np.float32), output_ids=np.zeros((total, B * K), np.int32),

@@ -62,7 +62,7 @@ for case in range(ncase):
         else:
             r = gh.run_op_beam(op, ids, lens, out, V, K, return_logits=True)
             from tests.test_gpu_beam import _replay
-            p_ids, p_len, p_cum = _replay(cfg, ids, lens, out, K, r["logits"], orc.BeamParams(B))
+            p_ids, p_len, p_cum, _ = _replay(cfg, ids, lens, out, K, r["logits"], orc.BeamParams(B))
             ok = r["output_ids"].tolist() == p_ids.tolist() and np.allclose(r["cum_log_probs"], p_cum, atol=1e-3, rtol=1e-4)
             o = m.generate_beam(ids, lens, out, K)
             agree = (r["output_ids"] == o["output_ids"]).mean()
