@@ -4,6 +4,9 @@
     cb = ContinuousBatcher(op, max_batch=8, page_tokens=64, num_pages=512, max_seq_len=2048)
     rid = cb.submit(prompt_ids, max_new_tokens=128)          # greedy; top_k / top_p / temperature / seed /
                                                              # repetition_penalty / stop_words optional
+    cb.submit(prompt_ids, 128, logit_bias={id: -inf}, bad_words=[[a, b]], presence_penalty=.5, frequency_penalty=.2,
+              min_new_tokens=8)                              # per-request logit processors
+    cb.set_token_mask(rid, allowed_ids)                      # the next tokens come from this set (grammar-constrained decoding)
     bid = cb.submit_beam(prompt_ids, 128, beam_width=4)      # beam search: one event (bid, -1, True), then cb.beam_result(bid)
     ContinuousBatcher(op, ..., prefix_cache=True)             # reuse the K/V pages of shared prompt prefixes (prefix_stats())
     while cb.busy():
@@ -16,6 +19,57 @@ import ctypes as C
 import numpy as np
 
 from . import capi
+
+
+def _word_list(words):
+    """token-id lists -> the [2, n] word list of to_word_list_format (codefuse_example.py:26-53)"""
+    flat = [int(t) for w in words for t in w]
+    arr = np.zeros((2, len(flat)), dtype=np.int32)
+    arr[0] = flat
+    arr[1] = -1
+    arr[1, :len(words)] = np.cumsum([len(w) for w in words])
+    return np.ascontiguousarray(arr)
+
+
+def pack_logit_options(logit_bias=None, bad_words=None, presence_penalty=0.0, frequency_penalty=0.0, min_new_tokens=0):
+    """The logit-processor keywords of submit() as (ftcf_logit_options, the arrays it points to), or (None, ()) when none is
+    set.  What can be checked without the vocabulary size is checked here (ValueError); ids >= V are the library's to refuse."""
+    pairs = list(logit_bias.items()) if isinstance(logit_bias, dict) else [tuple(p) for p in (logit_bias or ())]
+    ids = [int(i) for i, _ in pairs]
+    vals = [float(v) for _, v in pairs]
+    words = [list(w) for w in (bad_words or ())]
+    presence_penalty, frequency_penalty = float(presence_penalty), float(frequency_penalty)
+    if len(ids) > 1024:
+        raise ValueError("logit_bias takes at most 1024 pairs")
+    if len(set(ids)) != len(ids):
+        raise ValueError("logit_bias: duplicate token id")
+    if any(i < 0 for i in ids):
+        raise ValueError("logit_bias: token id out of range")
+    if any(np.isnan(v) or v == np.inf for v in vals):
+        raise ValueError("logit_bias: a value is NaN or +inf")
+    if not (np.isfinite(presence_penalty) and np.isfinite(frequency_penalty)):
+        raise ValueError("presence_penalty and frequency_penalty must be finite")
+    if int(min_new_tokens) != min_new_tokens or min_new_tokens < 0:
+        raise ValueError("min_new_tokens must be a non-negative integer")
+    if any(len(w) == 0 for w in words) or any(t < 0 for w in words for t in w):
+        raise ValueError("bad_words: an empty word or a negative token id")
+    if sum(len(w) for w in words) > 256:
+        raise ValueError("bad_words holds at most 256 tokens")
+    if not (ids or words or presence_penalty != 0.0 or frequency_penalty != 0.0 or min_new_tokens):
+        return None, ()
+    o = capi.LogitOptions()
+    o.struct_size = C.sizeof(capi.LogitOptions)
+    o.presence_penalty, o.frequency_penalty, o.min_new_tokens = presence_penalty, frequency_penalty, int(min_new_tokens)
+    keep = []
+    if ids:
+        a, v = np.asarray(ids, dtype=np.int32), np.asarray(vals, dtype=np.float32)
+        o.bias_ids, o.bias_values, o.n_bias = a.ctypes.data_as(C.POINTER(C.c_int)), v.ctypes.data_as(C.POINTER(C.c_float)), len(ids)
+        keep += [a, v]
+    if words:
+        w = _word_list(words)
+        o.bad_words, o.bad_words_len = w.ctypes.data_as(C.POINTER(C.c_int)), int(w.shape[1])
+        keep.append(w)
+    return o, tuple(keep)
 
 
 class ContinuousBatcher:
@@ -47,9 +101,16 @@ class ContinuousBatcher:
             pass
 
     def submit(self, prompt_ids, max_new_tokens, top_k=0, top_p=0.0, temperature=1.0, seed=0, repetition_penalty=1.0,
-               stop_words=None):
+               stop_words=None, *, logit_bias=None, bad_words=None, presence_penalty=0.0, frequency_penalty=0.0, min_new_tokens=0):
         """stop_words: a list of token-id lists (each one a stop sequence), or None.  The request ends after a stop
-        sequence has been emitted (stop_criteria_kernels.cu:24-83), like GptNeoXOp.forward with stop_words_list."""
+        sequence has been emitted (stop_criteria_kernels.cu:24-83), like GptNeoXOp.forward with stop_words_list.
+
+        Logit processors (ftcf_batcher_submit_opts; applied to every token of the request, the first included, in this order,
+        before the sampling parameters): presence_penalty / frequency_penalty over the GENERATED tokens (additive, OpenAI
+        semantics), logit_bias ({token id: value} or (id, value) pairs, at most 1024; -inf bans a token), min_new_tokens (the end
+        token is held back that long), bad_words (token-id lists as stop_words: a one-token word is banned, a longer one may not
+        be completed).  set_token_mask() adds the per-step allowed-token mask."""
+        opts, keep = pack_logit_options(logit_bias, bad_words, presence_penalty, frequency_penalty, min_new_tokens)
         ids = np.ascontiguousarray(prompt_ids, dtype=np.int32).reshape(-1)
         rid = C.c_long(0)
         sw, sw_len = None, 0
@@ -61,11 +122,42 @@ class ContinuousBatcher:
             arr[1] = -1
             arr[1, :len(stop_words)] = np.cumsum([len(w) for w in stop_words])
             sw = np.ascontiguousarray(arr)
+        if opts is not None:
+            capi.check(capi.lib().ftcf_batcher_submit_opts(
+                self._h, ids.ctypes.data_as(C.POINTER(C.c_int)), int(ids.size), int(max_new_tokens), int(top_k), C.c_float(top_p),
+                C.c_float(temperature), C.c_float(repetition_penalty), C.c_ulonglong(int(seed)),
+                sw.ctypes.data_as(C.POINTER(C.c_int)) if sw is not None else None, int(sw_len), C.byref(opts), C.byref(rid)))
+            del keep  # (the call copies the arrays)
+            return int(rid.value)
         capi.check(capi.lib().ftcf_batcher_submit_ex(
             self._h, ids.ctypes.data_as(C.POINTER(C.c_int)), int(ids.size), int(max_new_tokens), int(top_k), C.c_float(top_p),
             C.c_float(temperature), C.c_float(repetition_penalty), C.c_ulonglong(int(seed)),
             sw.ctypes.data_as(C.POINTER(C.c_int)) if sw is not None else None, int(sw_len), C.byref(rid)))
         return int(rid.value)
+
+    def set_token_mask(self, request_id, allowed):
+        """The allowed-token mask of a waiting or running request (ftcf_batcher_set_token_mask): every token sampled for it from
+        the next one on comes from `allowed` -- a bool array of length V or an iterable of token ids -- until the mask is
+        replaced; None clears it.  May be called from inside the token callback (grammar-constrained decoding: advance the
+        grammar on the event, hand the next step's mask back).  A request whose mask and options leave no token ends with end_id."""
+        if allowed is None:
+            capi.check(capi.lib().ftcf_batcher_set_token_mask(self._h, C.c_long(int(request_id)), None, 0))
+            return
+        V = int(self._op.vocab_size_)
+        a = np.asarray(allowed if isinstance(allowed, np.ndarray) else list(allowed))
+        if a.dtype == np.bool_:
+            if a.shape != (V,):
+                raise ValueError("a bool mask has one entry per token of the vocabulary")
+            bits = a
+        else:
+            a = a.astype(np.int64).reshape(-1)
+            if a.size and (a.min() < 0 or a.max() >= V):
+                raise ValueError("token mask: token id out of range")
+            bits = np.zeros(V, dtype=np.bool_)
+            bits[a] = True
+        words = np.ascontiguousarray(np.packbits(np.pad(bits, (0, -V % 32)), bitorder="little").view(np.uint32))
+        capi.check(capi.lib().ftcf_batcher_set_token_mask(self._h, C.c_long(int(request_id)), words.ctypes.data_as(C.POINTER(C.c_uint)),
+                                                          int(words.size)))
 
     def submit_beam(self, prompt_ids, max_new_tokens, beam_width, beam_search_diversity_rate=0.0, len_penalty=0.0, temperature=1.0,
                     repetition_penalty=1.0, min_length=0, stop_words=None):

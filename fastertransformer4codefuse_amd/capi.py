@@ -86,6 +86,22 @@ class DynamicDecodeArgs(C.Structure):  # ftcf_dynamic_decode_args
         ("top_logprobs", C.c_int), ("top_ids", C.c_void_p), ("top_log_probs", C.c_void_p)]
 
 
+class LogitProcessArgs(C.Structure):  # ftcf_logit_process_args
+    _fields_ = [("struct_size", C.c_int), ("batch_size", C.c_int), ("vocab_size", C.c_int), ("end_id", C.c_int),
+                ("logits", C.c_void_p), ("finished", C.c_void_p), ("row_on", C.c_void_p), ("hist", C.c_void_p),
+                ("stride_t", C.c_longlong), ("stride_b", C.c_longlong), ("hist_len", C.c_void_p), ("gen_start", C.c_void_p),
+                ("hist_len_add", C.c_int), ("bias_stride", C.c_int), ("presence_penalty", C.c_void_p),
+                ("frequency_penalty", C.c_void_p), ("min_new_tokens", C.c_void_p), ("bias_ids", C.c_void_p),
+                ("bias_values", C.c_void_p), ("n_bias", C.c_void_p), ("bad_words", C.c_void_p), ("bad_words_len", C.c_int),
+                ("slice", C.c_int), ("mask", C.c_void_p), ("mask_on", C.c_void_p)]
+
+
+class LogitOptions(C.Structure):  # ftcf_logit_options
+    _fields_ = [("struct_size", C.c_int), ("presence_penalty", C.c_float), ("frequency_penalty", C.c_float),
+                ("min_new_tokens", C.c_int), ("bias_ids", C.POINTER(C.c_int)), ("bias_values", C.POINTER(C.c_float)),
+                ("n_bias", C.c_int), ("bad_words", C.POINTER(C.c_int)), ("bad_words_len", C.c_int)]
+
+
 class BeamSearchArgs(C.Structure):  # ftcf_beam_search_args
     _fields_ = [(n, C.c_void_p) for n in (
         "logits", "output_ids", "parent_ids", "finished", "seq_len", "cum_log_probs", "cache_indir", "input_lengths",
@@ -119,13 +135,13 @@ EXPORTED = [
     "ftcf_context_attention",
     "ftcf_verify_attention", "ftcf_verify_attention_workspace", "ftcf_ngram_draft",
     "ftcf_paged_attention", "ftcf_scatter_kv_to_pages", "ftcf_gather_pages_to_kv",
-    "ftcf_dynamic_decode_step", "ftcf_beam_search_step",
+    "ftcf_dynamic_decode_step", "ftcf_beam_search_step", "ftcf_logit_process",
     "ftcf_comm_get_unique_id", "ftcf_comm_init", "ftcf_comm_destroy", "ftcf_comm_local_unique_id",
     "ftcf_comm_init_local", "ftcf_comm_init_host_exchange", "ftcf_comm_allreduce_sum",
     "ftcf_comm_allgather", "ftcf_gptneox_create", "ftcf_gptneox_forward", "ftcf_gptneox_begin", "ftcf_gptneox_step", "ftcf_gptneox_finish",
     "ftcf_gptneox_get_stats",
     "ftcf_gptneox_set_profiling", "ftcf_gptneox_destroy",
-    "ftcf_batcher_create", "ftcf_batcher_create_ex", "ftcf_batcher_prefix_stats", "ftcf_batcher_clear_prefix_cache", "ftcf_batcher_submit", "ftcf_batcher_submit_ex", "ftcf_batcher_submit_beam", "ftcf_batcher_submit_beam_ex", "ftcf_batcher_beam_result", "ftcf_batcher_step", "ftcf_batcher_step_ex", "ftcf_batcher_step_top", "ftcf_batcher_set_token_callback", "ftcf_batcher_status", "ftcf_batcher_cancel", "ftcf_batcher_destroy"]
+    "ftcf_batcher_create", "ftcf_batcher_create_ex", "ftcf_batcher_prefix_stats", "ftcf_batcher_clear_prefix_cache", "ftcf_batcher_submit", "ftcf_batcher_submit_ex", "ftcf_batcher_submit_opts", "ftcf_batcher_set_token_mask", "ftcf_batcher_submit_beam", "ftcf_batcher_submit_beam_ex", "ftcf_batcher_beam_result", "ftcf_batcher_step", "ftcf_batcher_step_ex", "ftcf_batcher_step_top", "ftcf_batcher_set_token_callback", "ftcf_batcher_status", "ftcf_batcher_cancel", "ftcf_batcher_destroy"]
 
 _lib = None
 

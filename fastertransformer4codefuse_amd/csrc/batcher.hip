@@ -158,6 +158,139 @@ struct ftcf_batcher : BatcherSched {
     unsigned     smallm_seq = 0;
     long         gemm_steps = 0;
     std::vector<void*> owned;
+    // Logit processors (kernels_logits.hip): the options and masks of `rows` rows on the device with their host mirrors -- one set
+    // indexed by slot for the decode steps, one by the rows of an admission's ragged batch for its first tokens.  The host
+    // mirrors are members: an asynchronous copy reads them until the step's synchronisation, and nobody changes them before it.
+    struct LogitRows {
+        float *            d_pres = nullptr, *d_freq = nullptr, *d_bias_values = nullptr;
+        int *              d_min_new = nullptr, *d_gen_start = nullptr, *d_n_bias = nullptr, *d_bias_ids = nullptr, *d_bad = nullptr;
+        unsigned*          d_mask = nullptr;
+        uint8_t*           d_flags = nullptr;  // [2][rows]: row_on, mask_on
+        std::vector<float> pres, freq;
+        std::vector<int>   min_new, gen_start, n_bias;
+        std::vector<uint8_t> flags, flags_dev;
+        int                rows = 0, W = 0;
+    };
+    LogitRows lp_slots, lp_adm;
+    long      logit_launches = 0;  // stages enqueued so far (decode steps and admissions)
+    void init_logit_rows(LogitRows& lr, int rows)
+    {
+        lr.rows          = rows;
+        lr.W             = (e->V + 31) / 32;
+        lr.d_pres        = dmalloc<float>(rows);
+        lr.d_freq        = dmalloc<float>(rows);
+        lr.d_min_new     = dmalloc<int>(rows);
+        lr.d_gen_start   = dmalloc<int>(rows);
+        lr.d_n_bias      = dmalloc<int>(rows);
+        lr.d_bias_ids    = dmalloc<int>((size_t)rows * BIAS_MAX);
+        lr.d_bias_values = dmalloc<float>((size_t)rows * BIAS_MAX);
+        lr.d_bad         = dmalloc<int>((size_t)rows * 2 * BAD_LW);
+        lr.d_mask        = dmalloc<unsigned>((size_t)rows * lr.W);
+        lr.d_flags       = dmalloc<uint8_t>(2 * (size_t)rows);
+        lr.pres.assign(rows, 0.f);
+        lr.freq.assign(rows, 0.f);
+        lr.min_new.assign(rows, 0);
+        lr.gen_start.assign(rows, 0);
+        lr.n_bias.assign(rows, 0);
+        lr.flags.assign(2 * (size_t)rows, 0);
+        lr.flags_dev = lr.flags;
+    }
+    // row `i` <- the options (opts given) and / or the mask (mask given) of a request whose generated tokens begin at gen_start
+    void stage_logit_row(LogitRows& lr, int i, const LogitOptions* opts, const std::vector<unsigned>* mask, int gen_start, hipStream_t st)
+    {
+        static const std::vector<int> no_words = [] {
+            std::vector<int> w(2 * BAD_LW, -1);
+            return w;
+        }();
+        if (opts) {
+            lr.pres[i]      = opts->presence;
+            lr.freq[i]      = opts->frequency;
+            lr.min_new[i]   = opts->min_new;
+            lr.gen_start[i] = gen_start;
+            lr.n_bias[i]    = (int)opts->bias_ids.size();
+            if (lr.n_bias[i] > 0) {
+                FTCF_HIP_CHECK(hipMemcpyAsync(lr.d_bias_ids + (size_t)i * BIAS_MAX, opts->bias_ids.data(), (size_t)lr.n_bias[i] * 4,
+                                              hipMemcpyHostToDevice, st));
+                FTCF_HIP_CHECK(hipMemcpyAsync(lr.d_bias_values + (size_t)i * BIAS_MAX, opts->bias_values.data(), (size_t)lr.n_bias[i] * 4,
+                                              hipMemcpyHostToDevice, st));
+            }
+            FTCF_HIP_CHECK(hipMemcpyAsync(lr.d_bad + (size_t)i * 2 * BAD_LW, opts->bad.empty() ? no_words.data() : opts->bad.data(),
+                                          (size_t)2 * BAD_LW * 4, hipMemcpyHostToDevice, st));
+        }
+        if (mask) {
+            lr.flags[lr.rows + i] = mask->empty() ? 0 : 1;
+            if (!mask->empty()) {
+                FTCF_HIP_CHECK(hipMemcpyAsync(lr.d_mask + (size_t)i * lr.W, mask->data(), (size_t)lr.W * 4, hipMemcpyHostToDevice, st));
+            }
+        }
+    }
+    // the per-row scalars of rows that changed and the flags when they differ from the device's, then the stage itself
+    void enqueue_logit_stage(LogitRows& lr, bool scalars_changed, float* lg, int rows, const uint8_t* finished, const int* hist,
+                             long long stride_t, long long stride_b, const int* hist_len, int hist_len_add, hipStream_t st)
+    {
+        if (scalars_changed) {
+            FTCF_HIP_CHECK(hipMemcpyAsync(lr.d_pres, lr.pres.data(), (size_t)lr.rows * 4, hipMemcpyHostToDevice, st));
+            FTCF_HIP_CHECK(hipMemcpyAsync(lr.d_freq, lr.freq.data(), (size_t)lr.rows * 4, hipMemcpyHostToDevice, st));
+            FTCF_HIP_CHECK(hipMemcpyAsync(lr.d_min_new, lr.min_new.data(), (size_t)lr.rows * 4, hipMemcpyHostToDevice, st));
+            FTCF_HIP_CHECK(hipMemcpyAsync(lr.d_gen_start, lr.gen_start.data(), (size_t)lr.rows * 4, hipMemcpyHostToDevice, st));
+            FTCF_HIP_CHECK(hipMemcpyAsync(lr.d_n_bias, lr.n_bias.data(), (size_t)lr.rows * 4, hipMemcpyHostToDevice, st));
+        }
+        if (lr.flags != lr.flags_dev) {
+            FTCF_HIP_CHECK(hipMemcpyAsync(lr.d_flags, lr.flags.data(), lr.flags.size(), hipMemcpyHostToDevice, st));
+            lr.flags_dev = lr.flags;
+        }
+        LogitProcessParams lp{};
+        lp.logits       = lg;
+        lp.B            = rows;
+        lp.V            = e->V;
+        lp.end_id       = e->cfg.end_id;
+        lp.finished     = finished;
+        lp.row_on       = lr.d_flags;
+        lp.hist         = hist;
+        lp.stride_t     = stride_t;
+        lp.stride_b     = stride_b;
+        lp.hist_len     = hist_len;
+        lp.gen_start    = lr.d_gen_start;
+        lp.hist_len_add = hist_len_add;
+        lp.presence     = lr.d_pres;
+        lp.frequency    = lr.d_freq;
+        lp.min_new      = lr.d_min_new;
+        lp.bias_ids     = lr.d_bias_ids;
+        lp.bias_values  = lr.d_bias_values;
+        lp.n_bias       = lr.d_n_bias;
+        lp.bias_stride  = BIAS_MAX;
+        lp.bad_words    = lr.d_bad;
+        lp.bad_len      = BAD_LW;
+        lp.mask         = lr.d_mask;
+        lp.mask_on      = lr.d_flags + lr.rows;
+        launch_logit_process(lp, st);
+        logit_launches++;
+    }
+    // the decode step's stage: the rows of running ordinary slots with options or a mask (none: nothing is enqueued)
+    void enqueue_decode_logit_stage(hipStream_t st)
+    {
+        bool any = false, scalars = false;
+        for (int si = 0; si < max_batch; si++) {
+            Slot&      s  = slots[si];
+            const bool on = s.active && s.group < 0 && s.processed();
+            lp_slots.flags[si] = on ? 1 : 0;
+            if (!on) {
+                continue;
+            }
+            any = true;
+            if (s.lopt_dirty || s.mask_dirty) {
+                stage_logit_row(lp_slots, si, s.lopt_dirty ? &s.lopt : nullptr, s.mask_dirty ? &s.mask : nullptr,
+                                (int)s.hist.size() - s.generated, st);
+                scalars |= s.lopt_dirty;
+                s.lopt_dirty = s.mask_dirty = false;
+            }
+        }
+        if (any) {
+            // (the slot's history: column si of d_hist, positions [0, len]; finished rows and the rows of beam groups are not on)
+            enqueue_logit_stage(lp_slots, scalars, logits, max_batch, d_fin, d_hist, max_batch, 1, d_len, 1, st);
+        }
+    }
+    static_assert(BIAS_MAX == LOGIT_BIAS_MAX && BAD_LW == LOGIT_BAD_WORDS_MAX, "the scheduler's option limits are the logit stage's");
 
     template<typename T>
     T* dmalloc(size_t n, bool zero = true)
@@ -256,6 +389,8 @@ struct ftcf_batcher : BatcherSched {
         d_pseq = dmalloc<int>(B);
         d_pages_tmp = dmalloc<int>(max_pages);
         samp_ws = dmalloc<char>(sampling_workspace_bytes(max_batch, V), false);
+        init_logit_rows(lp_slots, max_batch);
+        init_logit_rows(lp_adm, max_batch);
         {
             const int rows_env = getenv("FTCF_BATCHER_ROWS") ? atoi(getenv("FTCF_BATCHER_ROWS")) : 1;
             if (rows_env && e->rows && e->cfg.tensor_para_size == 1 && !e->fp32 && max_batch <= 16 && e->cfg.use_gptj_residual && L <= 255
@@ -344,6 +479,19 @@ struct ftcf_batcher : BatcherSched {
         }
     };
 
+    // the engine's logits hook (engine.hip.h), for one forward(); an empty function leaves the engine as it is
+    struct LogitsHook {
+        ftcf_gptneox* e;
+        LogitsHook(ftcf_gptneox* eng, std::function<void(float*, int, hipStream_t)> fn): e(eng)
+        {
+            e->logits_hook = std::move(fn);
+        }
+        ~LogitsHook()
+        {
+            e->logits_hook = nullptr;
+        }
+    };
+
     // prompts -> ONE ragged batch through the engine's context path (+ first tokens) -> pages of their slots
     // hit (one request only): the cached pages of its first prompt blocks (pinned here: the slot's page list owns one reference)
     // (the first n of rs, into the first n of sis)
@@ -411,6 +559,21 @@ struct ftcf_batcher : BatcherSched {
             a.top_logprob_ids    = d_ptop_ids;  // [n, 1, 1, top_n]
             a.top_logprob_values = d_ptop_lp;
         }
+        // the first tokens' logit processors: the rows' options and masks by row of this batch, the stage as the engine's
+        // logits hook (history = the padded prompt rows, nothing generated yet)
+        bool any_lp = false;
+        for (int i = 0; i < n; i++) {
+            const bool on = rs[i].lopt.any() || !rs[i].mask.empty();
+            lp_adm.flags[i] = on ? 1 : 0;
+            if (on) {
+                stage_logit_row(lp_adm, i, &rs[i].lopt, &rs[i].mask, lens[i], st);
+                any_lp = true;
+            }
+        }
+        LogitsHook first_logits(e, any_lp ? std::function<void(float*, int, hipStream_t)>([this, n, S](float* lg, int rows, hipStream_t s2) {
+            FTCF_CHECK_ARG(rows == n, "batcher: the engine's first step has other rows than the admission");
+            enqueue_logit_stage(lp_adm, true, lg, n, nullptr, d_prompt, 1, S, d_plen, 0, s2);
+        }) : nullptr);
         const int hit_tokens = hit ? (int)hit->size() * P : 0;
         if (hit_tokens > 0) {
             // the prompt phase starts at the first uncached token; first the cached pages go to cache row 0 (the engine's cache
@@ -885,6 +1048,9 @@ struct ftcf_batcher : BatcherSched {
                 e->allgather_logits(gather, logits, B, st);
             }
         }
+        // the logit processors of the rows that have any: everything behind this point (beam kernels aside: their rows are not
+        // processed) reads the processed logits.  No such row: nothing is enqueued.
+        enqueue_decode_logit_stage(st);
         SamplingParams sp{};
         sp.logits = logits;
         sp.B = B;
@@ -1162,6 +1328,33 @@ extern "C" int ftcf_batcher_submit_ex(ftcf_batcher_t b, const int* prompt_ids, i
         FTCF_CHECK_ARG(b && request_id, "NULL argument");
         *request_id = b->submit(prompt_ids, prompt_len, max_new_tokens, top_k, top_p, temperature, (uint64_t)seed,
                                 repetition_penalty, stop_words, stop_len);
+    });
+}
+extern "C" int ftcf_batcher_submit_opts(ftcf_batcher_t b, const int* prompt_ids, int prompt_len, int max_new_tokens, int top_k,
+                                        float top_p, float temperature, float repetition_penalty, unsigned long long seed,
+                                        const int* stop_words, int stop_len, const ftcf_logit_options* opts, long* request_id)
+{
+    return guarded([&] {
+        FTCF_CHECK_ARG(b && request_id, "NULL argument");
+        ftcf_batcher::LogitOptions o;
+        // (a zeroed struct, struct_size included, asks for nothing)
+        const bool zeroed = opts && opts->struct_size == 0 && opts->presence_penalty == 0.f && opts->frequency_penalty == 0.f
+                            && opts->min_new_tokens == 0 && !opts->bias_ids && !opts->bias_values && opts->n_bias == 0
+                            && !opts->bad_words && opts->bad_words_len == 0;
+        if (opts && !zeroed) {
+            FTCF_CHECK_ARG(opts->struct_size == (int)sizeof(ftcf_logit_options), "struct_size is not sizeof(ftcf_logit_options)");
+            o = b->make_logit_options(opts->presence_penalty, opts->frequency_penalty, opts->min_new_tokens, opts->bias_ids,
+                                      opts->bias_values, opts->n_bias, opts->bad_words, opts->bad_words_len);
+        }
+        *request_id = b->submit_opts(prompt_ids, prompt_len, max_new_tokens, top_k, top_p, temperature, (uint64_t)seed,
+                                     repetition_penalty, stop_words, stop_len, std::move(o));
+    });
+}
+extern "C" int ftcf_batcher_set_token_mask(ftcf_batcher_t b, long request_id, const unsigned* allowed_bits, int n_words)
+{
+    return guarded([&] {
+        FTCF_CHECK_ARG(b, "NULL argument");
+        b->set_token_mask(request_id, allowed_bits, n_words);
     });
 }
 extern "C" int ftcf_batcher_submit_beam(ftcf_batcher_t b, const int* prompt_ids, int prompt_len, int max_new_tokens, int beam_width,

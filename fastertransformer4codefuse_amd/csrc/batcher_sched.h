@@ -14,6 +14,7 @@
 #include "prefix_index.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <deque>
@@ -26,6 +27,20 @@ namespace ftcf {
 
 struct BatcherSched {
     typedef std::vector<std::vector<int>> StopWords;  // stop sequences (token ids)
+    static constexpr int BIAS_MAX = 1024;  // logit-bias pairs per request (the logit stage's LOGIT_BIAS_MAX)
+    static constexpr int BAD_LW   = 256;   // total bad-word tokens per request (its LOGIT_BAD_WORDS_MAX)
+    // a request's logit processors (ftcf_batcher_submit_opts), checked; all defaults: none
+    struct LogitOptions {
+        float              presence = 0.f, frequency = 0.f;
+        int                min_new = 0;
+        std::vector<int>   bias_ids;
+        std::vector<float> bias_values;
+        std::vector<int>   bad;  // the [2][BAD_LW] word list of the device, or empty
+        bool any() const
+        {
+            return presence != 0.f || frequency != 0.f || min_new > 0 || !bias_ids.empty() || !bad.empty();
+        }
+    };
     struct Request {
         long             id;
         std::vector<int> prompt;
@@ -36,6 +51,8 @@ struct BatcherSched {
         int              beam_width = 1;     // > 1: a beam group (submit_beam)
         float            diversity = 0.f, len_penalty = 0.f;
         int              min_length = 0;     // beam requests: the end token is held back for this many new tokens
+        LogitOptions          lopt;  // ordinary requests: logit processors
+        std::vector<unsigned> mask;  // ... and the allowed-token mask set while it waits (empty: none)
     };
     struct Slot {
         bool             active = false;
@@ -49,6 +66,14 @@ struct BatcherSched {
         StopWords        stop;
         float            repetition_penalty = 1.f;
         int              group = -1;  // a beam of the group whose first slot this is (-1: an ordinary sequence)
+        // the request's logit processors and allowed-token mask; *_dirty: the device's copy of the slot's row is not this one yet
+        LogitOptions          lopt;
+        std::vector<unsigned> mask;
+        bool                  lopt_dirty = false, mask_dirty = false;
+        bool processed() const
+        {
+            return lopt.any() || !mask.empty();
+        }
     };
     // Beam search inside the batcher (round 4; the reference's serving layer runs beam requests through the same decoder:
     // triton_backend/gptneox/GptNeoXTritonModelInstance.cc).  A request of beam width K lives in K CONSECUTIVE slots -- its
@@ -301,6 +326,78 @@ struct BatcherSched {
         r.repetition_penalty = repetition_penalty;
         return enqueue(r, ids, n, stop_words, stop_len);
     }
+    // the logit processors of a request, checked (ftcf_batcher_submit_opts: what is invalid)
+    LogitOptions make_logit_options(float presence, float frequency, int min_new, const int* bias_ids, const float* bias_values,
+                                    int n_bias, const int* bad_words, int bad_len) const
+    {
+        LogitOptions o;
+        FTCF_CHECK_ARG(std::isfinite(presence) && std::isfinite(frequency), "presence_penalty and frequency_penalty must be finite");
+        FTCF_CHECK_ARG(min_new >= 0, "min_new_tokens must not be negative");
+        FTCF_CHECK_ARG(n_bias >= 0 && n_bias <= BIAS_MAX && (n_bias == 0 || (bias_ids && bias_values)), "logit_bias takes at most 1024 pairs");
+        FTCF_CHECK_ARG(bad_len >= 0 && bad_len <= BAD_LW && (bad_len == 0 || bad_words), "bad_words holds at most 256 tokens");
+        o.presence  = presence;
+        o.frequency = frequency;
+        o.min_new   = min_new;
+        std::set<int> seen;
+        for (int i = 0; i < n_bias; i++) {
+            FTCF_CHECK_ARG(bias_ids[i] >= 0 && bias_ids[i] < vocab, "logit_bias: token id out of range");
+            FTCF_CHECK_ARG(seen.insert(bias_ids[i]).second, "logit_bias: duplicate token id");
+            FTCF_CHECK_ARG(!std::isnan(bias_values[i]) && bias_values[i] != INFINITY, "logit_bias: a value is NaN or +inf");
+        }
+        o.bias_ids.assign(bias_ids, bias_ids + n_bias);
+        o.bias_values.assign(bias_values, bias_values + n_bias);
+        const StopWords words = parse_word_list(bad_words, bad_len);
+        if (!words.empty()) {
+            o.bad.assign(2 * BAD_LW, -1);
+            std::fill(o.bad.begin(), o.bad.begin() + BAD_LW, 0);
+            int pos = 0, k = 0;
+            for (const auto& wd : words) {
+                for (const int t : wd) {
+                    FTCF_CHECK_ARG(t >= 0 && t < vocab, "bad_words: token id out of range");
+                    o.bad[pos++] = t;
+                }
+                o.bad[BAD_LW + k++] = pos;
+            }
+        }
+        return o;
+    }
+    long submit_opts(const int* ids, int n, int max_new, int top_k, float top_p, float temperature, uint64_t seed,
+                     float repetition_penalty, const int* stop_words, int stop_len, LogitOptions opts)
+    {
+        const long id       = submit(ids, n, max_new, top_k, top_p, temperature, seed, repetition_penalty, stop_words, stop_len);
+        waiting.back().lopt = std::move(opts);
+        return id;
+    }
+    // the allowed-token mask of a waiting or running request (NULL clears it); the slot's device row follows before its next step
+    void set_token_mask(long id, const unsigned* bits, int n_words)
+    {
+        const int W = (vocab + 31) / 32;
+        std::vector<unsigned> m;
+        if (bits) {
+            FTCF_CHECK_ARG(n_words == W, "token mask: n_words must be ceil(vocab_size / 32)");
+            m.assign(bits, bits + W);
+            if (vocab % 32) {
+                m[W - 1] &= (1u << (vocab % 32)) - 1u;
+            }
+            FTCF_CHECK_ARG(std::any_of(m.begin(), m.end(), [](unsigned w) { return w != 0u; }), "token mask: no token of the vocabulary is allowed");
+        }
+        for (Request& r : waiting) {
+            if (r.id == id) {
+                FTCF_CHECK_ARG(r.beam_width == 1, "token mask: beam requests take no mask");
+                r.mask = std::move(m);
+                return;
+            }
+        }
+        for (Slot& s : slots) {
+            if (s.active && s.id == id) {
+                FTCF_CHECK_ARG(s.group < 0, "token mask: beam requests take no mask");
+                s.mask       = std::move(m);
+                s.mask_dirty = true;
+                return;
+            }
+        }
+        FTCF_CHECK_ARG(false, "token mask: no waiting or running request has this id");
+    }
     // a beam-search request (GptNeoXOp.forward with beam_width > 1: OnlineBeamSearchLayer): K consecutive slots; one event when
     // it has finished (token = -1), the K hypotheses through beam_result()
     long submit_beam(const int* ids, int n, int max_new, int beam_width, float diversity, float len_penalty, float temperature,
@@ -496,6 +593,9 @@ struct BatcherSched {
         s.hist.push_back(first);
         s.stop               = r.stop;
         s.repetition_penalty = r.repetition_penalty;
+        s.lopt               = r.lopt;
+        s.mask               = r.mask;
+        s.lopt_dirty = s.mask_dirty = true;
         s.active             = true;
         s.id                 = r.id;
         s.len                = (int)r.prompt.size();
@@ -556,6 +656,8 @@ struct BatcherSched {
             s.pages.clear();
             s.hist.clear();
             s.stop.clear();
+            s.lopt = LogitOptions{};
+            s.mask.clear();
             s.repetition_penalty = 1.f;  // (the beam kernels apply the request's penalty themselves)
         }
         g.generated = 1;

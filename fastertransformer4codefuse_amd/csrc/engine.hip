@@ -793,6 +793,42 @@ extern "C" int ftcf_dynamic_decode_step(const ftcf_dynamic_decode_args* a, void*
     });
 }
 
+extern "C" int ftcf_logit_process(const ftcf_logit_process_args* a, void* stream)
+{
+    return guarded([&] {
+        require_device();
+        FTCF_CHECK_ARG(a != nullptr, "NULL arguments");
+        FTCF_CHECK_ARG(a->struct_size == (int)sizeof(ftcf_logit_process_args), "logit process: struct_size is not sizeof(ftcf_logit_process_args)");
+        FTCF_CHECK_ARG(a->logits, "NULL tensor");
+        LogitProcessParams p{};
+        p.logits       = a->logits;
+        p.B            = a->batch_size;
+        p.V            = a->vocab_size;
+        p.end_id       = a->end_id;
+        p.finished     = a->finished;
+        p.row_on       = a->row_on;
+        p.hist         = a->hist;
+        p.stride_t     = a->stride_t;
+        p.stride_b     = a->stride_b;
+        p.hist_len     = a->hist_len;
+        p.gen_start    = a->gen_start;
+        p.hist_len_add = a->hist_len_add;
+        p.presence     = a->presence_penalty;
+        p.frequency    = a->frequency_penalty;
+        p.min_new      = a->min_new_tokens;
+        p.bias_ids     = a->bias_ids;
+        p.bias_values  = a->bias_values;
+        p.n_bias       = a->n_bias;
+        p.bias_stride  = a->bias_stride;
+        p.bad_words    = a->bad_words;
+        p.bad_len      = a->bad_words_len;
+        p.mask         = a->mask;
+        p.mask_on      = a->mask_on;
+        p.slice        = a->slice;
+        launch_logit_process(p, (hipStream_t)stream);
+    });
+}
+
 extern "C" int ftcf_beam_search_step(const ftcf_beam_search_args* a, void* stream)
 {
     return guarded([&] {
@@ -950,7 +986,7 @@ void ftcf_gptneox::begin(const ftcf_forward_args& a)
                 && verify_attention_supported(nhl, dh, total) && H % 64 == 0 && hl % 64 == 0 && il % 64 == 0 && !a.callback && !a.return_cum_log_probs
                 && !a.output_log_probs && a.top_logprobs == 0 && !a.debug_logits && !a.stop_words_list && !a.optional_last_tokens && a.n_min_length == 0
                 && (a.n_top_k == 0 || (a.top_k && a.top_k[0] <= 1)) && (a.n_top_p == 0 || (a.top_p && a.top_p[0] == 0.f))
-                && (a.n_repetition_penalty == 0 || (a.repetition_penalty && a.repetition_penalty[0] == 1.f));
+                && (a.n_repetition_penalty == 0 || (a.repetition_penalty && a.repetition_penalty[0] == 1.f)) && !logits_hook;
     if (spec) {  // (the token history must be dense from position 0: a prompt as long as its row)
         int h_len = 0;
         FTCF_HIP_CHECK(hipMemcpyAsync(&h_len, a.input_lengths, sizeof(int), hipMemcpyDeviceToHost, stream));
@@ -1250,7 +1286,7 @@ void ftcf_gptneox::enqueue_step(bool with_decoder)
         };
         // one GPU, <= 2 rows, an all-greedy step: the LM head launch picks the tokens, closes the step and prepares the next
         // token's input itself (k_lm_head_greedy) -- nothing is launched behind it
-        const bool lm_greedy = tp == 1 && fuse_ln && ses.K == 1 && lm_head_greedy_ok(ses.sp, H);
+        const bool lm_greedy = tp == 1 && fuse_ln && ses.K == 1 && !logits_hook && lm_head_greedy_ok(ses.sp, H);
         if (lm_greedy) {
             timed(KIND_LM_HEAD, 2.0 * V * H,
                   [&] { launch_lm_head_greedy(x, lm_head, logits, H, final_g, final_b, 1e-5f, ses.sp, stream); });
@@ -1268,6 +1304,9 @@ void ftcf_gptneox::enqueue_step(bool with_decoder)
         if (a.debug_logits) {
             FTCF_HIP_CHECK(hipMemcpyAsync(a.debug_logits + (size_t)(ses.next_step - S) * B * V, logits,
                                           (size_t)B * V * 4, hipMemcpyDeviceToDevice, stream));
+        }
+        if (logits_hook && ses.K == 1) {
+            logits_hook(logits, B, stream);
         }
     if (ses.K > 1) {
         dynamic_decode_layer.forward(ses.bp, ses.sp, stream);
@@ -1302,7 +1341,7 @@ int ftcf_gptneox::step(int max_steps)
         const bool with_decoder = !(S > 1 && step == S);
         // (with tensor parallelism the step contains RCCL collectives or the exchange windows' spins: not captured -- a capture
         // of the RCCL form aborted inside this image's HIP runtime, profiles/r05_notes.md)
-        const bool graph_ok     = use_graph && with_decoder && !profiling && tp == 1 && !a.debug_logits;
+        const bool graph_ok     = use_graph && with_decoder && !profiling && tp == 1 && !a.debug_logits && !logits_hook;
         // Several tokens per graph launch (FTCF_GRAPH_TOKENS, default 8): a graph launch costs ~14 us of GPU idle time between
         // two tokens (profiles/r03_notes.md section 6), and every kernel of a persistent-path token returns at once when the
         // device-side "every row has finished" flag is set, so the tokens of a graph behind the request's last one cost a few

@@ -663,6 +663,11 @@ struct ftcf_gptneox {
     std::function<void()> prefill_hook;
     int                   prefill_begin = 0;
     std::function<void()> prefill_prefix;
+    // The batcher's logit processors on an admission's FIRST token: when set, every step of the request materialises its logits
+    // [rows, V] (no one-launch LM head + greedy step, no captured graph, no speculation) and calls the hook on the engine's stream
+    // between the LM head (all-gather included) and the dynamic decode -- the way top_logprobs leaves the one-launch greedy step.
+    // Beam requests do not call it.  Set and reset around one forward() like the members above; unset, nothing changes.
+    std::function<void(float* logits, int rows, hipStream_t stream)> logits_hook;
     static bool chunked_supported(bool fp32_, int tp, bool gptj, int H_) { return !fp32_ && tp == 1 && gptj && residual_dual_ln_supported(H_); }
     bool context_decoder_chunked(int S, const int* input_lengths, int s_max, int tile = 1)
     {

@@ -532,4 +532,34 @@ struct VerifyAcceptParams {
 };
 void launch_verify_accept(const VerifyAcceptParams& p, hipStream_t s);
 
+// ---- per-request logit processors over logits [B, V] fp32, in place, BEFORE the dynamic decode : kernels_logits.hip ----
+// (include/ftcf.h ftcf_logit_process_args is the contract; the fields are its fields.)  A row is processed when it is enabled
+// (row_on NULL: every row), not finished and has at least one option set; every other row keeps its bits.
+struct LogitProcessParams {
+    float*          logits;  // [B, V]
+    int             B, V, end_id;
+    const uint8_t*  finished;  // [B] or NULL
+    const uint8_t*  row_on;    // [B] or NULL
+    // token t of row b: hist[t * stride_t + b * stride_b], t in [0, hist_len[b] + hist_len_add); generated from gen_start[b] on
+    const int*      hist;
+    long long       stride_t, stride_b;
+    const int*      hist_len;
+    const int*      gen_start;
+    int             hist_len_add;
+    const float*    presence;  // [B] or NULL
+    const float*    frequency;
+    const int*      min_new;   // [B] or NULL
+    const int*      bias_ids;  // [B, bias_stride]
+    const float*    bias_values;
+    const int*      n_bias;    // [B] or NULL
+    int             bias_stride;
+    const int*      bad_words;  // [B, 2, bad_len] or NULL
+    int             bad_len;
+    const unsigned* mask;     // [B, ceil(V / 32)] or NULL
+    const uint8_t*  mask_on;  // [B] or NULL (every row has a mask)
+    int             slice;    // logits per workgroup: a multiple of 32 in [32, LOGIT_SLICE_MAX], 0 = LOGIT_SLICE_DEFAULT
+};
+constexpr int LOGIT_SLICE_MAX = 4096, LOGIT_SLICE_DEFAULT = 2048, LOGIT_BIAS_MAX = 1024, LOGIT_BAD_WORDS_MAX = 256;
+void launch_logit_process(const LogitProcessParams& p, hipStream_t s);
+
 }  // namespace ftcf

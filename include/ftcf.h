@@ -323,6 +323,57 @@ typedef struct {
     int B, K, V, step, max_input_len, total_len, s_max, end_id;
 } ftcf_beam_search_args;
 int ftcf_beam_search_step(const ftcf_beam_search_args* args, void* stream);
+/* Per-request LOGIT PROCESSORS: one stage over logits [batch_size, vocab_size] fp32 (device, modified in place), to run between
+ * the LM head and ftcf_dynamic_decode_step (the continuous batcher runs it there: ftcf_batcher_submit_opts /
+ * ftcf_batcher_set_token_mask).  A row is processed when row_on[b] != 0 (row_on NULL: every row), finished[b] == 0 (NULL: no row
+ * is finished) and at least one option below is set for it; every other row keeps its bits.  For a processed row, in this order:
+ *   1. penalties over the GENERATED tokens only (the prompt is the business of the multiplicative repetition_penalty of the
+ *      dynamic decode, which runs afterwards): c[t] = occurrences of t among the row's history positions [gen_start[b], len_b),
+ *      logit[t] -= presence_penalty[b] * (c[t] > 0) + frequency_penalty[b] * c[t]
+ *      (the additive form of kernels/sampling_penalty_kernels.cu);
+ *   2. logit[bias_ids[b][i]] += bias_values[b][i] for i < n_bias[b] <= 1024; -INFINITY bans the token.  The ids of a row are
+ *      distinct and in [0, vocab_size): the CALLER checks that (ids outside the vocabulary are ignored, a repeated id takes one
+ *      of its values);
+ *   3. while len_b - gen_start[b] < min_new_tokens[b]: logit[end_id] = -inf;
+ *   4. bad words, the reference's word list [2][bad_words_len] per row (ids back to back, then cumulative end offsets, -1
+ *      padded; bad_words_len <= 256): a one-token word is banned, an n-token word bans its last token when its first n - 1 are
+ *      the last n - 1 tokens of the history, prompt and generated alike (kernels/ban_bad_words.cu:42-85; unlike there token 0
+ *      can be banned);
+ *   5. mask[b] = ceil(vocab_size / 32) words, bit t clear: logit[t] = -inf (rows with mask_on[b] != 0; mask_on NULL: every row);
+ *   6. the guard: a row left without one finite logit gets logit[end_id] = 0 (the sampling kernels never see an all -inf row).
+ * History: token t of row b is hist[t * stride_t + b * stride_b] (elements), len_b = hist_len[b] + hist_len_add, gen_start[b]
+ * is clamped to [0, len_b]; hist NULL: every history is empty.  All pointers are device pointers; presence_penalty /
+ * frequency_penalty / min_new_tokens / n_bias [batch_size] or NULL, bias_ids / bias_values [batch_size, bias_stride].
+ * A penalised or biased logit is the exact sum rounded to fp32 once (fp64 inside); banned and masked logits are exactly -inf,
+ * every other logit keeps its bits.  Every logit is written by one workgroup: the result does not depend on `slice` (logits per
+ * workgroup, a multiple of 32 in [32, 4096]; 0 = the default), and two runs are bit-identical.  Enqueues two launches on
+ * `stream` and does not synchronise.  struct_size != sizeof(ftcf_logit_process_args), end_id outside the vocabulary, a bad
+ * slice or bad_words_len: FTCF_ERR_INVALID_ARG. */
+typedef struct {
+    int             struct_size;
+    int             batch_size, vocab_size, end_id;
+    float*          logits;
+    const uint8_t*  finished;
+    const uint8_t*  row_on;
+    const int*      hist;
+    long long       stride_t, stride_b;
+    const int*      hist_len;
+    const int*      gen_start;
+    int             hist_len_add;
+    int             bias_stride;
+    const float*    presence_penalty;
+    const float*    frequency_penalty;
+    const int*      min_new_tokens;
+    const int*      bias_ids;
+    const float*    bias_values;
+    const int*      n_bias;
+    const int*      bad_words;
+    int             bad_words_len;
+    int             slice;
+    const unsigned* mask;
+    const uint8_t*  mask_on;
+} ftcf_logit_process_args;
+int ftcf_logit_process(const ftcf_logit_process_args* args, void* stream);
 
 /* ================================================================================================
  * libth_gptneox counterpart -- the engine behind GptNeoXOp
@@ -559,6 +610,37 @@ int ftcf_batcher_submit(ftcf_batcher_t b, const int* prompt_ids, int prompt_len,
 int ftcf_batcher_submit_ex(ftcf_batcher_t b, const int* prompt_ids, int prompt_len, int max_new_tokens, int top_k, float top_p,
                            float temperature, float repetition_penalty, unsigned long long seed, const int* stop_words,
                            int stop_len, long* request_id);
+/* The same with per-request LOGIT PROCESSORS (ftcf_logit_process above defines each of them and their order; they apply to
+ * every token of the request, the first one included, before the sampling parameters do -- log_probs and top_logprobs of the
+ * step calls are those of the processed distribution).  All arrays are HOST arrays, copied by the call.
+ *   presence_penalty / frequency_penalty  over the request's generated tokens (finite);
+ *   min_new_tokens                        the end token is held back for that many new tokens (>= 0);
+ *   bias_ids / bias_values [n_bias]       the sparse logit bias, n_bias <= 1024, distinct ids in [0, V), values not NaN and not +inf;
+ *   bad_words [2][bad_words_len]          banned words in the layout of stop_words, bad_words_len <= 256.
+ * opts == NULL, or options that are all zero, is exactly ftcf_batcher_submit_ex.  struct_size must be
+ * sizeof(ftcf_logit_options); anything outside the ranges above is FTCF_ERR_INVALID_ARG and nothing is queued.  Beam requests
+ * take no options. */
+typedef struct {
+    int          struct_size;
+    float        presence_penalty;
+    float        frequency_penalty;
+    int          min_new_tokens;
+    const int*   bias_ids;
+    const float* bias_values;
+    int          n_bias;
+    const int*   bad_words;
+    int          bad_words_len;
+} ftcf_logit_options;
+int ftcf_batcher_submit_opts(ftcf_batcher_t b, const int* prompt_ids, int prompt_len, int max_new_tokens, int top_k, float top_p,
+                             float temperature, float repetition_penalty, unsigned long long seed, const int* stop_words,
+                             int stop_len, const ftcf_logit_options* opts, long* request_id);
+/* The ALLOWED-TOKEN MASK of a waiting or running request (the hook of grammar-constrained decoding): allowed_bits is a HOST
+ * array of n_words = ceil(V / 32) words, bit t set: token t may be sampled.  It applies to every token sampled for the request
+ * from the next one on -- set on a waiting request it governs the first token -- until it is replaced; allowed_bits == NULL
+ * clears it.  May be called from inside the token callback.  A mask is copied to the device before the next step only when it
+ * changed.  A mask without a bit in [0, V), a wrong n_words, an unknown or finished request and a beam request are
+ * FTCF_ERR_INVALID_ARG.  A request whose options and mask leave no token ends with end_id. */
+int ftcf_batcher_set_token_mask(ftcf_batcher_t b, long request_id, const unsigned* allowed_bits, int n_words);
 /* A beam-search request (GptNeoXOp.forward with beam_width > 1: OnlineBeamSearchLayer semantics, the engine's own beam kernels):
  * it occupies `beam_width` consecutive slots, its beams share the prompt's pages and every page they have in common (copy on
  * write).  ftcf_batcher_step reports ONE event for it, when it has finished: token = -1, finished = 1; the hypotheses are
