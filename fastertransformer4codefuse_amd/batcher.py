@@ -9,6 +9,8 @@
     cb.set_token_mask(rid, allowed_ids)                      # the next tokens come from this set (grammar-constrained decoding)
     bid = cb.submit_beam(prompt_ids, 128, beam_width=4)      # beam search: one event (bid, -1, True), then cb.beam_result(bid)
     ContinuousBatcher(op, ..., prefix_cache=True)             # reuse the K/V pages of shared prompt prefixes (prefix_stats())
+    ContinuousBatcher(op, ..., overcommit=True, swap_pages=0) # pages on demand, the latest arrival swapped to host memory when
+                                                             # the pool runs dry (preempt_stats()); streams stay exact
     while cb.busy():
         for request_id, token, finished in cb.step():
             ...
@@ -73,13 +75,23 @@ def pack_logit_options(logit_bias=None, bad_words=None, presence_penalty=0.0, fr
 
 
 class ContinuousBatcher:
-    def __init__(self, op, max_batch, page_tokens, num_pages, max_seq_len, prefix_cache=False):
+    def __init__(self, op, max_batch, page_tokens, num_pages, max_seq_len, prefix_cache=False, overcommit=False, swap_pages=0):
         """prefix_cache=True: full prompt blocks of page_tokens tokens stay cached in the pool and later prompts that start with
-        them reuse their K/V (ftcf_batcher_create_ex); refused for tensor_para_size > 1 and fp32 engines."""
+        them reuse their K/V (ftcf_batcher_create_ex); refused for tensor_para_size > 1 and fp32 engines.
+        overcommit=True (ftcf_batcher_create_opts): requests take pages as their sequences grow instead of reserving
+        prompt + max_new_tokens at admission; when the pool runs dry the latest arrival is swapped out to swap_pages pinned host
+        pages (0: num_pages) and resumes later, token for token as if it had never left (preempt_stats()); refused for
+        tensor_para_size > 1."""
         self._op = op  # keeps the engine (and its weights) alive
         self.max_batch = int(max_batch)
         self._h = C.c_void_p()
-        if prefix_cache:
+        if overcommit:
+            o = capi.BatcherOptions()
+            o.struct_size = C.sizeof(capi.BatcherOptions)
+            o.max_batch, o.page_tokens, o.num_pages, o.max_seq_len = int(max_batch), int(page_tokens), int(num_pages), int(max_seq_len)
+            o.prefix_cache, o.overcommit, o.swap_pages, o.swap_stage_bytes = int(bool(prefix_cache)), 1, int(swap_pages), 0
+            capi.check(capi.lib().ftcf_batcher_create_opts(op._h, C.byref(o), C.byref(self._h)))
+        elif prefix_cache:
             capi.check(capi.lib().ftcf_batcher_create_ex(op._h, int(max_batch), int(page_tokens), int(num_pages), int(max_seq_len), 1,
                                                          C.byref(self._h)))
         else:
@@ -247,6 +259,16 @@ class ContinuousBatcher:
                                                         C.byref(pt), C.byref(ht), C.byref(ct), C.byref(ev)))
         return {"enabled": en.value, "cached_pages": cached.value, "evictable_pages": evictable.value, "lookups": lk.value,
                 "prompt_tokens": pt.value, "hit_tokens": ht.value, "computed_tokens": ct.value, "evictions": ev.value}
+
+    def preempt_stats(self):
+        """Counters of overcommit: enabled, swapped_requests (swapped out now), swap_pages_used, swap_pages_total, preemptions,
+        resumes, pages_out, pages_in (all 0 without overcommit)."""
+        en, sw, used, total = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        pre, res, po, pi = C.c_long(0), C.c_long(0), C.c_long(0), C.c_long(0)
+        capi.check(capi.lib().ftcf_batcher_preempt_stats(self._h, C.byref(en), C.byref(sw), C.byref(used), C.byref(total),
+                                                         C.byref(pre), C.byref(res), C.byref(po), C.byref(pi)))
+        return {"enabled": en.value, "swapped_requests": sw.value, "swap_pages_used": used.value, "swap_pages_total": total.value,
+                "preemptions": pre.value, "resumes": res.value, "pages_out": po.value, "pages_in": pi.value}
 
     def clear_prefix_cache(self):
         """Drops every cached page that no request is using (they return to the free list)."""

@@ -102,6 +102,11 @@ class LogitOptions(C.Structure):  # ftcf_logit_options
                 ("n_bias", C.c_int), ("bad_words", C.POINTER(C.c_int)), ("bad_words_len", C.c_int)]
 
 
+class BatcherOptions(C.Structure):  # ftcf_batcher_options
+    _fields_ = [(n, C.c_int) for n in ("struct_size", "max_batch", "page_tokens", "num_pages", "max_seq_len", "prefix_cache",
+                                       "overcommit", "swap_pages")] + [("swap_stage_bytes", C.c_size_t)]
+
+
 class BeamSearchArgs(C.Structure):  # ftcf_beam_search_args
     _fields_ = [(n, C.c_void_p) for n in (
         "logits", "output_ids", "parent_ids", "finished", "seq_len", "cum_log_probs", "cache_indir", "input_lengths",
@@ -134,14 +139,14 @@ EXPORTED = [
     "ftcf_masked_multihead_attention", "ftcf_masked_multihead_attention_workspace", "ftcf_masked_multihead_attention_beams",
     "ftcf_context_attention",
     "ftcf_verify_attention", "ftcf_verify_attention_workspace", "ftcf_ngram_draft",
-    "ftcf_paged_attention", "ftcf_scatter_kv_to_pages", "ftcf_gather_pages_to_kv",
+    "ftcf_paged_attention", "ftcf_scatter_kv_to_pages", "ftcf_gather_pages_to_kv", "ftcf_pages_pack", "ftcf_pages_unpack",
     "ftcf_dynamic_decode_step", "ftcf_beam_search_step", "ftcf_logit_process",
     "ftcf_comm_get_unique_id", "ftcf_comm_init", "ftcf_comm_destroy", "ftcf_comm_local_unique_id",
     "ftcf_comm_init_local", "ftcf_comm_init_host_exchange", "ftcf_comm_allreduce_sum",
     "ftcf_comm_allgather", "ftcf_gptneox_create", "ftcf_gptneox_forward", "ftcf_gptneox_begin", "ftcf_gptneox_step", "ftcf_gptneox_finish",
     "ftcf_gptneox_get_stats",
     "ftcf_gptneox_set_profiling", "ftcf_gptneox_destroy",
-    "ftcf_batcher_create", "ftcf_batcher_create_ex", "ftcf_batcher_prefix_stats", "ftcf_batcher_clear_prefix_cache", "ftcf_batcher_submit", "ftcf_batcher_submit_ex", "ftcf_batcher_submit_opts", "ftcf_batcher_set_token_mask", "ftcf_batcher_submit_beam", "ftcf_batcher_submit_beam_ex", "ftcf_batcher_beam_result", "ftcf_batcher_step", "ftcf_batcher_step_ex", "ftcf_batcher_step_top", "ftcf_batcher_set_token_callback", "ftcf_batcher_status", "ftcf_batcher_cancel", "ftcf_batcher_destroy"]
+    "ftcf_batcher_create", "ftcf_batcher_create_ex", "ftcf_batcher_create_opts", "ftcf_batcher_preempt_stats", "ftcf_batcher_prefix_stats", "ftcf_batcher_clear_prefix_cache", "ftcf_batcher_submit", "ftcf_batcher_submit_ex", "ftcf_batcher_submit_opts", "ftcf_batcher_set_token_mask", "ftcf_batcher_submit_beam", "ftcf_batcher_submit_beam_ex", "ftcf_batcher_beam_result", "ftcf_batcher_step", "ftcf_batcher_step_ex", "ftcf_batcher_step_top", "ftcf_batcher_set_token_callback", "ftcf_batcher_status", "ftcf_batcher_cancel", "ftcf_batcher_destroy"]
 
 _lib = None
 

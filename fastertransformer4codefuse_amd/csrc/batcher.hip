@@ -15,7 +15,7 @@
 //   * `max_batch` SLOTS: page table, length, last token, sampling parameters of the sequence living there;
 //   * a queue of waiting requests.
 // One iteration (ftcf_batcher_step) = ADMIT waiting requests into free slots while their pages (prompt + max_new_tokens,
-// reserved up front: a running sequence never has to be preempted) are available, then ONE decode step for all running
+// reserved up front: by default a running sequence never has to be preempted) are available, then ONE decode step for all running
 // slots.  Admission runs the prompt through the engine's own context path (ftcf_gptneox_forward with output_len 1: prefill +
 // first token sampled by the engine's dynamic decode) and scatters the prompt's K/V into the slot's pages; the decode
 // step is the general layer sequence of the engine (§4a: dual LayerNorm, burst / tiled GEMMs, fused residual) with the
@@ -27,6 +27,10 @@
 // (prefix_index.h); a request whose prompt starts with cached blocks takes those pages, k_gather_pages_to_kv copies them into
 // the engine's cache and the prompt phase runs from the first uncached token (context_decoder_chunked with prefill_begin).
 // Beam requests neither read nor populate it.
+// Overcommit (ftcf_batcher_create_opts, off by default; batcher_sched.h): requests take their pages as they grow; when
+// the pool runs dry the latest arrival among the running ordinary requests is swapped out -- k_pages_pack into a staging buffer,
+// a linear copy to pinned host pages -- and resumes later in any free slot on fresh pages (the reverse with k_pages_unpack), its
+// device state uploaded by the function an admission uses (upload_slot_state).  Beam groups are never swapped.
 // ---------------------------------------------------------------------------------------------------------------
 __global__ void k_batcher_embed(f16* out, const f16* table, const int* tok, int H)
 {
@@ -158,6 +162,14 @@ struct ftcf_batcher : BatcherSched {
     unsigned     smallm_seq = 0;
     long         gemm_steps = 0;
     std::vector<void*> owned;
+    // overcommit (batcher_sched.h): the swap space -- `swap_total` host pages of page_all_elems fp16 (one page of every layer of
+    // both pools) in ONE pinned region, and the device staging buffer of stage_pages such pages the copies go through
+    void*            swap_host = nullptr;
+    f16*             swap_stage = nullptr;
+    int              stage_pages = 0;
+    size_t           page_all_elems = 0;
+    int*             d_swap_list = nullptr;
+    std::vector<int> swap_list_host, grow_host;
     // Logit processors (kernels_logits.hip): the options and masks of `rows` rows on the device with their host mirrors -- one set
     // indexed by slot for the decode steps, one by the rows of an admission's ragged batch for its first tokens.  The host
     // mirrors are members: an asynchronous copy reads them until the step's synchronisation, and nobody changes them before it.
@@ -308,11 +320,18 @@ struct ftcf_batcher : BatcherSched {
         for (void* p : owned) {
             (void)hipFree(p);
         }
+        if (swap_host) {
+            (void)hipHostFree(swap_host);
+        }
     }
 
-    void init(ftcf_gptneox* eng, int mb, int page_tokens, int pages, int max_seq_len, bool prefix_cache = false)
+    void init(ftcf_gptneox* eng, int mb, int page_tokens, int pages, int max_seq_len, bool prefix_cache = false,
+              bool overcommit_on = false, int swap_pages = 0, size_t swap_stage_bytes = 0)
     {
         e = eng;
+        FTCF_CHECK_ARG(!overcommit_on || e->cfg.tensor_para_size == 1,
+                       "overcommit needs tensor_para_size 1 (every rank would have to swap the same requests: not built)");
+        FTCF_CHECK_ARG(swap_pages >= 0, "swap_pages must not be negative");
         FTCF_CHECK_ARG(!prefix_cache
                            || ftcf_gptneox::chunked_supported(e->fp32, e->cfg.tensor_para_size, e->cfg.use_gptj_residual, e->H),
                        "the prefix cache needs an fp16 / int8 engine with tensor_para_size 1, parallel residual and a hidden size "
@@ -422,6 +441,19 @@ struct ftcf_batcher : BatcherSched {
         }
         std::vector<uint8_t> fin(max_batch, 1);
         FTCF_HIP_CHECK(hipMemcpy(d_fin, fin.data(), max_batch, hipMemcpyHostToDevice));
+        if (overcommit_on) {
+            init_overcommit(swap_pages);
+            page_all_elems = 2 * (size_t)L * e->nhl * P * e->dh;
+            const size_t want = swap_stage_bytes ? swap_stage_bytes : (size_t)64 << 20;
+            // at least one page of all layers; no more than one request's pages (nobody swaps more at a time) and than one launch of
+            // the copy kernels takes (2^31 16-byte pieces)
+            stage_pages = (int)std::min<size_t>(std::max<size_t>(want / (page_all_elems * sizeof(f16)), 1), (size_t)max_pages);
+            stage_pages = (int)std::max<size_t>(std::min<size_t>((size_t)stage_pages, (((size_t)1 << 31) - 1) / (page_all_elems / 8)), 1);
+            swap_stage  = dmalloc<f16>((size_t)stage_pages * page_all_elems, false);
+            d_swap_list = dmalloc<int>(max_pages);
+            grow_host.assign(max_batch, 0);
+            FTCF_HIP_CHECK(hipHostMalloc(&swap_host, (size_t)swap_total * page_all_elems * sizeof(f16), hipHostMallocDefault));
+        }
     }
 
     struct Event {
@@ -491,6 +523,127 @@ struct ftcf_batcher : BatcherSched {
             e->logits_hook = nullptr;
         }
     };
+
+    // The device's per-slot state of the decode steps, from the slot's host fields: length, last token, token history (time-major
+    // column si), sampling parameters, seed, and what the caller knows of the device's own counters -- draws made so far and
+    // the cumulative log-probability.  A fresh admission and a resume after a swap go through here; the slot is live afterwards
+    // (d_fin = 0).  Host synchronous: the temporaries die here.
+    void upload_slot_state(const int si, const Slot& s, const uint64_t draws, const float cum, hipStream_t st)
+    {
+        const int     len = s.len, last = s.hist.back(), k_eff = keff(s.top_k, s.top_p);
+        const float   ptk = (s.top_p == 0.f) ? 1.f : s.top_p;
+        const uint8_t zero8 = 0;
+        FTCF_HIP_CHECK(hipMemcpyAsync(d_len + si, &len, 4, hipMemcpyHostToDevice, st));
+        FTCF_HIP_CHECK(hipMemcpyAsync(d_tok + si, &last, 4, hipMemcpyHostToDevice, st));
+        FTCF_HIP_CHECK(hipMemcpyAsync(d_topk + si, &k_eff, 4, hipMemcpyHostToDevice, st));
+        FTCF_HIP_CHECK(hipMemcpyAsync(d_ptopk + si, &ptk, 4, hipMemcpyHostToDevice, st));
+        FTCF_HIP_CHECK(hipMemcpyAsync(d_ptopp + si, &s.top_p, 4, hipMemcpyHostToDevice, st));
+        FTCF_HIP_CHECK(hipMemcpyAsync(d_temp + si, &s.temperature, 4, hipMemcpyHostToDevice, st));
+        FTCF_HIP_CHECK(hipMemcpyAsync(d_rep + si, &s.repetition_penalty, 4, hipMemcpyHostToDevice, st));
+        FTCF_HIP_CHECK(hipMemcpy2DAsync(d_hist + si, (size_t)max_batch * 4, s.hist.data(), 4, 4, s.hist.size(), hipMemcpyHostToDevice, st));
+        FTCF_HIP_CHECK(hipMemcpyAsync(d_seed + si, &s.seed, 8, hipMemcpyHostToDevice, st));
+        FTCF_HIP_CHECK(hipMemcpyAsync(d_draws + si, &draws, 8, hipMemcpyHostToDevice, st));
+        FTCF_HIP_CHECK(hipMemcpyAsync(d_cum + si, &cum, 4, hipMemcpyHostToDevice, st));
+        FTCF_HIP_CHECK(hipMemcpyAsync(d_fin + si, &zero8, 1, hipMemcpyHostToDevice, st));
+        FTCF_HIP_CHECK(hipStreamSynchronize(st));
+    }
+
+    // ---- overcommit: the device half of a preemption and of a resume (batcher_sched.h: preempt / resume) -------------------------
+    char* host_page(const int hp) const
+    {
+        return reinterpret_cast<char*>(swap_host) + (size_t)hp * page_all_elems * sizeof(f16);
+    }
+    // staging <-> the host pages host[c0 .. c0 + nc), one linear copy per run of consecutive host pages
+    void copy_host_pages(const std::vector<int>& host, const int c0, const int nc, const bool out, hipStream_t st)
+    {
+        const size_t pb = page_all_elems * sizeof(f16);
+        for (int j = 0, run; j < nc; j += run) {
+            for (run = 1; j + run < nc && host[c0 + j + run] == host[c0 + j] + run;) {
+                run++;
+            }
+            char* dev = reinterpret_cast<char*>(swap_stage) + (size_t)j * pb;
+            FTCF_CHECK_ARG(host[c0 + j] >= 0 && host[c0 + j] + run <= swap_total, "batcher: a host page outside the swap space");
+            if (out) {
+                FTCF_HIP_CHECK(hipMemcpyAsync(host_page(host[c0 + j]), dev, (size_t)run * pb, hipMemcpyDeviceToHost, st));
+            }
+            else {
+                FTCF_HIP_CHECK(hipMemcpyAsync(dev, host_page(host[c0 + j]), (size_t)run * pb, hipMemcpyHostToDevice, st));
+            }
+        }
+    }
+    void upload_swap_list(const std::vector<int>& pages, hipStream_t st)
+    {
+        FTCF_CHECK_ARG((int)pages.size() <= max_pages, "batcher: a page list longer than max_pages");
+        for (const int pg : pages) {
+            FTCF_CHECK_ARG(pg >= 0 && pg < num_pages, "batcher: a page outside the pool");
+        }
+        swap_list_host = pages;  // (a member: the asynchronous copy reads it until the synchronisation that ends the swap)
+        FTCF_HIP_CHECK(hipMemcpyAsync(d_swap_list, swap_list_host.data(), pages.size() * 4, hipMemcpyHostToDevice, st));
+    }
+    // every page of the victim's list -> its host pages, in chunks of whole pages through the staging buffer (k_pages_pack, then
+    // the linear copy; stream order alone keeps a chunk's pack behind the previous chunk's copy); the draw counter and the
+    // cumulative log-probability come back with the same synchronisation; the device learns the slot is finished
+    void swap_out_dev(const int si, const std::vector<int>& pages, const std::vector<int>& host, uint64_t& draws, float& cum)
+    {
+        Range       rg("ftcf.batcher.swap_out");
+        hipStream_t st = e->stream;
+        const int   n  = (int)pages.size();
+        FTCF_CHECK_ARG(host.size() == pages.size(), "batcher: a victim's host pages do not match its page list");
+        upload_swap_list(pages, st);
+        for (int c0 = 0; c0 < n; c0 += stage_pages) {
+            const int nc = std::min(stage_pages, n - c0);
+            launch_pages_pack(swap_stage, kpool, vpool, d_swap_list + c0, nc, e->L, page_all_elems / (2 * (size_t)e->L), pool_layer_elems, st);
+            copy_host_pages(host, c0, nc, true, st);
+        }
+        const uint8_t one8 = 1;
+        FTCF_HIP_CHECK(hipMemcpyAsync(&draws, d_draws + si, 8, hipMemcpyDeviceToHost, st));
+        FTCF_HIP_CHECK(hipMemcpyAsync(&cum, d_cum + si, 4, hipMemcpyDeviceToHost, st));
+        FTCF_HIP_CHECK(hipMemcpyAsync(d_fin + si, &one8, 1, hipMemcpyHostToDevice, st));
+        FTCF_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    // the reverse into the first pages of the slot's fresh list (k_pages_unpack), then the slot's page table row and its state
+    // through the function an admission uses
+    void swap_in_dev(const int si, const Swapped& w, const std::vector<int>& pages)
+    {
+        Range       rg("ftcf.batcher.swap_in");
+        hipStream_t st = e->stream;
+        const int   n  = (int)w.host.size();
+        FTCF_CHECK_ARG(n <= (int)pages.size(), "batcher: a resumed request has more host pages than its new page list");
+        upload_swap_list(pages, st);
+        for (int c0 = 0; c0 < n; c0 += stage_pages) {
+            const int nc = std::min(stage_pages, n - c0);
+            copy_host_pages(w.host, c0, nc, false, st);
+            launch_pages_unpack(swap_stage, kpool, vpool, d_swap_list + c0, nc, e->L, page_all_elems / (2 * (size_t)e->L), pool_layer_elems, st);
+        }
+        std::vector<int> row(max_pages, 0);
+        std::copy(pages.begin(), pages.end(), row.begin());
+        FTCF_HIP_CHECK(hipMemcpyAsync(d_pt + (size_t)si * max_pages, row.data(), (size_t)max_pages * 4, hipMemcpyHostToDevice, st));
+        upload_slot_state(si, slots[si], w.draws, w.cum, st);  // (host synchronous)
+    }
+    // before a decode step enqueues anything: the slots whose next token starts a page take it (preempting when the pool has
+    // none); their page table rows get the new entry
+    void grow_before_decode(hipStream_t st)
+    {
+        try {
+            grow_slots(
+                [this](int si, const std::vector<int>& pages, const std::vector<int>& host, uint64_t& draws, float& cum) {
+                    swap_out_dev(si, pages, host, draws, cum);
+                },
+                // ONE growth: the row's new last entry goes up the moment the host has handed the page out, so that a failure at a
+                // later slot ("swap space exhausted", a HIP error of a swap-out) leaves no page the device does not know of
+                [this, st](int si) {
+                    const int k = (int)slots[si].pages.size() - 1;
+                    FTCF_CHECK_ARG(k >= 0 && k < max_pages && slots[si].pages[k] >= 0 && slots[si].pages[k] < num_pages,
+                                   "batcher: a page list outgrew max_pages");
+                    grow_host[si] = slots[si].pages[k];  // (a member: read by the copy until the step's synchronisation)
+                    FTCF_HIP_CHECK(hipMemcpyAsync(d_pt + (size_t)si * max_pages + k, &grow_host[si], 4, hipMemcpyHostToDevice, st));
+                });
+        }
+        catch (...) {
+            (void)hipStreamSynchronize(st);  // (no decode step follows: the entries already enqueued land before the caller goes on)
+            throw;
+        }
+    }
 
     // prompts -> ONE ragged batch through the engine's context path (+ first tokens) -> pages of their slots
     // hit (one request only): the cached pages of its first prompt blocks (pinned here: the slot's page list owns one reference)
@@ -618,28 +771,9 @@ struct ftcf_batcher : BatcherSched {
                                        e->v_cache + (size_t)i * row_kv + (size_t)hit_tokens * e->dh, kpool, vpool,
                                        d_pt + (size_t)si * max_pages + hit_tokens / P, e->L, e->nhl, e->dh, S + 1, len - hit_tokens, P,
                                        pool_layer_elems, st, (size_t)n * row_kv);
-            // per-slot state of the decode steps
-            const int      k_eff = keff(r.top_k, r.top_p);
-            const float    ptk = (r.top_p == 0.f) ? 1.f : r.top_p;
-            const uint8_t  zero8 = 0;
-            const uint64_t one = 1;
-            const float    zf = 0.f;
-            FTCF_HIP_CHECK(hipMemcpyAsync(d_len + si, &len, 4, hipMemcpyHostToDevice, st));
-            FTCF_HIP_CHECK(hipMemcpyAsync(d_tok + si, &first, 4, hipMemcpyHostToDevice, st));
-            FTCF_HIP_CHECK(hipMemcpyAsync(d_topk + si, &k_eff, 4, hipMemcpyHostToDevice, st));
-            FTCF_HIP_CHECK(hipMemcpyAsync(d_ptopk + si, &ptk, 4, hipMemcpyHostToDevice, st));
-            FTCF_HIP_CHECK(hipMemcpyAsync(d_ptopp + si, &r.top_p, 4, hipMemcpyHostToDevice, st));
-            FTCF_HIP_CHECK(hipMemcpyAsync(d_temp + si, &r.temperature, 4, hipMemcpyHostToDevice, st));
-            FTCF_HIP_CHECK(hipMemcpyAsync(d_rep + si, &r.repetition_penalty, 4, hipMemcpyHostToDevice, st));
-            // the slot's token history, time-major column si: prompt, then the first token
+            // per-slot state of the decode steps: the history is prompt, then the first token; draw 0 went to the first token
             const int done = start_slot(si, r, first, e->cfg.end_id) ? 1 : 0;
-            FTCF_HIP_CHECK(hipMemcpy2DAsync(d_hist + si, (size_t)max_batch * 4, s.hist.data(), 4, 4, s.hist.size(),
-                                            hipMemcpyHostToDevice, st));
-            FTCF_HIP_CHECK(hipMemcpyAsync(d_seed + si, &r.seed, 8, hipMemcpyHostToDevice, st));
-            FTCF_HIP_CHECK(hipMemcpyAsync(d_draws + si, &one, 8, hipMemcpyHostToDevice, st));  // draw 0 went to the first token
-            FTCF_HIP_CHECK(hipMemcpyAsync(d_cum + si, &zf, 4, hipMemcpyHostToDevice, st));
-            FTCF_HIP_CHECK(hipMemcpyAsync(d_fin + si, &zero8, 1, hipMemcpyHostToDevice, st));
-            FTCF_HIP_CHECK(hipStreamSynchronize(st));  // the host temporaries above die here
+            upload_slot_state(si, s, 1, 0.f, st);
             ev.push_back(Event{r.id, first, done, first_lp[i]});  // (the token callback fires when the admission has succeeded: step())
             ev.back().top_ids.assign(first_top_ids.begin() + (size_t)i * want_top, first_top_ids.begin() + (size_t)(i + 1) * want_top);
             ev.back().top_lp.assign(first_top_lp.begin() + (size_t)i * want_top, first_top_lp.begin() + (size_t)(i + 1) * want_top);
@@ -936,6 +1070,13 @@ struct ftcf_batcher : BatcherSched {
         const int              tp = e->cfg.tensor_para_size;
         const bool             tp1 = tp == 1;  // (tensor parallel: the layer ends with residual + all-reduce, GptNeoXDecoder.cc:357-359)
         e->stats.decode_path = use_rows ? 3 : 2;  // (ftcf_gptneox_get_stats of the borrowed engine: which layers the last decode step ran)
+        if (overcommit) {
+            grow_before_decode(st);  // (may swap requests out; throws "swap space exhausted" before anything of the step is enqueued)
+            if (!any_active()) {
+                return;  // (the only running request swapped itself out: beam budgets hold the pool)
+            }
+            refresh_host_flags();
+        }
         hipLaunchKernelGGL(k_batcher_embed, dim3(B), dim3(256), 0, st, x, e->wte, d_tok, H);
         if ((gemm_steps++ & 0x3ffff) == 0 && smallm_ws) {  // the tag space of the burst GEMMs wraps: start it clean
             FTCF_HIP_CHECK(hipMemsetAsync(smallm_ws, 0, smallm_partial + gemm_smallm_ticket_bytes(), st));
@@ -1242,6 +1383,11 @@ struct ftcf_batcher : BatcherSched {
         }
         // then what plan_admission() finds room for: a beam request or a prefix hit alone, else the queue's head requests as one
         // ragged batch -- or, with slots running and a long prompt among them, one after the other
+        // overcommit: swapped-out requests resume first, oldest first, each in the lowest free slot (no event: the slot decodes
+        // with the next step); while one is left plan_admission() admits nobody
+        for (int si; (si = plan_resume()) >= 0;) {
+            resume(si, [this](int s2, const Swapped& w, const std::vector<int>& pages) { swap_in_dev(s2, w, pages); });
+        }
         Admission a = plan_admission(any);
         if (a.kind != Kind::none) {
             do {
@@ -1272,6 +1418,50 @@ extern "C" int ftcf_batcher_create_ex(ftcf_gptneox_t engine, int max_batch, int 
         auto b = std::make_unique<ftcf_batcher>();
         b->init(engine, max_batch, page_tokens, num_pages, max_seq_len, prefix_cache != 0);
         *out = b.release();
+    });
+}
+extern "C" int ftcf_batcher_create_opts(ftcf_gptneox_t engine, const ftcf_batcher_options* options, ftcf_batcher_t* out)
+{
+    return guarded([&] {
+        FTCF_CHECK_ARG(engine && options && out, "NULL argument");
+        FTCF_CHECK_ARG(options->struct_size == (int)sizeof(ftcf_batcher_options), "struct_size is not sizeof(ftcf_batcher_options)");
+        require_device();
+        auto b = std::make_unique<ftcf_batcher>();
+        b->init(engine, options->max_batch, options->page_tokens, options->num_pages, options->max_seq_len, options->prefix_cache != 0,
+                options->overcommit != 0, options->swap_pages, options->swap_stage_bytes);
+        *out = b.release();
+    });
+}
+extern "C" int ftcf_batcher_preempt_stats(ftcf_batcher_t b, int* enabled, int* swapped_requests, int* swap_pages_used,
+                                          int* swap_pages_total, long* preemptions, long* resumes, long* pages_out, long* pages_in)
+{
+    return guarded([&] {
+        require_device();  // (no batcher exists without one)
+        FTCF_CHECK_ARG(b, "NULL argument");
+        if (enabled) {
+            *enabled = b->overcommit ? 1 : 0;
+        }
+        if (swapped_requests) {
+            *swapped_requests = (int)b->swapped.size();
+        }
+        if (swap_pages_used) {
+            *swap_pages_used = b->swap_total - (int)b->host_free.size();
+        }
+        if (swap_pages_total) {
+            *swap_pages_total = b->swap_total;
+        }
+        if (preemptions) {
+            *preemptions = b->pe_preemptions;
+        }
+        if (resumes) {
+            *resumes = b->pe_resumes;
+        }
+        if (pages_out) {
+            *pages_out = b->pe_pages_out;
+        }
+        if (pages_in) {
+            *pages_in = b->pe_pages_in;
+        }
     });
 }
 extern "C" int ftcf_batcher_prefix_stats(ftcf_batcher_t b, int* enabled, int* cached_pages, int* evictable_pages, long* lookups,
@@ -1485,7 +1675,7 @@ extern "C" int ftcf_batcher_status(ftcf_batcher_t b, int* waiting, int* running,
             run += s.active ? 1 : 0;
         }
         if (waiting) {
-            *waiting = (int)b->waiting.size();
+            *waiting = (int)(b->waiting.size() + b->swapped.size());  // (a swapped-out request waits for a slot and pages)
         }
         if (running) {
             *running = run + (b->outbox.empty() ? 0 : 1);  // (events still to be fetched keep the batcher "busy")
@@ -1506,6 +1696,9 @@ extern "C" int ftcf_batcher_cancel(ftcf_batcher_t b, long request_id, int* found
                 hit = 1;
                 break;
             }
+        }
+        if (!hit && b->drop_swapped(request_id)) {  // a swapped-out request: its host pages return
+            hit = 1;
         }
         for (int si = 0; si < b->max_batch && !hit; si++) {
             ftcf_batcher::Slot& s = b->slots[si];

@@ -1,6 +1,7 @@
 // What the continuous batcher (batcher.hip) decides on the host: the request queue, the slots' host
 // fields, page accounting and the admission policy.  Plain C++ (no HIP): tools/check_batcher_sched.cc drives it with a fake
 // prompt phase that fails at seeded points and checks the page accounting, the queue order and the rollbacks.
+// tools/check_batcher_preempt.cc does the same for the overcommit policy (pages on demand, preemption by swap, resume).
 //
 // ftcf_batcher derives from BatcherSched and adds the device side: buffers, launches and the mirrors of this state on the
 // device (d_fin, d_isbeam, page tables).  Where an operation has a device half the name here is the host half's.
@@ -70,10 +71,25 @@ struct BatcherSched {
         LogitOptions          lopt;
         std::vector<unsigned> mask;
         bool                  lopt_dirty = false, mask_dirty = false;
+        // the request's sampling parameters (the device holds them per slot; a swapped-out request takes them to its next slot)
+        int      top_k = 0;
+        float    top_p = 0.f, temperature = 1.f;
+        uint64_t seed = 0;
         bool processed() const
         {
             return lopt.any() || !mask.empty();
         }
+    };
+    // A preempted request (overcommit): its slot's fields without the pages, the host pages that hold its K/V (in the order of
+    // its page list), the host's view of its top-k and temperature, and what only the device knew: draw counter, cumulative
+    // log-probability.
+    struct Swapped {
+        Slot             s;
+        std::vector<int> host;
+        int              slot_topk = 1;
+        float            slot_temp = 1.f;
+        uint64_t         draws = 0;
+        float            cum = 0.f;
     };
     // Beam search inside the batcher (round 4; the reference's serving layer runs beam requests through the same decoder:
     // triton_backend/gptneox/GptNeoXTritonModelInstance.cc).  A request of beam width K lives in K CONSECUTIVE slots -- its
@@ -132,6 +148,27 @@ struct BatcherSched {
     bool               host_any_temperature = false, host_any_repetition = false;
     std::vector<int>   slot_topk;
     std::vector<float> slot_temp;
+    // Overcommit (ftcf_batcher_create_opts; off: none of this is touched).  An ordinary request takes the pages
+    // its prompt needs and one more each time its sequence crosses a page boundary (grow_slots); when the pool cannot give
+    // one, the latest arrival among the running ordinary slots is swapped out to host pages and resumes -- before anybody is
+    // admitted -- when a slot and pages are free again.  `swapped` is in request-id order; host_free: the host pages nobody holds;
+    // inflight_reserve: pages a beam admission in flight was promised and has not taken yet (its group opens after the prompt
+    // phase, and the decode steps between its chunks must leave them alone).
+    bool                overcommit = false;
+    int                 swap_total = 0, inflight_reserve = 0;
+    std::vector<int>    host_free;
+    std::deque<Swapped> swapped;
+    long                pe_preemptions = 0, pe_resumes = 0, pe_pages_out = 0, pe_pages_in = 0;
+
+    void init_overcommit(int swap_pages)
+    {
+        overcommit = true;
+        swap_total = swap_pages > 0 ? swap_pages : num_pages;
+        host_free.resize(swap_total);
+        for (int i = 0; i < swap_total; i++) {
+            host_free[i] = swap_total - 1 - i;  // (taken from the back: ascending, so that a victim's host pages are mostly one run)
+        }
+    }
 
     void init_sched(int mb, int page_tokens, int pages, int max_seq_len, int vocab_size, bool prefix_cache)
     {
@@ -243,6 +280,153 @@ struct BatcherSched {
         for (int pg; (pg = pindex.evict_one(page_ref)) >= 0;) {
             drop_page(pg);
         }
+    }
+
+    // ---- overcommit: pages on demand, preemption by swap -------------------------------------------------------------------
+    // the pages an ordinary request takes at admission: all it can ever need, or (overcommit) its prompt's and the first token's
+    int admission_pages(const Request& r) const
+    {
+        return overcommit ? ((int)r.prompt.size() + 1 + P - 1) / P : pages_needed((int)r.prompt.size(), r.max_new);
+    }
+    int running_ordinary() const
+    {
+        int n = 0;
+        for (const Slot& s : slots) {
+            n += (s.active && s.group < 0) ? 1 : 0;
+        }
+        return n;
+    }
+    // what an ordinary sequence may take now: not what running groups or a beam admission in flight were promised
+    int pages_grantable() const
+    {
+        return pages_available() - inflight_reserve;
+    }
+    // the victim of a preemption: the running ordinary slot of the largest request id (the latest arrival) whose pages the swap
+    // space can take; -1: none.  Beams and the slots of an admission in flight (not active yet) are never victims.
+    int pick_victim() const
+    {
+        int v = -1;
+        for (int si = 0; si < max_batch; si++) {
+            const Slot& s = slots[si];
+            if (s.active && s.group < 0 && s.pages.size() <= host_free.size() && (v < 0 || s.id > slots[v].id)) {
+                v = si;
+            }
+        }
+        return v;
+    }
+    // the slot's request leaves for the swap space.  swap_out(si, pages, host_pages, draws, cum) is the device half: copies the
+    // pages out, reads the draw counter and the cumulative log-probability back, tells the device the slot is finished.
+    template<typename SwapOut>
+    void preempt(const int si, SwapOut& swap_out)
+    {
+        Slot&   s = slots[si];
+        Swapped w;
+        w.host.assign(host_free.end() - s.pages.size(), host_free.end());
+        std::reverse(w.host.begin(), w.host.end());
+        swap_out(si, s.pages, w.host, w.draws, w.cum);  // (throws: nothing has changed)
+        host_free.resize(host_free.size() - s.pages.size());
+        pe_preemptions++;
+        pe_pages_out += (long)s.pages.size();
+        release(s);
+        w.slot_topk = slot_topk[si];
+        w.slot_temp = slot_temp[si];
+        w.s         = s;
+        auto at = std::find_if(swapped.begin(), swapped.end(), [&](const Swapped& x) { return x.s.id > w.s.id; });
+        swapped.insert(at, std::move(w));
+    }
+    // Before a decode step enqueues anything: every running ordinary slot whose next token starts a page takes that page, in slot
+    // order; when the pool has none (cached pages nobody holds are evicted first, take_page) victims are swapped out until it
+    // has -- the slot itself when it is the latest arrival.  on_grow(si) is the device half of ONE growth -- the slot's page
+    // table row gets its new last entry -- and runs the moment the slot has grown: when a later slot throws, the device already
+    // knows every page the host has handed out (an on_grow that throws gives its page back first).  Returns how many slots grew.
+    // Throws -2 when no victim fits the swap space: whatever grew or left before stays so, on both sides; nothing is half done.
+    template<typename SwapOut, typename OnGrow>
+    int grow_slots(SwapOut swap_out, OnGrow on_grow)
+    {
+        int grown = 0;
+        if (!overcommit) {
+            return grown;
+        }
+        for (int si = 0; si < max_batch; si++) {
+            Slot& s = slots[si];
+            if (!s.active || s.group >= 0 || s.len < (int)s.pages.size() * P) {
+                continue;
+            }
+            while (s.active && pages_grantable() < 1) {
+                const int v = pick_victim();
+                if (v < 0) {
+                    throw Error(-2, "batcher: swap space exhausted (no running request fits the free host pages; cancel a request or "
+                                    "create the batcher with more swap_pages)");
+                }
+                preempt(v, swap_out);
+            }
+            if (s.active) {
+                s.pages.push_back(take_page());
+                try {
+                    on_grow(si);
+                }
+                catch (...) {
+                    drop_page(s.pages.back());
+                    s.pages.pop_back();
+                    throw;
+                }
+                grown++;
+            }
+        }
+        return grown;
+    }
+    // the slot the head of `swapped` may resume in now (the lowest free one), or -1: no request is swapped out, no slot is free
+    // or the pool lacks its pages plus the watermark of one page per running ordinary slot (waived when none runs)
+    int plan_resume() const
+    {
+        if (swapped.empty()) {
+            return -1;
+        }
+        int si = 0;
+        while (si < max_batch && slots[si].active) {
+            si++;
+        }
+        const int need = (swapped.front().s.len + 1 + P - 1) / P;
+        return (si < max_batch && pages_grantable() >= need + running_ordinary()) ? si : -1;
+    }
+    // ... and does: fresh private pages, the slot's fields as they were.  swap_in(si, swapped_request, pages) is the device half:
+    // the host pages into the first pages of the new list, the slot's device state.  No event: nothing was generated.
+    template<typename SwapIn>
+    void resume(const int si, SwapIn swap_in)
+    {
+        Swapped& w = swapped.front();
+        Slot&    s = slots[si];
+        s          = w.s;
+        for (int k = 0, need = (s.len + 1 + P - 1) / P; k < need; k++) {
+            s.pages.push_back(take_page());
+        }
+        s.active     = true;
+        s.lopt_dirty = s.mask_dirty = true;
+        slot_topk[si] = w.slot_topk;
+        slot_temp[si] = w.slot_temp;
+        try {
+            swap_in(si, w, s.pages);
+        }
+        catch (...) {
+            release(s);
+            throw;
+        }
+        host_free.insert(host_free.end(), w.host.rbegin(), w.host.rend());
+        pe_resumes++;
+        pe_pages_in += (long)w.host.size();
+        swapped.pop_front();
+    }
+    // a swapped-out request is dropped (cancel): its host pages return; false: no such request
+    bool drop_swapped(const long id)
+    {
+        for (auto it = swapped.begin(); it != swapped.end(); ++it) {
+            if (it->s.id == id) {
+                host_free.insert(host_free.end(), it->host.rbegin(), it->host.rend());
+                swapped.erase(it);
+                return true;
+            }
+        }
+        return false;
     }
 
     // ---- stop words --------------------------------------------------------------------------------------------------
@@ -396,6 +580,12 @@ struct BatcherSched {
                 return;
             }
         }
+        for (Swapped& w : swapped) {  // (a swapped-out request: its slot's row follows when it resumes)
+            if (w.s.id == id) {
+                w.s.mask = std::move(m);
+                return;
+            }
+        }
         FTCF_CHECK_ARG(false, "token mask: no waiting or running request has this id");
     }
     // a beam-search request (GptNeoXOp.forward with beam_width > 1: OnlineBeamSearchLayer): K consecutive slots; one event when
@@ -434,10 +624,13 @@ struct BatcherSched {
     Admission plan_admission(const bool any)
     {
         Admission a;
-        if (waiting.empty()) {
+        if (waiting.empty() || !swapped.empty()) {  // (overcommit: a swapped-out request resumes before anybody is admitted)
             return a;
         }
         int pages_left = pages_available();
+        // overcommit: an ordinary admission leaves a watermark of one page per running ordinary slot (the ones this plan has
+        // admitted so far included), so that it cannot itself cause a preemption within the next P steps; none runs: waived
+        const int running = overcommit ? running_ordinary() : 0;
         if (waiting.front().beam_width > 1) {
             const Request& r = waiting.front();
             const int      K = r.beam_width, need = K * pages_needed((int)r.prompt.size(), r.max_new);
@@ -460,6 +653,8 @@ struct BatcherSched {
             // slots are running and the prompt is long: its prompt phase in chunks, a decode step of the running slots after every
             // chunk (the events of those steps are final whatever happens to the admission)
             a.install_hook = any_active() && prefill_chunk > 0 && (int)r.prompt.size() > prefill_chunk;
+            // (overcommit: the hook's decode steps take pages too, and the group opens only after the prompt phase)
+            inflight_reserve = overcommit ? need : 0;
             take_head(a);
             return a;
         }
@@ -471,7 +666,8 @@ struct BatcherSched {
             if (r.beam_width > 1) {
                 break;  // (admitted alone, by the next iteration)
             }
-            int need = pages_needed((int)r.prompt.size(), r.max_new);
+            int       need      = admission_pages(r);
+            const int watermark = overcommit ? running + (int)a.slots.size() : 0;
             if (prefix_on) {
                 // at most floor((S - 1) / P) blocks: the last prompt token is always computed (its logits give the first token)
                 // and decode never writes into a cached page
@@ -489,7 +685,7 @@ struct BatcherSched {
                         page_ref[pg]--;
                     }
                     need -= (int)h.size();
-                    if (avail < need) {
+                    if (avail < need + watermark) {
                         break;
                     }
                     // the tail's prompt phase from the hit offset, in chunks with decode steps between them when it is long
@@ -500,7 +696,7 @@ struct BatcherSched {
                     return a;
                 }
             }
-            if (pages_left < need) {
+            if (pages_left < need + watermark) {
                 break;  // FIFO: nobody overtakes the head of the queue
             }
             pages_left -= need;
@@ -520,10 +716,20 @@ struct BatcherSched {
         return a;
     }
     // after a chunked_one admission has succeeded: on to the next of its requests (false: that was the last)
-    bool next_chunked(Admission& a) const
+    bool next_chunked(Admission& a)
     {
         a.slots.erase(a.slots.begin());
         a.requests.erase(a.requests.begin());
+        // overcommit: the decode steps inside the admission took pages and may have swapped somebody out; when the next request
+        // no longer fits, or somebody waits to resume, the rest of the plan returns to the queue's head
+        if (overcommit && !a.slots.empty()
+            && (!swapped.empty() || pages_grantable() < admission_pages(a.requests[0]) + running_ordinary())) {
+            for (std::size_t i = a.requests.size(); i-- > 0;) {
+                waiting.push_front(std::move(a.requests[i]));
+            }
+            a.requests.clear();
+            a.slots.clear();
+        }
         a.install_hook = any_active();
         return !a.slots.empty();
     }
@@ -533,6 +739,7 @@ struct BatcherSched {
     template<typename Retire, typename ReleaseGroup>
     void rollback(Admission& a, Retire retire, ReleaseGroup release_group)
     {
+        inflight_reserve = 0;
         if (a.kind == Kind::beam) {
             release_group(a.slots[0]);
         }
@@ -581,7 +788,7 @@ struct BatcherSched {
             }
             pindex.touch(r.prompt.data(), (int)hit->size());
         }
-        for (int k = (int)s.pages.size(), need = pages_needed((int)r.prompt.size(), r.max_new); k < need; k++) {
+        for (int k = (int)s.pages.size(), need = admission_pages(r); k < need; k++) {
             s.pages.push_back(take_page());
         }
     }
@@ -596,6 +803,10 @@ struct BatcherSched {
         s.lopt               = r.lopt;
         s.mask               = r.mask;
         s.lopt_dirty = s.mask_dirty = true;
+        s.top_k              = r.top_k;
+        s.top_p              = r.top_p;
+        s.temperature        = r.temperature;
+        s.seed               = r.seed;
         s.active             = true;
         s.id                 = r.id;
         s.len                = (int)r.prompt.size();
@@ -617,6 +828,7 @@ struct BatcherSched {
     BeamGroup& open_group(const int si, const Request& r)
     {
         const int n = (int)r.prompt.size();
+        inflight_reserve = 0;  // (from here on the group's budget is the promise)
         BeamGroup g;
         g.id        = r.id;
         g.si        = si;

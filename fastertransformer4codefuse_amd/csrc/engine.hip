@@ -590,6 +590,28 @@ extern "C" int ftcf_gather_pages_to_kv(void* k_cache, void* v_cache, const void*
                                   page_tokens, pool_layer_elems, (hipStream_t)stream, dst_layer_elems);
     });
 }
+extern "C" int ftcf_pages_pack(void* staging, const void* k_pool, const void* v_pool, const int* pages, int n, int L, int nh, int dh,
+                               int page_tokens, size_t pool_layer_elems, void* stream)
+{
+    return guarded([&] {
+        require_device();
+        FTCF_CHECK_ARG(staging && k_pool && v_pool && pages, "NULL tensor");
+        FTCF_CHECK_ARG(n >= 0 && L >= 1 && nh >= 1 && page_tokens >= 1 && dh >= 8 && dh % 8 == 0, "pages_pack: bad geometry");
+        launch_pages_pack((f16*)staging, (const f16*)k_pool, (const f16*)v_pool, pages, n, L, (size_t)nh * page_tokens * dh,
+                          pool_layer_elems, (hipStream_t)stream);
+    });
+}
+extern "C" int ftcf_pages_unpack(const void* staging, void* k_pool, void* v_pool, const int* pages, int n, int L, int nh, int dh,
+                                 int page_tokens, size_t pool_layer_elems, void* stream)
+{
+    return guarded([&] {
+        require_device();
+        FTCF_CHECK_ARG(staging && k_pool && v_pool && pages, "NULL tensor");
+        FTCF_CHECK_ARG(n >= 0 && L >= 1 && nh >= 1 && page_tokens >= 1 && dh >= 8 && dh % 8 == 0, "pages_unpack: bad geometry");
+        launch_pages_unpack((const f16*)staging, (f16*)k_pool, (f16*)v_pool, pages, n, L, (size_t)nh * page_tokens * dh,
+                            pool_layer_elems, (hipStream_t)stream);
+    });
+}
 
 template<typename T>
 static std::vector<T> broadcast_arg(const T* p, int n, int B, T dflt, const char* name)

@@ -191,6 +191,12 @@ void   launch_scatter_kv_to_pages(const f16* kc, const f16* vc, f16* kpool, f16*
 // the inverse (the batcher's prefix cache): tokens [0, T) (T a multiple of P) of a sequence's pages -> a row of the engine cache
 void   launch_gather_pages_to_kv(f16* kc, f16* vc, const f16* kpool, const f16* vpool, const int* pages, int L, int nh, int dh,
                                  int s_max, int T, int P, size_t pool_layer_elems, hipStream_t s, size_t dst_layer_elems = 0);
+// whole pages of every layer of both pools <-> a contiguous staging buffer [n][2 (K, V)][L][page_elems] (the batcher's swap
+// space: preemption under overcommit); page_elems = nh * P * dh, a multiple of 8.  Bit-exact copies, exact inverses.
+void   launch_pages_pack(f16* staging, const f16* kpool, const f16* vpool, const int* pages, int n, int L, size_t page_elems,
+                         size_t pool_layer_elems, hipStream_t s);
+void   launch_pages_unpack(const f16* staging, f16* kpool, f16* vpool, const int* pages, int n, int L, size_t page_elems,
+                           size_t pool_layer_elems, hipStream_t s);
 
 // ---- fused attention + FFN1 weight stream : kernels_fused.hip ----
 void launch_mmha_ln_gemv(const MmhaParams& ap, const LnGemvParams& gp, bool int8, int M, hipStream_t s);

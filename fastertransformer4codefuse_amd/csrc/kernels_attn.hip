@@ -852,4 +852,61 @@ void launch_gather_pages_to_kv(f16* kc, f16* vc, const f16* kpool, const f16* vp
     FTCF_HIP_CHECK(hipGetLastError());
 }
 
+// The batcher's swap space (preemption under overcommit): n whole pages of a page list, every layer of both pools
+// [L][page][nh][P][dh], <-> a contiguous staging buffer [n][2 (K, V)][L][page_elems] that one linear copy moves to or from
+// pinned host memory.  One 16-byte piece per thread and iteration, the staging side linear in the piece index (upp: pieces per
+// page and layer); a bit-exact copy.
+// (32-bit index arithmetic: the launchers keep the piece count below 2^31 -- a staging buffer of 32 GiB -- and gfx950 emulates 64-bit division)
+__global__ void k_pages_pack(f16* __restrict__ staging, const f16* __restrict__ kpool, const f16* __restrict__ vpool,
+                             const int* __restrict__ pages, unsigned L, unsigned upp, size_t pool_layer_elems, unsigned total)
+{
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        const unsigned u = i % upp, r = i / upp, l = r % L, jp = r / L;  // jp = page of the list * 2 + pool
+        const f16*     pool = ((jp & 1) ? vpool : kpool) + (size_t)l * pool_layer_elems + ((size_t)pages[jp >> 1] * upp + u) * 8;
+        *reinterpret_cast<u32x4*>(staging + (size_t)i * 8) = *reinterpret_cast<const u32x4*>(pool);
+    }
+}
+__global__ void k_pages_unpack(const f16* __restrict__ staging, f16* __restrict__ kpool, f16* __restrict__ vpool,
+                               const int* __restrict__ pages, unsigned L, unsigned upp, size_t pool_layer_elems, unsigned total)
+{
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        const unsigned u = i % upp, r = i / upp, l = r % L, jp = r / L;
+        f16*           pool = ((jp & 1) ? vpool : kpool) + (size_t)l * pool_layer_elems + ((size_t)pages[jp >> 1] * upp + u) * 8;
+        *reinterpret_cast<u32x4*>(pool) = *reinterpret_cast<const u32x4*>(staging + (size_t)i * 8);
+    }
+}
+static unsigned pages_move_grid(size_t total)
+{
+    // grid-stride over the pieces, capped as k_gather_pages_to_kv caps its grid: at most 16 workgroups of 256 threads per CU
+    return (unsigned)std::min<size_t>((total + 255) / 256, 256 * 16);
+}
+void launch_pages_pack(f16* staging, const f16* kpool, const f16* vpool, const int* pages, int n, int L, size_t page_elems,
+                       size_t pool_layer_elems, hipStream_t s)
+{
+    FTCF_CHECK_ARG(n >= 0 && L >= 1 && page_elems >= 8 && page_elems % 8 == 0 && pool_layer_elems % page_elems == 0,
+                   "pages_pack: bad geometry");
+    const size_t total = (size_t)n * 2 * L * (page_elems / 8);
+    if (total == 0) {
+        return;
+    }
+    FTCF_CHECK_ARG(total < ((size_t)1 << 31), "pages_pack: more than 2^31 16-byte pieces in one launch");
+    hipLaunchKernelGGL(k_pages_pack, dim3(pages_move_grid(total)), dim3(256), 0, s, staging, kpool, vpool, pages, (unsigned)L,
+                       (unsigned)(page_elems / 8), pool_layer_elems, (unsigned)total);
+    FTCF_HIP_CHECK(hipGetLastError());
+}
+void launch_pages_unpack(const f16* staging, f16* kpool, f16* vpool, const int* pages, int n, int L, size_t page_elems,
+                         size_t pool_layer_elems, hipStream_t s)
+{
+    FTCF_CHECK_ARG(n >= 0 && L >= 1 && page_elems >= 8 && page_elems % 8 == 0 && pool_layer_elems % page_elems == 0,
+                   "pages_unpack: bad geometry");
+    const size_t total = (size_t)n * 2 * L * (page_elems / 8);
+    if (total == 0) {
+        return;
+    }
+    FTCF_CHECK_ARG(total < ((size_t)1 << 31), "pages_unpack: more than 2^31 16-byte pieces in one launch");
+    hipLaunchKernelGGL(k_pages_unpack, dim3(pages_move_grid(total)), dim3(256), 0, s, staging, kpool, vpool, pages, (unsigned)L,
+                       (unsigned)(page_elems / 8), pool_layer_elems, (unsigned)total);
+    FTCF_HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace ftcf

@@ -245,6 +245,15 @@ int ftcf_scatter_kv_to_pages(const void* k_cache, const void* v_cache, void* k_p
 int ftcf_gather_pages_to_kv(void* k_cache, void* v_cache, const void* k_pool, const void* v_pool, const int* pages, int L, int nh,
                             int dh, int s_max, int T, int page_tokens, size_t pool_layer_elems, size_t dst_layer_elems,
                             void* stream);
+/* The batcher's swap space (ftcf_batcher_create_opts with overcommit): pages pages[0 .. n) of every layer of both pools
+ * (layouts and pool_layer_elems as in ftcf_scatter_kv_to_pages) -> a contiguous DEVICE staging buffer
+ * [n][2 (K, V)][L][nh * page_tokens * dh] of fp16; pages: DEVICE array of page ids, each < pool_layer_elems / (nh * page_tokens * dh).
+ * A bit-exact copy; nothing beyond n pages of the staging buffer is written. */
+int ftcf_pages_pack(void* staging, const void* k_pool, const void* v_pool, const int* pages, int n, int L, int nh, int dh,
+                    int page_tokens, size_t pool_layer_elems, void* stream);
+/* The exact inverse: the staging buffer -> the pages of (another) page list; no other page of the pools is written. */
+int ftcf_pages_unpack(const void* staging, void* k_pool, void* v_pool, const int* pages, int n, int L, int nh, int dh,
+                      int page_tokens, size_t pool_layer_elems, void* stream);
 /* ONE step of the dynamic-decode layer (DynamicDecodeLayer.cc:192-497 with beam_width 1: optional-token mask, temperature,
  * repetition penalty, min-length mask, end mask, top-k / top-p sampling, stop words, length criterion) on the caller's logits and
  * state -- the launch sequence the engine and the continuous batcher run per token, with the same routing of the runtime
@@ -592,6 +601,38 @@ int ftcf_batcher_create(ftcf_gptneox_t engine, int max_batch, int page_tokens, i
  * hidden sizes without the dual LayerNorm. */
 int ftcf_batcher_create_ex(ftcf_gptneox_t engine, int max_batch, int page_tokens, int num_pages, int max_seq_len, int prefix_cache,
                            ftcf_batcher_t* out);
+/* The general form.  struct_size must be sizeof(ftcf_batcher_options); max_batch .. prefix_cache as above.
+ * OVERCOMMIT (overcommit = 1; 0 is exactly ftcf_batcher_create_ex): an ordinary request no longer reserves the pages of
+ * prompt + max_new_tokens at admission.  It takes ceil((prompt_len + 1) / page_tokens) pages (less its prefix hit) and is
+ * admitted when the pool has them plus one page per running ordinary request (waived when none runs); a running request takes
+ * one page more each time its sequence crosses a page boundary, before the decode step.  When the pool cannot give that page
+ * (cached prefix pages nobody uses are evicted first) the running ordinary request that arrived LAST is swapped out: its K/V
+ * pages are copied to pinned host memory, bit for bit, its slot is freed.  Swapped-out requests resume, oldest first and before
+ * anybody waiting is admitted, when a slot and their pages (plus the same watermark) are free -- in any slot, on fresh pages,
+ * with their sampling state (draw counter, cumulative log-probability, history, logit processors, token mask) as it was: every
+ * request still produces exactly the tokens it produces alone.  A resume produces no event.  A swapped-out request counts as
+ * `waiting` in ftcf_batcher_status; ftcf_batcher_cancel (its host pages return) and ftcf_batcher_set_token_mask find it by id.
+ * Beam requests keep reserving
+ * their whole budget and are never swapped.  swap_pages: host pages of 2 * num_layer * page bytes (0: num_pages);
+ * max_batch * ceil(max_seq_len / page_tokens) can never fill.  When no victim fits the free host pages ftcf_batcher_step
+ * fails with -2 "swap space exhausted" before the step enqueues anything; the batcher stays consistent, cancel a
+ * request and call again.  swap_stage_bytes: the device staging buffer the copies go through (0: 64 MiB).  It is
+ * rounded to whole pages of all layers: at least one, and at most ceil(max_seq_len / page_tokens) -- one request's pages, more
+ * is never in flight -- so a larger value allocates no more than that.  A request must still fit the pool alone at full
+ * length.  Refused for tensor_para_size > 1. */
+typedef struct {
+    int    struct_size;
+    int    max_batch, page_tokens, num_pages, max_seq_len;
+    int    prefix_cache;
+    int    overcommit;
+    int    swap_pages;
+    size_t swap_stage_bytes;
+} ftcf_batcher_options;
+int ftcf_batcher_create_opts(ftcf_gptneox_t engine, const ftcf_batcher_options* options, ftcf_batcher_t* out);
+/* Overcommit counters (any pointer may be NULL): enabled, requests swapped out now, host pages in use and in all, then since
+ * creation: preemptions, resumes, pages copied out and in.  Without overcommit: enabled = 0 and zeros. */
+int ftcf_batcher_preempt_stats(ftcf_batcher_t b, int* enabled, int* swapped_requests, int* swap_pages_used, int* swap_pages_total,
+                               long* preemptions, long* resumes, long* pages_out, long* pages_in);
 /* Prefix-cache counters (any pointer may be NULL): enabled, cached pages, cached pages eviction could free now, admissions
  * looked up, their prompt tokens, the tokens served from the cache, the prompt tokens actually computed, pages evicted to make
  * room.  A batcher without the cache reports enabled = 0 and zeros. */
