@@ -170,6 +170,7 @@ struct ftcf_batcher : BatcherSched {
     size_t           page_all_elems = 0;
     int*             d_swap_list = nullptr;
     std::vector<int> swap_list_host, grow_host;
+    std::vector<int> pt_host;  // [max_batch][max_pages]: where page-table rows are staged (stage_page_row)
     // Logit processors (kernels_logits.hip): the options and masks of `rows` rows on the device with their host mirrors -- one set
     // indexed by slot for the decode steps, one by the rows of an admission's ragged batch for its first tokens.  The host
     // mirrors are members: an asynchronous copy reads them until the step's synchronisation, and nobody changes them before it.
@@ -363,6 +364,7 @@ struct ftcf_batcher : BatcherSched {
         // schedulers take identical decisions, the decode step's collectives are the engine's): the LM head's [TP][B][V/TP] slices
         gather = e->cfg.tensor_para_size > 1 ? dmalloc<float>(B * V) : nullptr;
         d_pt = dmalloc<int>(B * max_pages);
+        pt_host.assign(B * max_pages, 0);
         d_len = dmalloc<int>(B);
         d_tok = dmalloc<int>(B);
         d_topk = dmalloc<int>(B);
@@ -410,22 +412,7 @@ struct ftcf_batcher : BatcherSched {
         samp_ws = dmalloc<char>(sampling_workspace_bytes(max_batch, V), false);
         init_logit_rows(lp_slots, max_batch);
         init_logit_rows(lp_adm, max_batch);
-        {
-            const int rows_env = getenv("FTCF_BATCHER_ROWS") ? atoi(getenv("FTCF_BATCHER_ROWS")) : 1;
-            if (rows_env && e->rows && e->cfg.tensor_para_size == 1 && !e->fp32 && max_batch <= 16 && e->cfg.use_gptj_residual && L <= 255
-                && (e->dh == 64 || e->dh == 128) && P % rows_paged_block(e->dh) == 0) {
-                rplan = rows_plan(max_batch, H, hl, il, e->nhl, e->dh, 1, e->int8, e->num_cu, 0);
-                if (rplan.ok && rows_resident(rplan, e->int8, e->dh, e->num_cu, true)) {
-                    rows_ws   = dmalloc<char>(rows_workspace_bytes(rplan, max_batch, H, hl, il, e->nhl, e->dh));
-                    d_rlayers = dmalloc<PersistLayer>(L);
-                    d_rot     = dmalloc<float>(B * std::max(1, e->cfg.rotary_embedding_dim));
-                    d_rstep   = dmalloc<int>(1);
-                    const std::vector<PersistLayer> pl = persist_layer_table(e->layers, kpool, vpool, pool_layer_elems);
-                    FTCF_HIP_CHECK(hipMemcpy(d_rlayers, pl.data(), sizeof(PersistLayer) * L, hipMemcpyHostToDevice));
-                    use_rows = true;
-                }
-            }
-        }
+        init_rows();
         // (tensor parallel: up to 32 slots as two micro-batches of <= 16 rows with their own split-K regions -- the decode overlap)
         if (max_batch > 4 && (max_batch <= e->SMALLM_MAX_ROWS || (e->cfg.tensor_para_size > 1 && max_batch <= 32))) {
             const bool i8 = e->int8;
@@ -442,18 +429,42 @@ struct ftcf_batcher : BatcherSched {
         std::vector<uint8_t> fin(max_batch, 1);
         FTCF_HIP_CHECK(hipMemcpy(d_fin, fin.data(), max_batch, hipMemcpyHostToDevice));
         if (overcommit_on) {
-            init_overcommit(swap_pages);
-            page_all_elems = 2 * (size_t)L * e->nhl * P * e->dh;
-            const size_t want = swap_stage_bytes ? swap_stage_bytes : (size_t)64 << 20;
-            // at least one page of all layers; no more than one request's pages (nobody swaps more at a time) and than one launch of
-            // the copy kernels takes (2^31 16-byte pieces)
-            stage_pages = (int)std::min<size_t>(std::max<size_t>(want / (page_all_elems * sizeof(f16)), 1), (size_t)max_pages);
-            stage_pages = (int)std::max<size_t>(std::min<size_t>((size_t)stage_pages, (((size_t)1 << 31) - 1) / (page_all_elems / 8)), 1);
-            swap_stage  = dmalloc<f16>((size_t)stage_pages * page_all_elems, false);
-            d_swap_list = dmalloc<int>(max_pages);
-            grow_host.assign(max_batch, 0);
-            FTCF_HIP_CHECK(hipHostMalloc(&swap_host, (size_t)swap_total * page_all_elems * sizeof(f16), hipHostMallocDefault));
+            init_swap(swap_pages, swap_stage_bytes);
         }
+    }
+    // the rows kernel's plan, workspace and layer table over the pools, where the model, the geometry and FTCF_BATCHER_ROWS allow it
+    void init_rows()
+    {
+        const int H = e->H, hl = e->hl, il = e->il, L = e->L;
+        const int rows_env = getenv("FTCF_BATCHER_ROWS") ? atoi(getenv("FTCF_BATCHER_ROWS")) : 1;
+        if (rows_env && e->rows && e->cfg.tensor_para_size == 1 && !e->fp32 && max_batch <= 16 && e->cfg.use_gptj_residual && L <= 255
+            && (e->dh == 64 || e->dh == 128) && P % rows_paged_block(e->dh) == 0) {
+            rplan = rows_plan(max_batch, H, hl, il, e->nhl, e->dh, 1, e->int8, e->num_cu, 0);
+            if (rplan.ok && rows_resident(rplan, e->int8, e->dh, e->num_cu, true)) {
+                rows_ws   = dmalloc<char>(rows_workspace_bytes(rplan, max_batch, H, hl, il, e->nhl, e->dh));
+                d_rlayers = dmalloc<PersistLayer>(L);
+                d_rot     = dmalloc<float>((size_t)max_batch * std::max(1, e->cfg.rotary_embedding_dim));
+                d_rstep   = dmalloc<int>(1);
+                const std::vector<PersistLayer> pl = persist_layer_table(e->layers, kpool, vpool, pool_layer_elems);
+                FTCF_HIP_CHECK(hipMemcpy(d_rlayers, pl.data(), sizeof(PersistLayer) * L, hipMemcpyHostToDevice));
+                use_rows = true;
+            }
+        }
+    }
+    // overcommit: the host pages and the staging buffer
+    void init_swap(const int swap_pages, const size_t swap_stage_bytes)
+    {
+        init_overcommit(swap_pages);
+        page_all_elems = 2 * (size_t)e->L * e->nhl * P * e->dh;
+        const size_t want = swap_stage_bytes ? swap_stage_bytes : (size_t)64 << 20;
+        // at least one page of all layers; no more than one request's pages (nobody swaps more at a time) and than one launch of
+        // the copy kernels takes (2^31 16-byte pieces)
+        stage_pages = (int)std::min<size_t>(std::max<size_t>(want / (page_all_elems * sizeof(f16)), 1), (size_t)max_pages);
+        stage_pages = (int)std::max<size_t>(std::min<size_t>((size_t)stage_pages, (((size_t)1 << 31) - 1) / (page_all_elems / 8)), 1);
+        swap_stage  = dmalloc<f16>((size_t)stage_pages * page_all_elems, false);
+        d_swap_list = dmalloc<int>(max_pages);
+        grow_host.assign(max_batch, 0);
+        FTCF_HIP_CHECK(hipHostMalloc(&swap_host, (size_t)swap_total * page_all_elems * sizeof(f16), hipHostMallocDefault));
     }
 
     struct Event {
@@ -495,6 +506,29 @@ struct ftcf_batcher : BatcherSched {
         release(slots[si]);
         const uint8_t one8 = 1;
         return device_knows ? hipSuccess : hipMemcpy(d_fin + si, &one8, 1, hipMemcpyHostToDevice);
+    }
+    int* pt_row(const int si) const
+    {
+        return d_pt + (size_t)si * max_pages;
+    }
+    // slot si's region of the beam arrays d_bout / d_bpar / d_bres (a group's [max_len + 2][K] steps start at its leader's)
+    size_t beam_region(const int si) const
+    {
+        return (size_t)si * (max_len + 2);
+    }
+    // `rows` page lists as the page-table rows of slots si, si + 1, ... (unused entries: page 0), ONE copy.  The rows are staged
+    // in pt_host, a member with a row per slot: an asynchronous copy reads it until the caller's next synchronisation, and
+    // every caller synchronises before it returns -- nobody stages a row again while a copy of it is in flight.
+    void upload_page_rows(const int si, const std::vector<int>* lists, const int rows, hipStream_t st, const bool blocking = false)
+    {
+        int* src = pt_host.data() + (size_t)si * max_pages;
+        for (int k = 0; k < rows; k++) {
+            FTCF_CHECK_ARG(si + k < max_batch && (int)lists[k].size() <= max_pages, "batcher: a page list longer than max_pages");
+            std::fill(std::copy(lists[k].begin(), lists[k].end(), src + (size_t)k * max_pages), src + (size_t)(k + 1) * max_pages, 0);
+        }
+        const size_t bytes = (size_t)rows * max_pages * 4;
+        FTCF_HIP_CHECK(blocking ? hipMemcpy(pt_row(si), src, bytes, hipMemcpyHostToDevice)
+                                : hipMemcpyAsync(pt_row(si), src, bytes, hipMemcpyHostToDevice, st));
     }
     // the engine's prompt phase from a token offset, for one forward()
     struct PrefillFrom {
@@ -615,9 +649,7 @@ struct ftcf_batcher : BatcherSched {
             copy_host_pages(w.host, c0, nc, false, st);
             launch_pages_unpack(swap_stage, kpool, vpool, d_swap_list + c0, nc, e->L, page_all_elems / (2 * (size_t)e->L), pool_layer_elems, st);
         }
-        std::vector<int> row(max_pages, 0);
-        std::copy(pages.begin(), pages.end(), row.begin());
-        FTCF_HIP_CHECK(hipMemcpyAsync(d_pt + (size_t)si * max_pages, row.data(), (size_t)max_pages * 4, hipMemcpyHostToDevice, st));
+        upload_page_rows(si, &pages, 1, st);
         upload_slot_state(si, slots[si], w.draws, w.cum, st);  // (host synchronous)
     }
     // before a decode step enqueues anything: the slots whose next token starts a page take it (preempting when the pool has
@@ -636,7 +668,7 @@ struct ftcf_batcher : BatcherSched {
                     FTCF_CHECK_ARG(k >= 0 && k < max_pages && slots[si].pages[k] >= 0 && slots[si].pages[k] < num_pages,
                                    "batcher: a page list outgrew max_pages");
                     grow_host[si] = slots[si].pages[k];  // (a member: read by the copy until the step's synchronisation)
-                    FTCF_HIP_CHECK(hipMemcpyAsync(d_pt + (size_t)si * max_pages + k, &grow_host[si], 4, hipMemcpyHostToDevice, st));
+                    FTCF_HIP_CHECK(hipMemcpyAsync(pt_row(si) + k, &grow_host[si], 4, hipMemcpyHostToDevice, st));
                 });
         }
         catch (...) {
@@ -645,33 +677,49 @@ struct ftcf_batcher : BatcherSched {
         }
     }
 
-    // prompts -> ONE ragged batch through the engine's context path (+ first tokens) -> pages of their slots
-    // hit (one request only): the cached pages of its first prompt blocks (pinned here: the slot's page list owns one reference)
-    // (the first n of rs, into the first n of sis)
-    void admit(const std::vector<int>& sis, const std::vector<Request>& rs, const int n, std::vector<Event>& ev,
-               const std::vector<int>* hit = nullptr)
+    // slot i's top_n {id, log-probability} pairs out of a step's [rows][top_n] arrays
+    static void cut_top(Event& x, const std::vector<int>& ids, const std::vector<float>& lp, const int i, const int top_n)
     {
-        Range        rg("ftcf.batcher.admit");
-        deferred.clear();
-        hipStream_t  st = e->stream;
-        int          S  = 0;
+        x.top_ids.assign(ids.begin() + (size_t)i * top_n, ids.begin() + (size_t)(i + 1) * top_n);
+        x.top_lp.assign(lp.begin() + (size_t)i * top_n, lp.begin() + (size_t)(i + 1) * top_n);
+    }
+
+    // ONE ragged batch of prompts for the engine's context path: the engine's arguments and the host arrays they point into
+    struct AdmitBatch {
+        int                   n = 0, S = 0, hit_tokens = 0, top_n = 0;
+        std::vector<int>      lens, topk;
+        std::vector<float>    topp, temp, rep;
+        std::vector<uint64_t> seed;
+        bool                  any_lp = false;  // a row has logit processors: the stage runs as the engine's logits hook
+        ftcf_forward_args     a{};
+    };
+    // the first n of rs into the first n of sis: their pages, the ragged batch on the device, the engine's arguments, the logit
+    // rows of the first tokens
+    // hit (one request only): the cached pages of its first prompt blocks (pinned here: the slot's page list owns one reference)
+    void build_admission(AdmitBatch& b, const std::vector<int>& sis, const std::vector<Request>& rs, const int n,
+                         const std::vector<int>* hit, hipStream_t st)
+    {
+        int S = 0;
         for (int i = 0; i < n; i++) {
             S = std::max(S, (int)rs[i].prompt.size());
         }
-        std::vector<int>      ids((size_t)n * S, e->cfg.end_id), lens(n), topk(n);
-        std::vector<float>    topp(n), temp(n), rep(n);
-        bool                  any_stop = false;
-        std::vector<int>      sw((size_t)n * 2 * STOP_LW, 0);
-        std::vector<uint64_t> seed(n);
+        b.n          = n;
+        b.S          = S;
+        b.hit_tokens = hit ? (int)hit->size() * P : 0;
+        b.top_n      = want_top;
+        std::vector<int>&      lens = b.lens;
+        std::vector<int>       ids((size_t)n * S, e->cfg.end_id), sw((size_t)n * 2 * STOP_LW, 0);
+        bool                   any_stop = false;
+        lens.resize(n), b.topk.resize(n), b.topp.resize(n), b.temp.resize(n), b.rep.resize(n), b.seed.resize(n);
         for (int i = 0; i < n; i++) {
             const Request& r = rs[i];
             std::copy(r.prompt.begin(), r.prompt.end(), ids.begin() + (size_t)i * S);
-            lens[i] = (int)r.prompt.size();
-            topk[i] = r.top_k;
-            topp[i] = r.top_p;
-            temp[i] = r.temperature;
-            rep[i]  = r.repetition_penalty;
-            seed[i] = r.seed;
+            lens[i]   = (int)r.prompt.size();
+            b.topk[i] = r.top_k;
+            b.topp[i] = r.top_p;
+            b.temp[i] = r.temperature;
+            b.rep[i]  = r.repetition_penalty;
+            b.seed[i] = r.seed;
             // the request's stop sequences in the reference's word-list layout (the engine samples the FIRST token)
             build_word_list(r.stop, sw.data() + (size_t)i * 2 * STOP_LW);
             any_stop |= !r.stop.empty();
@@ -680,103 +728,107 @@ struct ftcf_batcher : BatcherSched {
         }
         FTCF_HIP_CHECK(hipMemcpy(d_prompt, ids.data(), ids.size() * 4, hipMemcpyHostToDevice));
         FTCF_HIP_CHECK(hipMemcpy(d_plen, lens.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-        ftcf_forward_args a{};
+        ftcf_forward_args& a = b.a;
         a.input_ids = d_prompt;
         a.input_lengths = d_plen;
         a.batch_size = n;
         a.max_input_len = S;
         a.output_len = 1;
         a.beam_width = 1;
-        a.top_k = topk.data();
+        a.top_k = b.topk.data();
         a.n_top_k = n;
-        a.top_p = topp.data();
+        a.top_p = b.topp.data();
         a.n_top_p = n;
-        a.temperature = temp.data();
+        a.temperature = b.temp.data();
         a.n_temperature = n;
-        a.repetition_penalty = rep.data();
+        a.repetition_penalty = b.rep.data();
         a.n_repetition_penalty = n;
         if (any_stop) {
             FTCF_HIP_CHECK(hipMemcpy(d_sw, sw.data(), sw.size() * 4, hipMemcpyHostToDevice));
             a.stop_words_list = d_sw;
             a.stop_words_len = STOP_LW;
         }
-        a.random_seed = seed.data();
+        a.random_seed = b.seed.data();
         a.n_random_seed = n;
         a.output_ids = d_pout;
         a.sequence_lengths = d_pseq;
         if (want_log_probs) {  // (the engine then runs the soft-max statistics as return_cum_log_probs = 1 does: the decode steps' setting)
             a.output_log_probs = d_polp;
         }
-        if (want_top > 0) {
-            a.top_logprobs       = want_top;
+        if (b.top_n > 0) {
+            a.top_logprobs       = b.top_n;
             a.top_logprob_ids    = d_ptop_ids;  // [n, 1, 1, top_n]
             a.top_logprob_values = d_ptop_lp;
         }
-        // the first tokens' logit processors: the rows' options and masks by row of this batch, the stage as the engine's
-        // logits hook (history = the padded prompt rows, nothing generated yet)
-        bool any_lp = false;
+        // the first tokens' logit processors: the rows' options and masks by row of this batch (history = the padded prompt
+        // rows, nothing generated yet)
         for (int i = 0; i < n; i++) {
             const bool on = rs[i].lopt.any() || !rs[i].mask.empty();
             lp_adm.flags[i] = on ? 1 : 0;
             if (on) {
                 stage_logit_row(lp_adm, i, &rs[i].lopt, &rs[i].mask, lens[i], st);
-                any_lp = true;
+                b.any_lp = true;
             }
         }
-        LogitsHook first_logits(e, any_lp ? std::function<void(float*, int, hipStream_t)>([this, n, S](float* lg, int rows, hipStream_t s2) {
+    }
+    // the prompt phase (host synchronous: K/V of row i, positions [0, len_i), are in the engine's cache [L][n][nh][S + 1][dh]
+    // afterwards), from the first uncached token when slot si0's request had a prefix hit
+    void prompt_phase(const AdmitBatch& b, const int si0)
+    {
+        const int  n = b.n, S = b.S, hit_tokens = b.hit_tokens;
+        LogitsHook first_logits(e, b.any_lp ? std::function<void(float*, int, hipStream_t)>([this, n, S](float* lg, int rows, hipStream_t s2) {
             FTCF_CHECK_ARG(rows == n, "batcher: the engine's first step has other rows than the admission");
             enqueue_logit_stage(lp_adm, true, lg, n, nullptr, d_prompt, 1, S, d_plen, 0, s2);
         }) : nullptr);
-        const int hit_tokens = hit ? (int)hit->size() * P : 0;
-        if (hit_tokens > 0) {
-            // the prompt phase starts at the first uncached token; first the cached pages go to cache row 0 (the engine's cache
-            // exists only inside forward(): the gather is its prefill_prefix hook)
-            const int        si = sis[0];
-            std::vector<int> row(max_pages, 0);
-            std::copy(slots[si].pages.begin(), slots[si].pages.end(), row.begin());
-            FTCF_HIP_CHECK(hipMemcpy(d_pt + (size_t)si * max_pages, row.data(), (size_t)max_pages * 4, hipMemcpyHostToDevice));
-            PrefillFrom from(e, hit_tokens, [this, si, S, hit_tokens] {
-                launch_gather_pages_to_kv(e->k_cache, e->v_cache, kpool, vpool, d_pt + (size_t)si * max_pages, e->L, e->nhl, e->dh, S + 1,
-                                          hit_tokens, P, pool_layer_elems, e->stream);
-            });
-            e->forward(a);
+        if (hit_tokens == 0) {
+            e->forward(b.a);
+            return;
         }
-        else {
-            e->forward(a);  // host synchronous: K/V of row i, positions [0, len_i), are in the engine's cache [L][n][nh][S + 1][dh]
-        }
+        // first the cached pages go to cache row 0 (the engine's cache exists only inside forward(): the gather is its
+        // prefill_prefix hook)
+        upload_page_rows(si0, &slots[si0].pages, 1, e->stream, true);
+        PrefillFrom from(e, hit_tokens, [this, si0, S, hit_tokens] {
+            launch_gather_pages_to_kv(e->k_cache, e->v_cache, kpool, vpool, pt_row(si0), e->L, e->nhl, e->dh, S + 1, hit_tokens, P,
+                                      pool_layer_elems, e->stream);
+        });
+        e->forward(b.a);
+    }
+    // the first tokens (with what the step asked for: log-probabilities, top-N pairs) and, per request, the prompt's K/V into
+    // the slot's pages and the slot's state
+    void install_admitted(const AdmitBatch& b, const std::vector<int>& sis, const std::vector<Request>& rs, std::vector<Event>& ev,
+                          hipStream_t st)
+    {
+        const int        n = b.n, S = b.S, hit_tokens = b.hit_tokens, top_n = b.top_n;
         std::vector<int> out((size_t)n * (S + 1));
         FTCF_HIP_CHECK(hipMemcpy(out.data(), d_pout, out.size() * 4, hipMemcpyDeviceToHost));
         std::vector<float> first_lp((size_t)n, NAN);
-        if (want_log_probs) {
+        if (b.a.output_log_probs) {
             FTCF_HIP_CHECK(hipMemcpy(first_lp.data(), d_polp, (size_t)n * 4, hipMemcpyDeviceToHost));
         }
-        std::vector<int>   first_top_ids((size_t)n * want_top);
-        std::vector<float> first_top_lp((size_t)n * want_top);
-        if (want_top > 0) {
+        std::vector<int>   first_top_ids((size_t)n * top_n);
+        std::vector<float> first_top_lp((size_t)n * top_n);
+        if (top_n > 0) {
             FTCF_HIP_CHECK(hipMemcpy(first_top_ids.data(), d_ptop_ids, first_top_ids.size() * 4, hipMemcpyDeviceToHost));
             FTCF_HIP_CHECK(hipMemcpy(first_top_lp.data(), d_ptop_lp, first_top_lp.size() * 4, hipMemcpyDeviceToHost));
         }
         const size_t row_kv = (size_t)e->nhl * (S + 1) * e->dh;  // one row of one layer of the engine's cache
         for (int i = 0; i < n; i++) {
             const Request& r  = rs[i];
-            const int      si = sis[i], len = lens[i];
+            const int      si = sis[i], len = b.lens[i];
             Slot&          s  = slots[si];
             // the engine's output rows are compacted (prompt, then the generated tokens: invokeGatherTree removes the padding)
-            const int        first = out[(size_t)i * (S + 1) + len];
-            std::vector<int> row(max_pages, 0);
-            std::copy(s.pages.begin(), s.pages.end(), row.begin());
-            FTCF_HIP_CHECK(hipMemcpyAsync(d_pt + (size_t)si * max_pages, row.data(), (size_t)max_pages * 4, hipMemcpyHostToDevice, st));
+            const int first = out[(size_t)i * (S + 1) + len];
+            upload_page_rows(si, &s.pages, 1, st);
             // (a hit: only the tail's pages; the cached ones are immutable)
             launch_scatter_kv_to_pages(e->k_cache + (size_t)i * row_kv + (size_t)hit_tokens * e->dh,
                                        e->v_cache + (size_t)i * row_kv + (size_t)hit_tokens * e->dh, kpool, vpool,
-                                       d_pt + (size_t)si * max_pages + hit_tokens / P, e->L, e->nhl, e->dh, S + 1, len - hit_tokens, P,
-                                       pool_layer_elems, st, (size_t)n * row_kv);
+                                       pt_row(si) + hit_tokens / P, e->L, e->nhl, e->dh, S + 1, len - hit_tokens, P, pool_layer_elems, st,
+                                       (size_t)n * row_kv);
             // per-slot state of the decode steps: the history is prompt, then the first token; draw 0 went to the first token
             const int done = start_slot(si, r, first, e->cfg.end_id) ? 1 : 0;
             upload_slot_state(si, s, 1, 0.f, st);
             ev.push_back(Event{r.id, first, done, first_lp[i]});  // (the token callback fires when the admission has succeeded: step())
-            ev.back().top_ids.assign(first_top_ids.begin() + (size_t)i * want_top, first_top_ids.begin() + (size_t)(i + 1) * want_top);
-            ev.back().top_lp.assign(first_top_lp.begin() + (size_t)i * want_top, first_top_lp.begin() + (size_t)(i + 1) * want_top);
+            cut_top(ev.back(), first_top_ids, first_top_lp, i, top_n);
             if (done) {
                 const uint8_t one8 = 1;
                 FTCF_HIP_CHECK(hipMemcpy(d_fin + si, &one8, 1, hipMemcpyHostToDevice));
@@ -784,16 +836,23 @@ struct ftcf_batcher : BatcherSched {
             }
         }
     }
+    // prompts -> ONE ragged batch through the engine's context path (+ first tokens) -> pages of their slots
+    void admit(const std::vector<int>& sis, const std::vector<Request>& rs, const int n, std::vector<Event>& ev,
+               const std::vector<int>* hit = nullptr)
+    {
+        Range rg("ftcf.batcher.admit");
+        deferred.clear();
+        AdmitBatch b;
+        build_admission(b, sis, rs, n, hit, e->stream);
+        prompt_phase(b, sis[0]);
+        install_admitted(b, sis, rs, ev, e->stream);
+    }
 
     // ---- beam groups ------------------------------------------------------------------------------------------------
     void upload_group_tables(const BeamGroup& g, hipStream_t st)
     {
-        std::vector<int> rows((size_t)g.K * max_pages, 0);
-        for (int k = 0; k < g.K; k++) {
-            std::copy(g.lists[k].begin(), g.lists[k].end(), rows.begin() + (size_t)k * max_pages);
-        }
-        FTCF_HIP_CHECK(hipMemcpyAsync(d_pt + (size_t)g.si * max_pages, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, st));
-        FTCF_HIP_CHECK(hipStreamSynchronize(st));  // (the host temporary dies here)
+        upload_page_rows(g.si, g.lists.data(), g.K, st);
+        FTCF_HIP_CHECK(hipStreamSynchronize(st));
     }
     // every unfinished beam gets a page of its OWN for position `pos` (the next append): a fresh one on a page boundary, a copy
     // of the shared one otherwise
@@ -828,15 +887,16 @@ struct ftcf_batcher : BatcherSched {
         BeamGroup&  g = groups.at(si);
         hipStream_t st = e->stream;
         const int   total = g.n + g.max_new;
-        launch_gather_tree_beam(d_bres + (size_t)si * (max_len + 2), d_bres_len + si, d_bout + (size_t)si * (max_len + 2),
-                                d_bpar + (size_t)si * (max_len + 2), d_bseq + si, d_bin + si, 1, g.K, g.n, total, e->cfg.end_id, st);
+        const size_t reg  = beam_region(si);
+        launch_gather_tree_beam(d_bres + reg, d_bres_len + si, d_bout + reg, d_bpar + reg, d_bseq + si, d_bin + si, 1, g.K, g.n, total,
+                                e->cfg.end_id, st);
         BeamResult r;
         r.K     = g.K;
         r.total = total;
         r.ids.resize((size_t)g.K * total);
         r.lens.resize(g.K);
         r.cum.resize(g.K);
-        FTCF_HIP_CHECK(hipMemcpyAsync(r.ids.data(), d_bres + (size_t)si * (max_len + 2), r.ids.size() * 4, hipMemcpyDeviceToHost, st));
+        FTCF_HIP_CHECK(hipMemcpyAsync(r.ids.data(), d_bres + reg, r.ids.size() * 4, hipMemcpyDeviceToHost, st));
         FTCF_HIP_CHECK(hipMemcpyAsync(r.lens.data(), d_bres_len + si, (size_t)g.K * 4, hipMemcpyDeviceToHost, st));
         FTCF_HIP_CHECK(hipMemcpyAsync(r.cum.data(), d_cum + si, (size_t)g.K * 4, hipMemcpyDeviceToHost, st));
         FTCF_HIP_CHECK(hipStreamSynchronize(st));
@@ -853,6 +913,21 @@ struct ftcf_batcher : BatcherSched {
         }
         else {
             ev.push_back(Event{id, -1, 1});
+        }
+    }
+    static bool all_finished(const std::vector<uint8_t>& fin)
+    {
+        return std::all_of(fin.begin(), fin.end(), [](uint8_t f) { return f != 0; });
+    }
+    // a group whose beams' flags after a step are `fin`: it leaves when every beam has finished or its budget is used up, else
+    // its beams get their pages for the next append
+    void finish_or_append(BeamGroup& g, const std::vector<uint8_t>& fin, std::vector<Event>& ev, const bool fire_now)
+    {
+        if (all_finished(fin) || g.generated >= g.max_new) {
+            finish_group(g.si, ev, fire_now);
+        }
+        else {
+            prepare_append(g, g.n + g.generated - 1, fin, e->stream);
         }
     }
     // prompt -> the engine's own beam-search request of ONE step (prefill of the K tiled rows, first beam step) -> the group's
@@ -898,9 +973,18 @@ struct ftcf_batcher : BatcherSched {
         BeamGroup& G = open_group(si, r);  // the prompt's pages, shared by every beam
         upload_group_tables(G, st);
         const size_t row_kv = (size_t)e->nhl * (n + 1) * e->dh;
-        launch_scatter_kv_to_pages(e->k_cache, e->v_cache, kpool, vpool, d_pt + (size_t)si * max_pages, e->L, e->nhl, e->dh, n + 1, n, P,
-                                   pool_layer_elems, st, (size_t)K * row_kv);
-        const size_t reg = (size_t)si * (max_len + 2);
+        launch_scatter_kv_to_pages(e->k_cache, e->v_cache, kpool, vpool, pt_row(si), e->L, e->nhl, e->dh, n + 1, n, P, pool_layer_elems, st,
+                                   (size_t)K * row_kv);
+        const std::vector<uint8_t> fin = upload_group_state(si, r, st);
+        start_group_slots(G);
+        finish_or_append(G, fin, ev, false);  // (a group that leaves at once: step() fires its event when the admission has succeeded)
+    }
+    // the state of a group's K slots after the engine's first beam step, out of the engine's buffers and the request; returns the
+    // beams' finished flags
+    std::vector<uint8_t> upload_group_state(const int si, const Request& r, hipStream_t st)
+    {
+        const int    K = r.beam_width, n = (int)r.prompt.size();
+        const size_t reg = beam_region(si);
         FTCF_HIP_CHECK(hipMemcpyAsync(d_bout + reg, e->step_ids, (size_t)(n + 1) * K * 4, hipMemcpyDeviceToDevice, st));
         FTCF_HIP_CHECK(hipMemcpyAsync(d_bpar + reg, e->parent_ids, (size_t)(n + 1) * K * 4, hipMemcpyDeviceToDevice, st));
         FTCF_HIP_CHECK(hipMemcpyAsync(d_bseq + si, e->seq_len, (size_t)K * 4, hipMemcpyDeviceToDevice, st));
@@ -925,16 +1009,7 @@ struct ftcf_batcher : BatcherSched {
         FTCF_HIP_CHECK(hipMemcpyAsync(d_bdiv + si, &r.diversity, 4, hipMemcpyHostToDevice, st));
         FTCF_HIP_CHECK(hipMemcpyAsync(d_blen + si, &r.len_penalty, 4, hipMemcpyHostToDevice, st));
         FTCF_HIP_CHECK(hipStreamSynchronize(st));
-        start_group_slots(G);
-        bool all_fin = true;
-        for (int k = 0; k < K; k++) {
-            all_fin &= fin[k] != 0;
-        }
-        if (all_fin || G.generated >= G.max_new) {
-            finish_group(si, ev, false);  // (step() fires it when the admission has succeeded)
-            return;
-        }
-        prepare_append(G, n, fin, st);
+        return fin;
     }
     // the beam kernels of every running group on this step's logits, BEFORE the sampling kernels (whose end-id mask rewrites the
     // logits of rows that are finished in their view -- the groups' rows)
@@ -943,7 +1018,7 @@ struct ftcf_batcher : BatcherSched {
         for (auto& kv : groups) {
             BeamGroup&   g   = kv.second;
             const int    si  = g.si, step = g.n + g.generated;
-            const size_t reg = (size_t)si * (max_len + 2);
+            const size_t reg = beam_region(si);
             hipLaunchKernelGGL(k_batcher_set_step, dim3(1), dim3(1), 0, st, d_bstate + si, step);
             BeamParams bp{};
             bp.logits = logits + (size_t)si * e->V;
@@ -980,13 +1055,12 @@ struct ftcf_batcher : BatcherSched {
             const BeamGroup& g    = kv.second;
             const int        step = g.n + g.generated;
             hipLaunchKernelGGL(k_batcher_beam_advance, dim3(1), dim3(64), 0, st, d_tok + g.si, d_len + g.si,
-                               d_bout + (size_t)g.si * (max_len + 2) + (size_t)step * g.K, g.K);
+                               d_bout + beam_region(g.si) + (size_t)step * g.K, g.K);
         }
     }
     // after the step's synchronisation: every beam takes over its parent's pages, finished groups leave
     void advance_groups(std::vector<Event>& ev, const std::vector<uint8_t>& fin_all)
     {
-        hipStream_t      st = e->stream;
         std::vector<int> leaders;
         for (auto& kv : groups) {
             leaders.push_back(kv.first);
@@ -995,21 +1069,12 @@ struct ftcf_batcher : BatcherSched {
             BeamGroup&       g = groups.at(si);
             const int        step = g.n + g.generated;
             std::vector<int> parent(g.K);
-            FTCF_HIP_CHECK(hipMemcpy(parent.data(), d_bpar + (size_t)si * (max_len + 2) + (size_t)step * g.K, (size_t)g.K * 4,
-                                     hipMemcpyDeviceToHost));
+            FTCF_HIP_CHECK(hipMemcpy(parent.data(), d_bpar + beam_region(si) + (size_t)step * g.K, (size_t)g.K * 4, hipMemcpyDeviceToHost));
             reparent_group(g, parent);
-            std::vector<uint8_t> fin(fin_all.begin() + si, fin_all.begin() + si + g.K);
-            bool                 all_fin = true;
             for (int k = 0; k < g.K; k++) {
-                all_fin &= fin[k] != 0;
                 slots[si + k].len += 1;
             }
-            if (all_fin || g.generated >= g.max_new) {
-                finish_group(si, ev);
-            }
-            else {
-                prepare_append(g, g.n + g.generated - 1, fin, st);
-            }
+            finish_or_append(g, std::vector<uint8_t>(fin_all.begin() + si, fin_all.begin() + si + g.K), ev, true);
         }
     }
 
@@ -1059,143 +1124,121 @@ struct ftcf_batcher : BatcherSched {
         }
     }
 
-    // one token for every running slot
-    void decode(std::vector<Event>& ev)
+    // ---- one decode step, stage by stage in enqueue order (decode() below) ------------------------------------------------------
+    // every slot's hidden state from its token (recomputed each step: the residual never aliases across steps), the burst
+    // GEMMs' tag space and step counter
+    void enqueue_embedding(hipStream_t st)
     {
-        Range                  rg("ftcf.batcher.decode");
-        hipStream_t            st = e->stream;
-        const int              B = max_batch, H = e->H, hl = e->hl, il = e->il, L = e->L, V = e->V;
-        const bool             int8 = e->int8;
-        const bool             dual = residual_dual_ln_supported(H);
-        const int              tp = e->cfg.tensor_para_size;
-        const bool             tp1 = tp == 1;  // (tensor parallel: the layer ends with residual + all-reduce, GptNeoXDecoder.cc:357-359)
-        e->stats.decode_path = use_rows ? 3 : 2;  // (ftcf_gptneox_get_stats of the borrowed engine: which layers the last decode step ran)
-        if (overcommit) {
-            grow_before_decode(st);  // (may swap requests out; throws "swap space exhausted" before anything of the step is enqueued)
-            if (!any_active()) {
-                return;  // (the only running request swapped itself out: beam budgets hold the pool)
-            }
-            refresh_host_flags();
-        }
-        hipLaunchKernelGGL(k_batcher_embed, dim3(B), dim3(256), 0, st, x, e->wte, d_tok, H);
+        hipLaunchKernelGGL(k_batcher_embed, dim3(max_batch), dim3(256), 0, st, x, e->wte, d_tok, e->H);
         if ((gemm_steps++ & 0x3ffff) == 0 && smallm_ws) {  // the tag space of the burst GEMMs wraps: start it clean
             FTCF_HIP_CHECK(hipMemsetAsync(smallm_ws, 0, smallm_partial + gemm_smallm_ticket_bytes(), st));
         }
         hipLaunchKernelGGL(k_batcher_tick, dim3(1), dim3(1), 0, st, d_gstate);
-        if (use_rows) {
-            // every layer of the step in one launch (rows_device.hip.h, paged K/V): x -> x
-            if ((rows_steps++ & 0xfffff) == 0) {  // (the tag space: start it clean now and then)
-                FTCF_HIP_CHECK(hipMemsetAsync(rows_ws, 0, rows_flag_bytes(rplan, B, e->nhl), st));
-                FTCF_HIP_CHECK(hipMemsetAsync(d_rstep, 0, sizeof(int), st));
-            }
-            hipLaunchKernelGGL(k_batcher_rows_prep, dim3(B), dim3(64), 0, st, d_rstep, d_rot, d_len, e->cfg.rotary_embedding_dim);
-            RowsParams rp{};
-            rp.layers = d_rlayers;
-            rp.L = L;
-            rp.l_begin = 0;
-            rp.l_end = L;
-            rp.x_in = x;
-            rp.x_out = x;
-            rp.M = B;
-            rp.H = H;
-            rp.Hl = hl;
-            rp.Il = il;
-            rp.nh = e->nhl;
-            rp.dh = e->dh;
-            rp.rot = e->cfg.rotary_embedding_dim;
-            rp.s_max = max_len;
-            rp.tp = 1;
-            rp.plan = rplan;
-            rows_carve(rp, rows_ws);
-            rp.d_step = d_rstep;
-            rp.d_stop = nullptr;
-            rp.seq_len = d_len;
-            rp.input_lengths = nullptr;
-            rp.max_input_len = 0;
-            rp.finished = d_fin;
-            rp.rot_table = d_rot;
-            rp.eps = 1e-5f;
-            rp.page_table = d_pt;
-            rp.page_tokens = P;
-            rp.max_pages = max_pages;
-            launch_decode_rows(rp, int8, st);
+    }
+    // the rows kernel over the paged pool: every slot has its own step (no stop flag, no input lengths), x -> x
+    RowsParams rows_params()
+    {
+        RowsParams rp = e->rows_shape(d_rlayers, x);
+        rp.M     = max_batch;
+        rp.s_max = max_len;
+        rp.tp    = 1;
+        rp.plan  = rplan;
+        rows_carve(rp, rows_ws);
+        rp.d_step      = d_rstep;
+        rp.seq_len     = d_len;
+        rp.finished    = d_fin;
+        rp.rot_table   = d_rot;
+        rp.page_table  = d_pt;
+        rp.page_tokens = P;
+        rp.max_pages   = max_pages;
+        return rp;
+    }
+    // every layer of the step in one launch (rows_device.hip.h, paged K/V)
+    void enqueue_rows_layers(hipStream_t st)
+    {
+        if ((rows_steps++ & 0xfffff) == 0) {  // (the tag space: start it clean now and then)
+            FTCF_HIP_CHECK(hipMemsetAsync(rows_ws, 0, rows_flag_bytes(rplan, max_batch, e->nhl), st));
+            FTCF_HIP_CHECK(hipMemsetAsync(d_rstep, 0, sizeof(int), st));
         }
-        // tensor parallel, 4..32 slots: the layer's all-reduce on the side stream under the other micro-batch's launches
-        // (FTCF_DECODE_OVERLAP = 0 / 1, auto = timed on this node)
-        const bool overlap = !use_rows && decode_overlap_now(B, dual);
-        const auto t_dec0  = std::chrono::steady_clock::now();
-        if (!use_rows) {
-            // the batched parallel-residual layers (layers.hip.h) over the paged K/V pool, with this batcher's buffers and burst
-            // workspace.  (Every slot's hidden state is recomputed from its token each step: the residual never aliases across steps.)
-            if (overlap) {
-                e->decode_overlap_streams();
-            }
-            ParallelResidualDecoder walk = e->layer_walk();
-            walk.fake_mul = 1;  // (fake peers: the all-reduce below scales the sum itself)
-            walk.x = x, walk.nrm = nrm, walk.nrm2 = nrm2, walk.qkv = qkv, walk.ctx = ctx, walk.att = att, walk.ffn = ffn, walk.mid = mid;
-            walk.ws = smallm_ws, walk.partial = smallm_partial, walk.region = smallm_region;
-            walk.d_step = &d_gstate->step;
-            walk.seq = &smallm_seq;
-            walk.plain = [&](const f16* A, const DenseWeight& dw, const f16* bias, int act, f16* C, int m, int n, int k, hipStream_t s2, int) {
-                gemm_dispatch(A, dw.kernel, dw.scale, bias, act, C, m, n, k, int8, s2, nullptr, 0, e->num_cu, nullptr, nullptr,
-                              s2 == st ? tiled_ws : nullptr);
-            };
-            auto attention = [&](int l, const LayerWeights& w, int r0, int M, hipStream_t s2) {
-                const size_t    o = (size_t)r0;
-                MmhaPagedParams mp{};
-                mp.qkv = qkv + o * 3 * hl;
-                mp.qkv_bias = w.qkv.bias;
-                mp.kpool = kpool + (size_t)l * pool_layer_elems;
-                mp.vpool = vpool + (size_t)l * pool_layer_elems;
-                mp.page_table = d_pt + o * max_pages;
-                mp.len = d_len + o;
-                mp.finished = d_fin + o;
-                mp.B = M;
-                mp.nh = e->nhl;
-                mp.dh = e->dh;
-                mp.rot = e->cfg.rotary_embedding_dim;
-                mp.P = P;
-                mp.max_pages = max_pages;
-                mp.ctx = ctx + o * hl;
-                launch_mmha_paged(mp, max_len, s2);
-            };
-            auto reduce = [&](f16* buf, size_t count, hipStream_t s2, bool) { e->allreduce(buf, count, s2); };
-            if (overlap) {
-                walk.forward_overlapped(B, attention, reduce);
-            }
-            else {
-                // the attention branch and the FFN branch on two streams, as the engine's batched decode, else up to
-                // 16 slots the independent GEMMs paired per launch, else gemm_dispatch
-                const DecodeGemms gemms = (smallm_ws && e->decode_branches && e->side) ? DecodeGemms::branches
-                                          : (smallm_ws && B <= 16)                     ? DecodeGemms::grouped
-                                                                                       : DecodeGemms::plain;
-                walk.forward(B, gemms, attention, reduce);
-            }
+        hipLaunchKernelGGL(k_batcher_rows_prep, dim3(max_batch), dim3(64), 0, st, d_rstep, d_rot, d_len, e->cfg.rotary_embedding_dim);
+        launch_decode_rows(rows_params(), e->int8, st);
+    }
+    // the batched parallel-residual layers (layers.hip.h) over the paged K/V pool, with this batcher's buffers and burst workspace
+    // overlap (tensor parallel, 4..32 slots): the layer's all-reduce on the side stream under the other micro-batch's launches
+    void enqueue_walk_layers(const bool overlap, hipStream_t st)
+    {
+        const int  B = max_batch, hl = e->hl;
+        const bool int8 = e->int8;
+        if (overlap) {
+            e->decode_overlap_streams();
         }
-        {
-            // LM head; tensor parallel: rank r computes rows [r V/TP, (r+1) V/TP) of the replicated lm_head into its slice of
-            // `gather`, all-gather + transpose (GptNeoX.cc:888-925, as the engine's own step)
-            const int    rows = tp1 ? V : e->vl;
-            const f16*   Wr   = tp1 ? e->lm_head : e->lm_head + (size_t)e->cfg.tensor_para_rank * e->vl * H;
-            float*       out  = tp1 ? logits : gather + (size_t)e->cfg.tensor_para_rank * B * e->vl;
-            if (B <= 4) {
-                launch_lm_head(x, Wr, out, B, rows, H, rows, st, e->final_g, e->final_b, 1e-5f);
-            }
-            else {
-                launch_layernorm(x, e->final_g, e->final_b, nrm, B, H, 1e-5f, true, st);
-                lm_head_dispatch(nrm, Wr, out, B, rows, H, rows, st);
-            }
-            if (!tp1) {
-                e->allgather_logits(gather, logits, B, st);
-            }
+        ParallelResidualDecoder walk = e->layer_walk();
+        walk.fake_mul = 1;  // (fake peers: the all-reduce below scales the sum itself)
+        walk.x = x, walk.nrm = nrm, walk.nrm2 = nrm2, walk.qkv = qkv, walk.ctx = ctx, walk.att = att, walk.ffn = ffn, walk.mid = mid;
+        walk.ws = smallm_ws, walk.partial = smallm_partial, walk.region = smallm_region;
+        walk.d_step = &d_gstate->step;
+        walk.seq = &smallm_seq;
+        walk.plain = [&](const f16* A, const DenseWeight& dw, const f16* bias, int act, f16* C, int m, int n, int k, hipStream_t s2, int) {
+            gemm_dispatch(A, dw.kernel, dw.scale, bias, act, C, m, n, k, int8, s2, nullptr, 0, e->num_cu, nullptr, nullptr,
+                          s2 == st ? tiled_ws : nullptr);
+        };
+        auto attention = [&](int l, const LayerWeights& w, int r0, int M, hipStream_t s2) {
+            const size_t    o = (size_t)r0;
+            MmhaPagedParams mp{};
+            mp.qkv = qkv + o * 3 * hl;
+            mp.qkv_bias = w.qkv.bias;
+            mp.kpool = kpool + (size_t)l * pool_layer_elems;
+            mp.vpool = vpool + (size_t)l * pool_layer_elems;
+            mp.page_table = pt_row(r0);
+            mp.len = d_len + o;
+            mp.finished = d_fin + o;
+            mp.B = M;
+            mp.nh = e->nhl;
+            mp.dh = e->dh;
+            mp.rot = e->cfg.rotary_embedding_dim;
+            mp.P = P;
+            mp.max_pages = max_pages;
+            mp.ctx = ctx + o * hl;
+            launch_mmha_paged(mp, max_len, s2);
+        };
+        auto reduce = [&](f16* buf, size_t count, hipStream_t s2, bool) { e->allreduce(buf, count, s2); };
+        if (overlap) {
+            walk.forward_overlapped(B, attention, reduce);
+            return;
         }
-        // the logit processors of the rows that have any: everything behind this point (beam kernels aside: their rows are not
-        // processed) reads the processed logits.  No such row: nothing is enqueued.
-        enqueue_decode_logit_stage(st);
+        // the attention branch and the FFN branch on two streams, as the engine's batched decode, else up to
+        // 16 slots the independent GEMMs paired per launch, else gemm_dispatch
+        const DecodeGemms gemms = (smallm_ws && e->decode_branches && e->side) ? DecodeGemms::branches
+                                  : (smallm_ws && B <= 16)                     ? DecodeGemms::grouped
+                                                                               : DecodeGemms::plain;
+        walk.forward(B, gemms, attention, reduce);
+    }
+    // LM head; tensor parallel: rank r computes rows [r V/TP, (r+1) V/TP) of the replicated lm_head into its slice of
+    // `gather`, all-gather + transpose (GptNeoX.cc:888-925, as the engine's own step)
+    void enqueue_lm_head(hipStream_t st)
+    {
+        const int  B = max_batch, H = e->H;
+        const bool tp1 = e->cfg.tensor_para_size == 1;
+        const int  rows = tp1 ? e->V : e->vl;
+        const f16* Wr   = tp1 ? e->lm_head : e->lm_head + (size_t)e->cfg.tensor_para_rank * e->vl * H;
+        float*     out  = tp1 ? logits : gather + (size_t)e->cfg.tensor_para_rank * B * e->vl;
+        if (B <= 4) {
+            launch_lm_head(x, Wr, out, B, rows, H, rows, st, e->final_g, e->final_b, 1e-5f);
+        }
+        else {
+            launch_layernorm(x, e->final_g, e->final_b, nrm, B, H, 1e-5f, true, st);
+            lm_head_dispatch(nrm, Wr, out, B, rows, H, rows, st);
+        }
+        if (!tp1) {
+            e->allgather_logits(gather, logits, B, st);
+        }
+    }
+    SamplingParams sampling_params()
+    {
         SamplingParams sp{};
         sp.logits = logits;
-        sp.B = B;
-        sp.V = V;
+        sp.B = max_batch;
+        sp.V = e->V;
         sp.max_input_len = 0;
         sp.end_id = e->cfg.end_id;
         sp.input_lengths = d_zero;
@@ -1218,9 +1261,8 @@ struct ftcf_batcher : BatcherSched {
         sp.seq_len = d_len;     // + 1 per sampled token: the slot's length
         sp.cum_log_probs = d_cum;
         sp.output_log_probs = d_olp;  // (row_len: one value per slot, written where cum_log_probs is)
-        const int top_n = want_top;
-        if (top_n > 0) {  // (row_len: one [B, top_n] row; only the slots that sample are written and read)
-            sp.top_logprobs       = top_n;
+        if (want_top > 0) {  // (row_len: one [B, top_n] row; only the slots that sample are written and read)
+            sp.top_logprobs       = want_top;
             sp.top_logprob_ids    = d_top_ids;
             sp.top_logprob_values = d_top_lp;
         }
@@ -1229,91 +1271,147 @@ struct ftcf_batcher : BatcherSched {
         sp.ws = samp_ws;
         sp.max_top_k = host_max_top_k;
         sp.any_top_p = host_any_top_p;
-        if (!groups.empty()) {  // the rows of beam groups are "finished" for the sampling kernels
+        return sp;
+    }
+    // the sampling kernels on the slots' rows and, with beam groups running, the beam kernels on theirs: the groups' rows are
+    // "finished" in the sampling kernels' view (d_sfin), whose new flags of the other rows go back to d_fin afterwards
+    void enqueue_sampling(hipStream_t st)
+    {
+        SamplingParams sp    = sampling_params();
+        const bool     beams = !groups.empty();
+        if (beams) {
             enqueue_beam_steps(st);
-            hipLaunchKernelGGL(k_batcher_sampling_view, dim3(1), dim3(64), 0, st, d_sfin, d_fin, d_isbeam, B, 0);
+            hipLaunchKernelGGL(k_batcher_sampling_view, dim3(1), dim3(64), 0, st, d_sfin, d_fin, d_isbeam, max_batch, 0);
             sp.finished = d_sfin;
         }
         DynamicDecodeLayer{}.forward(sp, st, false);  // (the stop / length criteria are the scheduler's: no finish step)
-        hipLaunchKernelGGL(k_batcher_last_token, dim3(1), dim3(64), 0, st, d_tok, d_hist, d_len, B);
-        if (!groups.empty()) {
-            hipLaunchKernelGGL(k_batcher_sampling_view, dim3(1), dim3(64), 0, st, d_sfin, d_fin, d_isbeam, B, 1);
+        hipLaunchKernelGGL(k_batcher_last_token, dim3(1), dim3(64), 0, st, d_tok, d_hist, d_len, max_batch);
+        if (beams) {
+            hipLaunchKernelGGL(k_batcher_sampling_view, dim3(1), dim3(64), 0, st, d_sfin, d_fin, d_isbeam, max_batch, 1);
             enqueue_beam_advance(st);
         }
-        std::vector<int>     tok(B);
-        std::vector<uint8_t> fin(B);
-        std::vector<float>   lp(B);
-        int                  gemm_err = 0;
-        FTCF_HIP_CHECK(hipMemcpyAsync(tok.data(), d_tok, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-        FTCF_HIP_CHECK(hipMemcpyAsync(lp.data(), d_olp, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-        std::vector<int>   top_ids((size_t)B * top_n);
-        std::vector<float> top_lp((size_t)B * top_n);
-        if (top_n > 0) {
-            FTCF_HIP_CHECK(hipMemcpyAsync(top_ids.data(), d_top_ids, top_ids.size() * 4, hipMemcpyDeviceToHost, st));
-            FTCF_HIP_CHECK(hipMemcpyAsync(top_lp.data(), d_top_lp, top_lp.size() * 4, hipMemcpyDeviceToHost, st));
+    }
+    // the host's copies of one decode step
+    struct StepResult {
+        int                  top_n = 0;
+        std::vector<int>     tok, top_ids;  // [B], [B][top_n]
+        std::vector<float>   lp, top_lp;
+        std::vector<uint8_t> fin;
+        // the sticky give-up words: the exchange-window all-reduce (read while ar_live), the rows kernel, the burst GEMMs
+        bool ar_live = false;
+        int  ar_err = 0, rows_err = 0, gemm_err = 0;
+    };
+    // ... filled by copies behind the step's kernels, then the step's ONE synchronisation
+    void read_back(StepResult& r, hipStream_t st)
+    {
+        const size_t B = (size_t)max_batch;
+        r.top_n = want_top;
+        r.tok.resize(B), r.lp.resize(B), r.fin.resize(B), r.top_ids.resize(B * r.top_n), r.top_lp.resize(B * r.top_n);
+        FTCF_HIP_CHECK(hipMemcpyAsync(r.tok.data(), d_tok, B * 4, hipMemcpyDeviceToHost, st));
+        FTCF_HIP_CHECK(hipMemcpyAsync(r.lp.data(), d_olp, B * 4, hipMemcpyDeviceToHost, st));
+        if (r.top_n > 0) {
+            FTCF_HIP_CHECK(hipMemcpyAsync(r.top_ids.data(), d_top_ids, r.top_ids.size() * 4, hipMemcpyDeviceToHost, st));
+            FTCF_HIP_CHECK(hipMemcpyAsync(r.top_lp.data(), d_top_lp, r.top_lp.size() * 4, hipMemcpyDeviceToHost, st));
         }
-        FTCF_HIP_CHECK(hipMemcpyAsync(fin.data(), d_fin, (size_t)B, hipMemcpyDeviceToHost, st));
+        FTCF_HIP_CHECK(hipMemcpyAsync(r.fin.data(), d_fin, B, hipMemcpyDeviceToHost, st));
         if (smallm_ws) {  // sticky flag of the burst GEMMs' in-launch split-K reduction (the engine's finish() reads its own)
-            FTCF_HIP_CHECK(hipMemcpyAsync(&gemm_err, reinterpret_cast<char*>(smallm_ws) + smallm_partial, sizeof(int),
+            FTCF_HIP_CHECK(hipMemcpyAsync(&r.gemm_err, reinterpret_cast<char*>(smallm_ws) + smallm_partial, sizeof(int),
                                           hipMemcpyDeviceToHost, st));
+        }
+        if (use_rows) {
+            FTCF_HIP_CHECK(hipMemcpyAsync(&r.rows_err, rows_ws, sizeof(int), hipMemcpyDeviceToHost, st));
         }
         // tensor parallel: the window all-reduce's sticky give-up word of this step's 2 L all-reduces (a peer that never arrived:
         // x is partly reduced and the step's tokens are not to be trusted either), read with the same copies
-        int rows_err = 0;
-        if (use_rows) {
-            FTCF_HIP_CHECK(hipMemcpyAsync(&rows_err, rows_ws, sizeof(int), hipMemcpyDeviceToHost, st));
-        }
-        int        ar_err  = 0;
-        const bool ar_live = e->cfg.tensor_para_size > 1 && e->cfg.comm && e->cfg.comm->ar_sync && e->cfg.comm->ar_seq > 0
-                             && !e->cfg.comm->ar_failed;
-        if (ar_live) {
-            FTCF_HIP_CHECK(hipMemcpyAsync(&ar_err, e->cfg.comm->ar_sync + 2, sizeof(int), hipMemcpyDeviceToHost, st));
+        r.ar_live = e->cfg.tensor_para_size > 1 && e->cfg.comm && e->cfg.comm->ar_sync && e->cfg.comm->ar_seq > 0 && !e->cfg.comm->ar_failed;
+        if (r.ar_live) {
+            FTCF_HIP_CHECK(hipMemcpyAsync(&r.ar_err, e->cfg.comm->ar_sync + 2, sizeof(int), hipMemcpyDeviceToHost, st));
         }
         FTCF_HIP_CHECK(hipStreamSynchronize(st));
-        decode_overlap_trial(std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_dec0).count(), st);
-        e->stats.decode_overlap = overlap ? 1 : 0;
-        if (ar_live && e->tp_scratch) {
+    }
+    // a step one of whose kernels gave up waiting: its tokens are dropped (nothing is reported, the slots keep their host state)
+    void check_give_ups(StepResult& r, hipStream_t st)
+    {
+        if (r.ar_live && e->tp_scratch) {
             // (collective: every rank's batcher runs the same step and has called the window all-reduce as often; all of them learn
             //  of any rank's failure and drop the step)
-            ar_err = comm_max(e->cfg.comm, ar_err, st, e->tp_scratch);
-            if (ar_err != 0) {
+            r.ar_err = comm_max(e->cfg.comm, r.ar_err, st, e->tp_scratch);
+            if (r.ar_err != 0) {
                 e->cfg.comm->ar_failed = true;  // this communicator keeps RCCL (or the emulation) from now on
                 throw Error(-2, "batcher decode: the exchange-window all-reduce gave up waiting for a peer; the step's tokens are dropped");
             }
         }
-        if (rows_err != 0) {
+        if (r.rows_err != 0) {
             // a hand-off of the rows kernel ran out of its bounded wait (cannot happen with every workgroup resident; bounded all the
-            // same): the step's tokens are dropped, the batcher goes on with the per-GEMM launches
+            // same): the batcher goes on with the per-GEMM launches
             use_rows = false;
-            throw Error(-2, "batcher decode: the rows kernel gave up waiting for a hand-off (code " + std::to_string(rows_err) + ")");
+            throw Error(-2, "batcher decode: the rows kernel gave up waiting for a hand-off (code " + std::to_string(r.rows_err) + ")");
         }
-        if (gemm_err != 0) {
-            // the tokens of this step are not to be trusted: nothing is reported, the slots keep their state (lengths and
-            // draw counters advanced on the device: the requests cannot be resumed exactly), the flag is cleared for the caller's
-            // next attempt
+        if (r.gemm_err != 0) {
+            // (lengths and draw counters advanced on the device: the requests cannot be resumed exactly); the flag is cleared for
+            // the caller's next attempt
             FTCF_HIP_CHECK(hipMemsetAsync(smallm_ws, 0, smallm_partial + gemm_smallm_ticket_bytes(), st));
             FTCF_HIP_CHECK(hipStreamSynchronize(st));
             throw Error(-2, "batcher decode: a split-K reducer of the batched GEMM gave up waiting for its sibling workgroups");
         }
-        for (int si = 0; si < B; si++) {
+    }
+    // the step's tokens into the running ordinary slots: events, and the sequences that end leave
+    void apply_tokens(const StepResult& r, std::vector<Event>& ev)
+    {
+        for (int si = 0; si < max_batch; si++) {
             Slot& s = slots[si];
             if (!s.active || s.group >= 0) {
                 continue;
             }
             s.len += 1;
             s.generated += 1;
-            s.hist.push_back(tok[si]);
-            const int done = (fin[si] || s.generated >= s.max_new || hits_stop_word(s)) ? 1 : 0;
-            Event x{s.id, tok[si], done, lp[si]};
-            x.top_ids.assign(top_ids.begin() + (size_t)si * top_n, top_ids.begin() + (size_t)(si + 1) * top_n);
-            x.top_lp.assign(top_lp.begin() + (size_t)si * top_n, top_lp.begin() + (size_t)(si + 1) * top_n);
+            s.hist.push_back(r.tok[si]);
+            const int done = (r.fin[si] || s.generated >= s.max_new || hits_stop_word(s)) ? 1 : 0;
+            Event     x{s.id, r.tok[si], done, r.lp[si]};
+            cut_top(x, r.top_ids, r.top_lp, si, r.top_n);
             emit(ev, x);
             if (done) {
-                FTCF_HIP_CHECK(retire(si, fin[si] != 0));
+                FTCF_HIP_CHECK(retire(si, r.fin[si] != 0));
             }
         }
+    }
+
+    // one token for every running slot
+    void decode(std::vector<Event>& ev)
+    {
+        Range       rg("ftcf.batcher.decode");
+        hipStream_t st = e->stream;
+        e->stats.decode_path = use_rows ? 3 : 2;  // (ftcf_gptneox_get_stats of the borrowed engine: which layers the last decode step ran)
+        if (overcommit) {
+            grow_before_decode(st);  // (may swap requests out; throws "swap space exhausted" before anything of the step is enqueued)
+            if (!any_active()) {
+                return;  // (the only running request swapped itself out: beam budgets hold the pool)
+            }
+            refresh_host_flags();
+        }
+        enqueue_embedding(st);
+        if (use_rows) {
+            enqueue_rows_layers(st);
+        }
+        // (FTCF_DECODE_OVERLAP = 0 / 1, auto = timed on this node from here to the step's synchronisation)
+        const bool overlap = !use_rows && decode_overlap_now(max_batch, residual_dual_ln_supported(e->H));
+        const auto t_dec0  = std::chrono::steady_clock::now();
+        if (!use_rows) {
+            enqueue_walk_layers(overlap, st);
+        }
+        enqueue_lm_head(st);
+        // the logit processors of the rows that have any: everything behind this point (beam kernels aside: their rows are not
+        // processed) reads the processed logits.  No such row: nothing is enqueued.
+        enqueue_decode_logit_stage(st);
+        enqueue_sampling(st);
+        StepResult r;
+        read_back(r, st);
+        decode_overlap_trial(std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_dec0).count(), st);
+        e->stats.decode_overlap = overlap ? 1 : 0;
+        check_give_ups(r, st);
+        apply_tokens(r, ev);
         if (!groups.empty()) {
-            advance_groups(ev, fin);
+            advance_groups(ev, r.fin);
         }
     }
 

@@ -904,22 +904,30 @@ struct ftcf_gptneox {
         return pp;
     }
 
-    RowsParams rows_params(int B, int s_max)
+    // the model's shape for the rows kernel: every layer of `layer_table`, hidden state xio -> xio (the batcher's decode step
+    // fills the rest for its paged pool, rows_params below for this engine's cache)
+    RowsParams rows_shape(const PersistLayer* layer_table, f16* xio) const
     {
         RowsParams rp{};
-        rp.layers = d_players;
+        rp.layers = layer_table;
         rp.L = L;
         rp.l_begin = 0;
         rp.l_end = L;
-        rp.x_in = x;
-        rp.x_out = x;
-        rp.M = B;
+        rp.x_in = xio;
+        rp.x_out = xio;
         rp.H = H;
         rp.Hl = hl;
         rp.Il = il;
         rp.nh = nhl;
         rp.dh = dh;
         rp.rot = cfg.rotary_embedding_dim;
+        rp.eps = 1e-5f;
+        return rp;
+    }
+    RowsParams rows_params(int B, int s_max)
+    {
+        RowsParams rp = rows_shape(d_players, x);
+        rp.M = B;
         rp.s_max = s_max;
         rp.tp = cfg.tensor_para_size;
         rp.plan = rplan;
@@ -932,7 +940,6 @@ struct ftcf_gptneox {
         rp.max_input_len = ses.S;
         rp.finished = finished;
         rp.rot_table = rot_table;
-        rp.eps = 1e-5f;
         rp.ts = rows_ts;
         return rp;
     }

@@ -19,57 +19,26 @@
 //   * after the last submit every geometry drains within (requests left + max_batch) * (max_seq_len + 2) steps.
 // Prints one "<case>: ok, ..." line per geometry with the preemptions, the resumes and the resumes into another slot (all > 0);
 // exits non-zero on the first violation.
-#include "batcher_sched.h"
+#include "batcher_sim.h"
 
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <random>
 
-using ftcf::BatcherSched;
-typedef BatcherSched::Kind Kind;
-
-#define CHECK(c, ...)                                                                                                                 \
-    do {                                                                                                                              \
-        if (!(c)) {                                                                                                                   \
-            std::printf("FAIL %s:%d: %s: ", __FILE__, __LINE__, #c);                                                                  \
-            std::printf(__VA_ARGS__);                                                                                                 \
-            std::printf("\n");                                                                                                        \
-            std::exit(1);                                                                                                             \
-        }                                                                                                                             \
-    } while (0)
-
-struct Injected {};  // the fake prompt phase's failure
-
-struct Sim : BatcherSched {
-    static constexpr int END_ID = 0, VOCAB = 14;
-    std::mt19937 rng;
-    int          fail_in = -1;     // the fake prompt phase throws at its fail_in-th point (-1: never)
-    bool         hook_on = false;  // decode steps run between the chunks of the prompt phase
+struct Sim : BatcherSim {
+    static constexpr int VOCAB = 14;
     bool         can_fill = false; // the swap space is smaller than max_batch * max_pages
-    long         steps = 0, admissions = 0, failed = 0, exhausted = 0, resumed_elsewhere = 0, decodes_in_hook = 0, grown = 0;
+    long         steps = 0, admissions = 0, failed = 0, exhausted = 0, resumed_elsewhere = 0, grown = 0;
     std::set<long>      gone;      // ids that finished or were cancelled
     std::map<long, int> left_slot; // a swapped-out request's old slot
     std::vector<std::vector<int>> dev_pt;  // the device's page table rows of ordinary slots, as the device halves leave them
     std::vector<long>   pending;   // requests of a chunked_one plan that are not in yet (they are in the plan, not in the queue)
 
-    Sim(int pages, int mb, int p, bool cache, int swap_pages, unsigned seed): rng(seed)
+    Sim(int pages, int mb, int p, bool cache, int swap_pages, unsigned seed): BatcherSim(seed, 7)
     {
         init_sched(mb, p, pages, 4 * p, VOCAB, cache);
         init_overcommit(swap_pages);
         dev_pt.assign(mb, {});
         can_fill      = swap_total < mb * max_pages;
         prefill_chunk = p;  // a prompt of more than one page is "long"
-    }
-    int rnd(int lo, int hi)  // [lo, hi]
-    {
-        return std::uniform_int_distribution<int>(lo, hi)(rng);
-    }
-    void point()
-    {
-        if (fail_in >= 0 && fail_in-- == 0) {
-            throw Injected{};
-        }
     }
     static uint64_t draws_of(long id)
     {
@@ -79,8 +48,7 @@ struct Sim : BatcherSched {
     // ---- the invariants ------------------------------------------------------------------------------------------------
     void check_all(const char* after)
     {
-        std::vector<int> holders(num_pages, 0);
-        std::set<int>    by_requests;
+        check_pages(after);
         std::map<long, int> places;  // id -> places it is in
         for (const Request& r : waiting) {
             places[r.id]++;
@@ -97,49 +65,19 @@ struct Sim : BatcherSched {
             CHECK(!w.host.empty() && w.draws == draws_of(w.s.id), "after %s: request %ld lost its device state", after, w.s.id);
         }
         for (const Slot& s : slots) {
-            CHECK(s.active || s.pages.empty(), "after %s: a free slot holds pages", after);
             if (s.active && s.group < 0) {
                 places[s.id]++;
                 CHECK(dev_pt[&s - slots.data()] == s.pages, "after %s: the device's page table row of slot %d is not the slot's page list", after,
                       (int)(&s - slots.data()));
             }
-            for (int pg : s.pages) {
-                holders[pg]++;
-                by_requests.insert(pg);
-            }
         }
         for (const auto& kv : groups) {
-            const BeamGroup& g = kv.second;
-            places[g.id]++;
-            CHECK(kv.first == g.si && (int)g.lists.size() == g.K, "after %s: a malformed group", after);
-            for (int k = 0; k < g.K; k++) {
-                const Slot& s = slots[g.si + k];
-                CHECK(s.active && s.group == g.si && s.id == g.id, "after %s: group %d's slot %d is not its own", after, g.si, g.si + k);
-                for (int pg : g.lists[k]) {
-                    holders[pg]++;
-                    by_requests.insert(pg);
-                }
-            }
+            places[kv.second.id]++;
         }
         for (long id = 1; id < next_id; id++) {
             const int n = places.count(id) ? places[id] : 0;
             CHECK(n + (int)gone.count(id) == 1, "after %s: request %ld is in %d places and %s", after, id, n, gone.count(id) ? "gone" : "not gone");
         }
-        for (const auto& n : pindex.nodes) {
-            if (n.live && n.page >= 0) {
-                holders[n.page]++;
-            }
-        }
-        std::vector<int> in_free(num_pages, 0);
-        for (int pg : free_pages) {
-            CHECK(pg >= 0 && pg < num_pages && ++in_free[pg] == 1, "after %s: page %d is twice in the free list", after, pg);
-        }
-        for (int pg = 0; pg < num_pages; pg++) {
-            CHECK(page_ref[pg] == holders[pg], "after %s: page %d has %d references and %d holders", after, pg, page_ref[pg], holders[pg]);
-            CHECK(in_free[pg] == (holders[pg] == 0 ? 1 : 0), "after %s: page %d, %d holders, free list %d", after, pg, holders[pg], in_free[pg]);
-        }
-        CHECK(reserved_pages() + (int)by_requests.size() <= num_pages, "after %s: %d pages promised and %zu held of %d", after,
-              reserved_pages(), by_requests.size(), num_pages);
         // the swap space
         std::vector<int> host_holders(swap_total, 0), host_in_free(swap_total, 0);
         for (const Swapped& w : swapped) {
@@ -155,14 +93,6 @@ struct Sim : BatcherSched {
                   host_in_free[hp]);
         }
         CHECK(inflight_reserve == 0, "after %s: a promise to an admission that is not in flight", after);
-    }
-    std::vector<long> queue_ids() const
-    {
-        std::vector<long> ids;
-        for (const Request& r : waiting) {
-            ids.push_back(r.id);
-        }
-        return ids;
     }
 
     // ---- the fake device side --------------------------------------------------------------------------------------------
@@ -196,15 +126,7 @@ struct Sim : BatcherSched {
         resumed_elsewhere += left_slot.at(w.s.id) != si ? 1 : 0;
         dev_pt[si] = pages;
     }
-    void hook()  // run_admission's chunk hook
-    {
-        if (hook_on && any_active()) {
-            refresh_host_flags();
-            decode();
-            decodes_in_hook++;
-        }
-    }
-    void admit(const std::vector<int>& sis, const std::vector<Request>& rs, const int n, const std::vector<int>* hit)
+    void admit(const std::vector<int>& sis, const std::vector<Request>& rs, const int n, const std::vector<int>* hit) override
     {
         deferred.clear();
         for (int i = 0; i < n; i++) {
@@ -226,41 +148,12 @@ struct Sim : BatcherSched {
             point();
         }
     }
-    void finish_or_append(BeamGroup& g, const std::vector<uint8_t>& fin)
+    void group_finished(const long id) override
     {
-        bool all_fin = true;
-        for (int k = 0; k < g.K; k++) {
-            all_fin &= fin[k] != 0;
-        }
-        if (all_fin || g.generated >= g.max_new) {
-            gone.insert(g.id);
-            drop_group(g.si);  // finish_group
-        }
-        else {
-            take_append_pages(g, g.n + g.generated - 1, fin);  // prepare_append
-        }
-    }
-    std::vector<uint8_t> random_fin(int K)
-    {
-        std::vector<uint8_t> fin(K);
-        for (auto& f : fin) {
-            f = rnd(0, 6) == 0;
-        }
-        return fin;
-    }
-    void admit_beam(const int si, const Request& r)
-    {
-        point();
-        hook();
-        point();
-        BeamGroup& g = open_group(si, r);
-        point();
-        start_group_slots(g);
-        finish_or_append(g, random_fin(g.K));
-        point();
+        gone.insert(id);
     }
     // ftcf_batcher::decode + advance_groups, host side
-    void decode()
+    void decode() override
     {
         grown += grow_slots(
             [this](int si, const std::vector<int>& pages, const std::vector<int>& host, uint64_t& draws, float& cum) {
@@ -283,22 +176,7 @@ struct Sim : BatcherSched {
                 release(s);
             }
         }
-        std::vector<int> leaders;
-        for (const auto& kv : groups) {
-            leaders.push_back(kv.first);
-        }
-        for (const int si : leaders) {
-            BeamGroup&       g = groups.at(si);
-            std::vector<int> parent(g.K);
-            for (int& p : parent) {
-                p = rnd(0, g.K - 1);
-            }
-            reparent_group(g, parent);
-            for (int k = 0; k < g.K; k++) {
-                slots[si + k].len += 1;
-            }
-            finish_or_append(g, random_fin(g.K));
-        }
+        decode_groups();
     }
     static bool is_exhausted(const ftcf::Error& e)
     {
@@ -363,16 +241,9 @@ struct Sim : BatcherSched {
             for (const Request& r : a.requests) {
                 ids.push_back(r.id);
             }
-            fail_in = inject ? rnd(0, 5) : -1;
-            hook_on = a.install_hook;
             bool ok = true;
             try {
-                if (kind == Kind::beam) {
-                    admit_beam(a.slots[0], a.requests[0]);
-                }
-                else {
-                    admit(a.slots, a.requests, n, kind == Kind::hit ? &a.hit : nullptr);
-                }
+                prompt_phase(a, n, inject);
             }
             catch (const Injected&) {
                 ok = false;
@@ -381,21 +252,14 @@ struct Sim : BatcherSched {
                 on_exhausted(e);
                 ok = false;
             }
-            hook_on = false;
-            fail_in = -1;
             pending.assign(ids.begin() + n, ids.end());
             if (!ok) {
                 pending.clear();
-                rollback(
-                    a, [this](int si) { release(slots[si]); }, [this](int si) { drop_group(si); });
+                roll_back(a, sis, ids[0], std::vector<long>(before.begin() + done, before.end()));
                 for (const long id : ids) {
                     gone.erase(id);  // (a request that ended with its first token is back in the queue)
                 }
                 failed++;
-                for (const int si : sis) {
-                    CHECK(!slots[si].active, "slot %d of a failed admission is active", si);
-                }
-                CHECK(queue_ids() == std::vector<long>(before.begin() + done, before.end()), "a failed admission reordered the queue");
                 check_all("a failed admission");
                 return;
             }

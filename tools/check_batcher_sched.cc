@@ -12,118 +12,21 @@
 //   * take_page never meets an empty pool when planning said the admission fits.
 // Prints one "<case>: ok, ..." line per geometry with the admissions and injected failures of every kind; exits non-zero on the
 // first violation.
-#include "batcher_sched.h"
+#include "batcher_sim.h"
 
-#include <cstdio>
-#include <cstdlib>
-#include <random>
+struct Sim : BatcherSim {
+    static constexpr int VOCAB = 6;
+    long admitted[5] = {0, 0, 0, 0, 0}, failed[5] = {0, 0, 0, 0, 0}, steps = 0;
 
-using ftcf::BatcherSched;
-typedef BatcherSched::Kind Kind;
-
-#define CHECK(c, ...)                                                                                                                 \
-    do {                                                                                                                              \
-        if (!(c)) {                                                                                                                   \
-            std::printf("FAIL %s:%d: %s: ", __FILE__, __LINE__, #c);                                                                  \
-            std::printf(__VA_ARGS__);                                                                                                 \
-            std::printf("\n");                                                                                                        \
-            std::exit(1);                                                                                                             \
-        }                                                                                                                             \
-    } while (0)
-
-struct Injected {};  // the fake prompt phase's failure
-
-struct Sim : BatcherSched {
-    static constexpr int END_ID = 0, VOCAB = 6;
-    std::mt19937 rng;
-    int          fail_in = -1;     // the fake prompt phase throws at its fail_in-th point (-1: never)
-    bool         hook_on = false;  // decode steps run between the chunks of the prompt phase
-    long         admitted[5] = {0, 0, 0, 0, 0}, failed[5] = {0, 0, 0, 0, 0}, steps = 0, decodes_in_hook = 0;
-
-    Sim(int pages, int mb, int p, bool cache, unsigned seed): rng(seed)
+    Sim(int pages, int mb, int p, bool cache, unsigned seed): BatcherSim(seed, 5)
     {
         init_sched(mb, p, pages, 4 * p, VOCAB, cache);
         prefill_chunk = p;  // a prompt of more than one page is "long"
     }
-    int rnd(int lo, int hi)  // [lo, hi]
-    {
-        return std::uniform_int_distribution<int>(lo, hi)(rng);
-    }
-    void point()
-    {
-        if (fail_in >= 0 && fail_in-- == 0) {
-            throw Injected{};
-        }
-    }
-
-    // ---- the invariants ------------------------------------------------------------------------------------------------
-    void check_all(const char* after)
-    {
-        std::vector<int> holders(num_pages, 0);
-        std::set<int>    by_requests;
-        for (const Slot& s : slots) {
-            CHECK(s.active || s.pages.empty(), "after %s: a free slot holds pages", after);
-            for (int pg : s.pages) {
-                holders[pg]++;
-                by_requests.insert(pg);
-            }
-        }
-        for (const auto& kv : groups) {
-            const BeamGroup& g = kv.second;
-            CHECK(kv.first == g.si && (int)g.lists.size() == g.K, "after %s: a malformed group", after);
-            for (int k = 0; k < g.K; k++) {
-                const Slot& s = slots[g.si + k];
-                CHECK(s.active && s.group == g.si && s.id == g.id, "after %s: group %d's slot %d is not its own", after, g.si, g.si + k);
-                for (int pg : g.lists[k]) {
-                    holders[pg]++;
-                    by_requests.insert(pg);
-                }
-            }
-        }
-        for (int si = 0; si < max_batch; si++) {
-            const Slot& s = slots[si];
-            if (s.active && s.group >= 0) {
-                auto it = groups.find(s.group);
-                CHECK(it != groups.end() && si >= it->second.si && si < it->second.si + it->second.K,
-                      "after %s: slot %d is a beam of a group that does not exist", after, si);
-            }
-        }
-        for (const auto& n : pindex.nodes) {
-            if (n.live && n.page >= 0) {
-                holders[n.page]++;
-            }
-        }
-        std::vector<int> in_free(num_pages, 0);
-        for (int pg : free_pages) {
-            CHECK(pg >= 0 && pg < num_pages && ++in_free[pg] == 1, "after %s: page %d is twice in the free list", after, pg);
-        }
-        for (int pg = 0; pg < num_pages; pg++) {
-            CHECK(page_ref[pg] == holders[pg], "after %s: page %d has %d references and %d holders", after, pg, page_ref[pg], holders[pg]);
-            CHECK(in_free[pg] == (holders[pg] == 0 ? 1 : 0), "after %s: page %d, %d holders, free list %d", after, pg, holders[pg], in_free[pg]);
-        }
-        CHECK(reserved_pages() + (int)by_requests.size() <= num_pages, "after %s: %d pages promised and %zu held of %d", after,
-              reserved_pages(), by_requests.size(), num_pages);
-    }
-    std::vector<long> queue_ids() const
-    {
-        std::vector<long> ids;
-        for (const Request& r : waiting) {
-            ids.push_back(r.id);
-        }
-        return ids;
-    }
 
     // ---- the fake device side --------------------------------------------------------------------------------------------
-    void hook()  // run_admission's chunk hook
-    {
-        if (hook_on && any_active()) {
-            refresh_host_flags();
-            decode();
-            decodes_in_hook++;
-        }
-    }
     // ftcf_batcher::admit: pages of every slot, the prompt phase (chunks, decode steps between them), first tokens
-    void admit(const std::vector<int>& sis, const std::vector<Request>& rs, const int n, const std::vector<int>* hit)
+    void admit(const std::vector<int>& sis, const std::vector<Request>& rs, const int n, const std::vector<int>* hit) override
     {
         deferred.clear();
         for (int i = 0; i < n; i++) {
@@ -140,41 +43,8 @@ struct Sim : BatcherSched {
             point();
         }
     }
-    void finish_or_append(BeamGroup& g, const std::vector<uint8_t>& fin)
-    {
-        bool all_fin = true;
-        for (int k = 0; k < g.K; k++) {
-            all_fin &= fin[k] != 0;
-        }
-        if (all_fin || g.generated >= g.max_new) {
-            drop_group(g.si);  // finish_group
-        }
-        else {
-            take_append_pages(g, g.n + g.generated - 1, fin);  // prepare_append
-        }
-    }
-    std::vector<uint8_t> random_fin(int K)
-    {
-        std::vector<uint8_t> fin(K);
-        for (auto& f : fin) {
-            f = rnd(0, 4) == 0;
-        }
-        return fin;
-    }
-    // ftcf_batcher::admit_beam: the prompt phase first, then the group and its shared pages, the beams' own pages
-    void admit_beam(const int si, const Request& r)
-    {
-        point();
-        hook();
-        point();
-        BeamGroup& g = open_group(si, r);
-        point();
-        start_group_slots(g);
-        finish_or_append(g, random_fin(g.K));
-        point();
-    }
     // ftcf_batcher::decode + advance_groups, host side
-    void decode()
+    void decode() override
     {
         for (Slot& s : slots) {
             if (!s.active || s.group >= 0) {
@@ -188,22 +58,7 @@ struct Sim : BatcherSched {
                 release(s);
             }
         }
-        std::vector<int> leaders;
-        for (const auto& kv : groups) {
-            leaders.push_back(kv.first);
-        }
-        for (const int si : leaders) {
-            BeamGroup&       g = groups.at(si);
-            std::vector<int> parent(g.K);
-            for (int& p : parent) {
-                p = rnd(0, g.K - 1);
-            }
-            reparent_group(g, parent);
-            for (int k = 0; k < g.K; k++) {
-                slots[si + k].len += 1;
-            }
-            finish_or_append(g, random_fin(g.K));
-        }
+        decode_groups();
     }
     // ftcf_batcher::step / run_admission
     void step(const bool inject)
@@ -212,7 +67,7 @@ struct Sim : BatcherSched {
         const bool any = any_active();
         if (any) {
             decode();
-            check_all("a decode step");
+            check_pages("a decode step");
         }
         const std::vector<long> before = queue_ids();
         Admission               a      = plan_admission(any);
@@ -233,40 +88,21 @@ struct Sim : BatcherSched {
             const std::vector<int> sis  = a.slots;
             const long             id   = a.requests[0].id;
             const int              n    = kind == Kind::chunked_one ? 1 : (int)a.requests.size();
-            fail_in = inject ? rnd(0, 5) : -1;
-            hook_on = a.install_hook;
             try {
-                if (kind == Kind::beam) {
-                    admit_beam(a.slots[0], a.requests[0]);
-                }
-                else {
-                    admit(a.slots, a.requests, n, kind == Kind::hit ? &a.hit : nullptr);
-                }
+                prompt_phase(a, n, inject);
             }
             catch (const Injected&) {
-                hook_on = false;
-                fail_in = -1;
-                rollback(
-                    a, [this](int si) { release(slots[si]); }, [this](int si) { drop_group(si); });
+                roll_back(a, sis, id, std::vector<long>(before.begin() + done, before.end()));
                 failed[(int)kind]++;
-                for (const int si : sis) {
-                    CHECK(!slots[si].active, "slot %d of a failed admission is active", si);
-                }
-                for (const auto& kv : groups) {
-                    CHECK(kv.second.id != id, "the group of a failed beam admission exists");
-                }
-                CHECK(queue_ids() == std::vector<long>(before.begin() + done, before.end()), "a failed admission reordered the queue");
-                check_all("a failed admission");
+                check_pages("a failed admission");
                 return;  // (the exception leaves step(): no refresh_host_flags)
             }
-            hook_on = false;
-            fail_in = -1;
             if (kind != Kind::beam) {
                 commit(a.slots, a.requests, n, (int)a.hit.size() * P);
             }
             admitted[(int)kind]++;
             done += n;
-            check_all("an admission");
+            check_pages("an admission");
         } while (a.kind == Kind::chunked_one && next_chunked(a));
         refresh_host_flags();
     }
@@ -330,18 +166,18 @@ static void run_case(const char* name, int pages, int mb, int p, bool cache, uns
             const int what = sim.rnd(0, 99);
             if (what < 40) {
                 sim.submit_random();
-                sim.check_all("submit");
+                sim.check_pages("submit");
             }
             else if (what < 92) {
                 sim.step(sim.rnd(0, 3) == 0);
             }
             else if (what < 98) {
                 sim.cancel_random();
-                sim.check_all("cancel");
+                sim.check_pages("cancel");
             }
             else {
                 sim.clear_prefix_cache();
-                sim.check_all("clear_prefix_cache");
+                sim.check_pages("clear_prefix_cache");
             }
         }
         // drain: everything leaves, the pool has all its pages back
@@ -350,7 +186,7 @@ static void run_case(const char* name, int pages, int mb, int p, bool cache, uns
             sim.step(false);
         }
         sim.clear_prefix_cache();
-        sim.check_all("the drain");
+        sim.check_pages("the drain");
         CHECK(!sim.any_active() && (int)sim.free_pages.size() == pages, "%zu of %d pages are back", sim.free_pages.size(), pages);
     }
     catch (const ftcf::Error& e) {
