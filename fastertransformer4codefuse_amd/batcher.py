@@ -7,6 +7,8 @@
     cb.submit(prompt_ids, 128, logit_bias={id: -inf}, bad_words=[[a, b]], presence_penalty=.5, frequency_penalty=.2,
               min_new_tokens=8)                              # per-request logit processors
     cb.set_token_mask(rid, allowed_ids)                      # the next tokens come from this set (grammar-constrained decoding)
+    rids = cb.submit_n(prompt_ids, 128, n=8, top_k=40, seed=1) # 8 samples of one prompt from ONE prompt phase (seed + i each);
+                                                             # the prompt's full pages are shared (fork_stats())
     bid = cb.submit_beam(prompt_ids, 128, beam_width=4)      # beam search: one event (bid, -1, True), then cb.beam_result(bid)
     ContinuousBatcher(op, ..., prefix_cache=True)             # reuse the K/V pages of shared prompt prefixes (prefix_stats())
     ContinuousBatcher(op, ..., overcommit=True, swap_pages=0) # pages on demand, the latest arrival swapped to host memory when
@@ -146,6 +148,33 @@ class ContinuousBatcher:
             C.c_float(temperature), C.c_float(repetition_penalty), C.c_ulonglong(int(seed)),
             sw.ctypes.data_as(C.POINTER(C.c_int)) if sw is not None else None, int(sw_len), C.byref(rid)))
         return int(rid.value)
+
+    def submit_n(self, prompt_ids, max_new_tokens, n, top_k=0, top_p=0.0, temperature=1.0, seed=0, repetition_penalty=1.0,
+                 stop_words=None, *, logit_bias=None, bad_words=None, presence_penalty=0.0, frequency_penalty=0.0, min_new_tokens=0):
+        """n samples of one prompt (ftcf_batcher_submit_n): ONE fork request, the list of its n request ids.  Sibling i is the
+        request submit() with seed + i would be and produces exactly its tokens; the prompt runs through the model once and its
+        full pages are shared (fork_stats()).  The other arguments are submit()'s.  From its first token on a sibling is an
+        ordinary request (events, cancel, set_token_mask, ...); while the fork waits, cancel(id) drops that sibling and
+        set_token_mask(id, ...) sets that sibling's own mask."""
+        opts, keep = pack_logit_options(logit_bias, bad_words, presence_penalty, frequency_penalty, min_new_tokens)
+        ids = np.ascontiguousarray(prompt_ids, dtype=np.int32).reshape(-1)
+        n = int(n)
+        rids = (C.c_long * max(n, 1))()
+        sw = _word_list(stop_words) if stop_words else None
+        capi.check(capi.lib().ftcf_batcher_submit_n(
+            self._h, ids.ctypes.data_as(C.POINTER(C.c_int)), int(ids.size), int(max_new_tokens), int(top_k), C.c_float(top_p),
+            C.c_float(temperature), C.c_float(repetition_penalty), C.c_ulonglong(int(seed) % (1 << 64)),
+            sw.ctypes.data_as(C.POINTER(C.c_int)) if sw is not None else None, int(sw.shape[1]) if sw is not None else 0,
+            C.byref(opts) if opts is not None else None, n, rids))
+        del keep  # (the call copies the arrays)
+        return [int(rids[i]) for i in range(n)]
+
+    def fork_stats(self):
+        """Counters of submit_n since creation: requests (fork admissions), siblings (the slots they opened), shared_pages (page
+        allocations sharing saved) and prompt_tokens_computed (what their prompt phases ran: one prompt per fork, less its hit)."""
+        r, s, p, t = C.c_long(0), C.c_long(0), C.c_long(0), C.c_long(0)
+        capi.check(capi.lib().ftcf_batcher_fork_stats(self._h, C.byref(r), C.byref(s), C.byref(p), C.byref(t)))
+        return {"requests": r.value, "siblings": s.value, "shared_pages": p.value, "prompt_tokens_computed": t.value}
 
     def set_token_mask(self, request_id, allowed):
         """The allowed-token mask of a waiting or running request (ftcf_batcher_set_token_mask): every token sampled for it from

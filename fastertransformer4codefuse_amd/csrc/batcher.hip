@@ -31,6 +31,9 @@
 // the pool runs dry the latest arrival among the running ordinary requests is swapped out -- k_pages_pack into a staging buffer,
 // a linear copy to pinned host pages -- and resumes later in any free slot on fresh pages (the reverse with k_pages_unpack), its
 // device state uploaded by the function an admission uses (upload_slot_state).  Beam groups are never swapped.
+// Fork requests (ftcf_batcher_submit_n; admit_fork): n samples of one prompt from ONE prompt phase -- the prompt's
+// full pages shared by reference, k_batcher_fanout for the logits row and the tail rows, the first tokens drawn by the decode
+// step's own logit and sampling stages; from then on n ordinary sequences.
 // ---------------------------------------------------------------------------------------------------------------
 __global__ void k_batcher_embed(f16* out, const f16* table, const int* tok, int H)
 {
@@ -80,6 +83,60 @@ __global__ void k_batcher_copy_pages(f16* kpool, f16* vpool, const int* pairs, s
     u32x4*       dp = reinterpret_cast<u32x4*>(pool + (size_t)blockIdx.y * pool_layer_elems + (size_t)dst * page_elems);
     for (size_t i = threadIdx.x; i < page_elems / 8; i += blockDim.x) {
         dp[i] = sp[i];
+    }
+}
+// A fork admission (ftcf_batcher_submit_n: n siblings of one prompt), ONE launch.  fork = {slot of sibling i}[n], then {tail
+// page of sibling i}[n]: the first page of its own, which receives the prompt's `tail` = len % P last rows.
+//   blockIdx.y == 0: the prompt's last-row logits `src` [V] into the n sibling rows of the step's logits buffer.  A row starts at
+//     element slot * V: 16-byte stores from the row's first aligned element on, scalar elements before it and behind the last whole
+//     quad (V = 97); the loads are 16 bytes too where V % 4 == 0 keeps source and row aligned alike.
+//   blockIdx.y == 1 + ((j - 1) * L + l) * 2 + kv: layer l, K | V, the LIVE rows [0, tail) of every head of sibling 0's tail page
+//     (written by the scatter from the engine's cache) into sibling j's.  A page is [nh][P][dh]: a head's live rows are ONE
+//     contiguous run of tail * dh fp16 (dh a multiple of 8: 16-byte pieces), one wave per run; the rest of the fresh page stays
+//     untouched.  tail == 0: the launch has no such blocks.
+__global__ __launch_bounds__(256) void k_batcher_fanout(float* logits, const float* src, int V, f16* kpool, f16* vpool, const int* fork,
+                                                        int n, int L, int nh, int P, int dh, int tail, size_t pool_layer_elems)
+{
+    if (blockIdx.y == 0) {
+        const int gtid = blockIdx.x * blockDim.x + threadIdx.x, gsize = gridDim.x * blockDim.x;
+        for (int i = 0; i < n; i++) {
+            const size_t o    = (size_t)fork[i] * V;
+            float*       d    = logits + o;
+            const int    head = min(V, (int)((4 - (o & 3)) & 3)), nq = (V - head) >> 2;
+            for (int q = gtid; q < nq; q += gsize) {
+                const float* s = src + head + 4 * q;
+                f32x4        v;
+                if (head == 0) {
+                    v = *reinterpret_cast<const f32x4*>(s);
+                }
+                else {
+                    v = f32x4{s[0], s[1], s[2], s[3]};
+                }
+                *reinterpret_cast<f32x4*>(d + head + 4 * q) = v;
+            }
+            if (blockIdx.x == 0) {
+                for (int t = threadIdx.x; t < head; t += blockDim.x) {
+                    d[t] = src[t];
+                }
+                for (int t = head + 4 * nq + threadIdx.x; t < V; t += blockDim.x) {
+                    d[t] = src[t];
+                }
+            }
+        }
+        return;
+    }
+    const int    y = blockIdx.y - 1, kv = y & 1, l = (y >> 1) % L, j = 1 + (y >> 1) / L;
+    const int    lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
+    const size_t page_elems = (size_t)nh * P * dh;
+    f16*         pool = (kv ? vpool : kpool) + (size_t)l * pool_layer_elems;
+    const u32x4* sp = reinterpret_cast<const u32x4*>(pool + (size_t)fork[n] * page_elems);
+    u32x4*       dp = reinterpret_cast<u32x4*>(pool + (size_t)fork[n + j] * page_elems);
+    const int    run = tail * dh / 8;  // 16-byte pieces of one head's live rows
+    for (int h = blockIdx.x * waves + wave; h < nh; h += gridDim.x * waves) {
+        const size_t ho = (size_t)h * P * dh / 8;
+        for (int i = lane; i < run; i += 64) {
+            dp[ho + i] = sp[ho + i];
+        }
     }
 }
 // the sampling kernels' view of `finished`: the rows of beam groups are not theirs (merge = 0: make the view, 1: take the
@@ -186,6 +243,13 @@ struct ftcf_batcher : BatcherSched {
     };
     LogitRows lp_slots, lp_adm;
     long      logit_launches = 0;  // stages enqueued so far (decode steps and admissions)
+    // fork admissions (admit_fork): the prompt's last-row logits as the LM head left them [V], k_batcher_fanout's {slots, tail
+    // pages}, the draw counters of the rows the fork's sampling launch is not about, and the host sides of the asynchronous copies
+    float*               fork_logits = nullptr;
+    int*                 d_fork = nullptr;
+    uint64_t*            d_draws_keep = nullptr;
+    std::vector<int>     fork_host;
+    std::vector<uint8_t> fork_view;
     void init_logit_rows(LogitRows& lr, int rows)
     {
         lr.rows          = rows;
@@ -412,6 +476,9 @@ struct ftcf_batcher : BatcherSched {
         samp_ws = dmalloc<char>(sampling_workspace_bytes(max_batch, V), false);
         init_logit_rows(lp_slots, max_batch);
         init_logit_rows(lp_adm, max_batch);
+        fork_logits  = dmalloc<float>((size_t)V);
+        d_fork       = dmalloc<int>(2 * B);
+        d_draws_keep = dmalloc<uint64_t>(B);
         init_rows();
         // (tensor parallel: up to 32 slots as two micro-batches of <= 16 rows with their own split-K regions -- the decode overlap)
         if (max_batch > 4 && (max_batch <= e->SMALLM_MAX_ROWS || (e->cfg.tensor_para_size > 1 && max_batch <= 32))) {
@@ -691,13 +758,15 @@ struct ftcf_batcher : BatcherSched {
         std::vector<float>    topp, temp, rep;
         std::vector<uint64_t> seed;
         bool                  any_lp = false;  // a row has logit processors: the stage runs as the engine's logits hook
+        float*                capture = nullptr;  // a fork's one row: its logits [V] go here before anything touches them
         ftcf_forward_args     a{};
     };
     // the first n of rs into the first n of sis: their pages, the ragged batch on the device, the engine's arguments, the logit
     // rows of the first tokens
     // hit (one request only): the cached pages of its first prompt blocks (pinned here: the slot's page list owns one reference)
+    // take_pages = false (a fork's one row): the slots have their pages already (take_fork_pages)
     void build_admission(AdmitBatch& b, const std::vector<int>& sis, const std::vector<Request>& rs, const int n,
-                         const std::vector<int>* hit, hipStream_t st)
+                         const std::vector<int>* hit, hipStream_t st, const bool take_pages = true)
     {
         int S = 0;
         for (int i = 0; i < n; i++) {
@@ -724,7 +793,9 @@ struct ftcf_batcher : BatcherSched {
             build_word_list(r.stop, sw.data() + (size_t)i * 2 * STOP_LW);
             any_stop |= !r.stop.empty();
             FTCF_CHECK_ARG(!hit || n == 1, "batcher: a prefix hit is admitted alone");
-            take_slot_pages(sis[i], r, hit);
+            if (take_pages) {
+                take_slot_pages(sis[i], r, hit);
+            }
         }
         FTCF_HIP_CHECK(hipMemcpy(d_prompt, ids.data(), ids.size() * 4, hipMemcpyHostToDevice));
         FTCF_HIP_CHECK(hipMemcpy(d_plen, lens.data(), (size_t)n * 4, hipMemcpyHostToDevice));
@@ -776,9 +847,16 @@ struct ftcf_batcher : BatcherSched {
     void prompt_phase(const AdmitBatch& b, const int si0)
     {
         const int  n = b.n, S = b.S, hit_tokens = b.hit_tokens;
-        LogitsHook first_logits(e, b.any_lp ? std::function<void(float*, int, hipStream_t)>([this, n, S](float* lg, int rows, hipStream_t s2) {
+        float* const capture = b.capture;
+        const bool   any_lp  = b.any_lp;
+        LogitsHook first_logits(e, (any_lp || capture) ? std::function<void(float*, int, hipStream_t)>([this, n, S, capture, any_lp](float* lg, int rows, hipStream_t s2) {
             FTCF_CHECK_ARG(rows == n, "batcher: the engine's first step has other rows than the admission");
-            enqueue_logit_stage(lp_adm, true, lg, n, nullptr, d_prompt, 1, S, d_plen, 0, s2);
+            if (capture) {
+                FTCF_HIP_CHECK(hipMemcpyAsync(capture, lg, (size_t)e->V * sizeof(float), hipMemcpyDeviceToDevice, s2));
+            }
+            if (any_lp) {
+                enqueue_logit_stage(lp_adm, true, lg, n, nullptr, d_prompt, 1, S, d_plen, 0, s2);
+            }
         }) : nullptr);
         if (hit_tokens == 0) {
             e->forward(b.a);
@@ -846,6 +924,122 @@ struct ftcf_batcher : BatcherSched {
         build_admission(b, sis, rs, n, hit, e->stream);
         prompt_phase(b, sis[0]);
         install_admitted(b, sis, rs, ev, e->stream);
+    }
+
+    // ---- fork requests (submit_n) ----------------------------------------------------------------------------------------
+    // ONE prompt phase for n siblings (batcher_sched.h: take_fork_pages).  The prompt runs as a batch of one greedy row whose own
+    // token nobody uses; the logits hook keeps its last-row logits.  Sibling 0's pages are filled from the engine's cache as any
+    // admission's; k_batcher_fanout copies the logits into the siblings' rows of the step's logits buffer and the prompt's tail
+    // rows into the other siblings' first own pages.  The n first tokens are then drawn by the stages a decode step runs -- the
+    // logit processors and the sampling kernels over the slots' rows -- with every sibling's slot set up as the plain request
+    // of seed + index BEFORE its first draw: length len - 1 (the engine's own convention: launch_decode_init), history = the
+    // prompt, draw counter 0, cumulative log-probability 0.  Every other row is finished in that launch's view (d_sfin); the top-p
+    // kernel draws for finished rows too, so the draw counters of those rows are put back.
+    void admit_fork(const std::vector<int>& sis, const Request& r, std::vector<Event>& ev, const std::vector<int>* hit)
+    {
+        Range       rg("ftcf.batcher.admit_fork");
+        hipStream_t st = e->stream;
+        const int   n = r.n_samples, S = (int)r.prompt.size(), shared = fork_shared_pages(r), tail = S % P, top_n = want_top;
+        const int   hit_tokens = hit ? (int)hit->size() * P : 0;
+        FTCF_CHECK_ARG(n >= 1 && (int)sis.size() == n && (int)r.sibs.size() == n, "batcher: a fork admission's slots are not its siblings'");
+        deferred.clear();
+        take_fork_pages(sis, r, hit);
+        std::vector<Request> one(1, r);
+        Request&             r0 = one[0];
+        r0.top_k = 0, r0.top_p = 0.f, r0.temperature = 1.f, r0.repetition_penalty = 1.f, r0.seed = 0;
+        r0.stop.clear(), r0.mask.clear(), r0.sibs.clear();
+        r0.lopt = LogitOptions{};
+        AdmitBatch b;
+        b.capture = fork_logits;
+        build_admission(b, sis, one, 1, hit, st, false);
+        prompt_phase(b, sis[0]);  // (host synchronous)
+        // the page table rows; sibling 0's pages from the engine's cache (a hit: the tail's pages only)
+        fork_host.assign(2 * (size_t)n, 0);
+        for (int i = 0; i < n; i++) {
+            const std::vector<int>& pages = slots[sis[i]].pages;
+            FTCF_CHECK_ARG(sis[i] >= 0 && sis[i] < max_batch && (int)pages.size() > shared && (int)pages.size() * P > S,
+                           "batcher: a sibling without a page of its own");
+            for (const int pg : pages) {
+                FTCF_CHECK_ARG(pg >= 0 && pg < num_pages, "batcher: a page outside the pool");
+            }
+            upload_page_rows(sis[i], &pages, 1, st);
+            fork_host[i]     = sis[i];
+            fork_host[n + i] = pages[shared];
+        }
+        const size_t row_kv = (size_t)e->nhl * (S + 1) * e->dh;
+        launch_scatter_kv_to_pages(e->k_cache + (size_t)hit_tokens * e->dh, e->v_cache + (size_t)hit_tokens * e->dh, kpool, vpool,
+                                   pt_row(sis[0]) + hit_tokens / P, e->L, e->nhl, e->dh, S + 1, S - hit_tokens, P, pool_layer_elems, st, row_kv);
+        FTCF_HIP_CHECK(hipMemcpyAsync(d_fork, fork_host.data(), fork_host.size() * 4, hipMemcpyHostToDevice, st));
+        const unsigned gx = (unsigned)std::min(64, std::max((e->V + 1023) / 1024, (e->nhl + 3) / 4));
+        const unsigned gy = 1u + (tail > 0 ? (unsigned)(n - 1) * (unsigned)e->L * 2u : 0u);
+        FTCF_CHECK_ARG(gy <= 65535u && e->dh % 8 == 0, "batcher: a fork of too many siblings and layers for one launch");
+        hipLaunchKernelGGL(k_batcher_fanout, dim3(gx, gy), dim3(256), 0, st, logits, fork_logits, e->V, kpool, vpool, d_fork, n, e->L, e->nhl,
+                           P, e->dh, tail, pool_layer_elems);
+        FTCF_HIP_CHECK(hipGetLastError());
+        // every sibling's slot before its first draw; the launch's view of `finished`; its flags are the siblings' alone
+        FTCF_HIP_CHECK(hipMemcpyAsync(d_draws_keep, d_draws, (size_t)max_batch * 8, hipMemcpyDeviceToDevice, st));
+        fork_view.assign(max_batch, 1);
+        std::fill(lp_slots.flags.begin(), lp_slots.flags.begin() + max_batch, 0);
+        bool any_lp = false;
+        for (int i = 0; i < n; i++) {
+            const Request::Sibling& sb = r.sibs[i];
+            Slot                    t;
+            t.len                = S - 1;
+            t.hist               = r.prompt;
+            t.top_k              = r.top_k;
+            t.top_p              = r.top_p;
+            t.temperature        = r.temperature;
+            t.repetition_penalty = r.repetition_penalty;
+            t.seed               = r.seed + (uint64_t)sb.index;
+            upload_slot_state(sis[i], t, 0, 0.f, st);
+            fork_view[sis[i]] = 0;
+            if (r.lopt.any() || !sb.mask.empty()) {
+                lp_slots.flags[sis[i]] = 1;
+                stage_logit_row(lp_slots, sis[i], &r.lopt, &sb.mask, S, st);
+                any_lp = true;
+            }
+        }
+        FTCF_HIP_CHECK(hipMemcpyAsync(d_sfin, fork_view.data(), (size_t)max_batch, hipMemcpyHostToDevice, st));
+        host_max_top_k       = keff(r.top_k, r.top_p);
+        host_any_top_p       = host_max_top_k == 0 ? 1 : 0;
+        host_max_top_k       = std::max(host_max_top_k, 1);
+        host_any_temperature = r.temperature != 1.f;
+        host_any_repetition  = r.repetition_penalty != 1.f;
+        if (any_lp) {
+            enqueue_logit_stage(lp_slots, true, logits, max_batch, d_sfin, d_hist, max_batch, 1, d_len, 1, st);
+        }
+        SamplingParams sp = sampling_params();
+        sp.finished       = d_sfin;
+        DynamicDecodeLayer{}.forward(sp, st, false);
+        FTCF_HIP_CHECK(hipMemcpyAsync(d_draws, d_draws_keep, (size_t)max_batch * 8, hipMemcpyDeviceToDevice, st));
+        // the first tokens (position len of every slot's history column) with what the step asked for
+        const size_t       B = (size_t)max_batch;
+        std::vector<int>   tok(B), top_ids(B * top_n);
+        std::vector<float> lp(B, NAN), top_lp(B * top_n);
+        FTCF_HIP_CHECK(hipMemcpyAsync(tok.data(), d_hist + (size_t)S * B, B * 4, hipMemcpyDeviceToHost, st));
+        if (want_log_probs) {
+            FTCF_HIP_CHECK(hipMemcpyAsync(lp.data(), d_olp, B * 4, hipMemcpyDeviceToHost, st));
+        }
+        if (top_n > 0) {
+            FTCF_HIP_CHECK(hipMemcpyAsync(top_ids.data(), d_top_ids, top_ids.size() * 4, hipMemcpyDeviceToHost, st));
+            FTCF_HIP_CHECK(hipMemcpyAsync(top_lp.data(), d_top_lp, top_lp.size() * 4, hipMemcpyDeviceToHost, st));
+        }
+        FTCF_HIP_CHECK(hipStreamSynchronize(st));
+        // from here on every sibling is an ordinary sequence: its slot as install_admitted leaves one, n events in sibling order
+        for (int i = 0; i < n; i++) {
+            const int     si = sis[i], first = tok[si];
+            const Request q  = sibling_request(r, r.sibs[i]);
+            FTCF_CHECK_ARG(first >= 0 && first < e->V, "batcher: a sibling's first token is outside the vocabulary");
+            const int done = start_slot(si, q, first, e->cfg.end_id) ? 1 : 0;
+            upload_slot_state(si, slots[si], 1, 0.f, st);
+            ev.push_back(Event{q.id, first, done, lp[si]});
+            cut_top(ev.back(), top_ids, top_lp, si, top_n);
+            if (done) {
+                const uint8_t one8 = 1;
+                FTCF_HIP_CHECK(hipMemcpy(d_fin + si, &one8, 1, hipMemcpyHostToDevice));
+                end_with_first_token(si);
+            }
+        }
     }
 
     // ---- beam groups ------------------------------------------------------------------------------------------------
@@ -1422,7 +1616,7 @@ struct ftcf_batcher : BatcherSched {
     void run_admission(Admission& a, std::vector<Event>& ev)
     {
         std::vector<Event> own, between;
-        const int          n = a.kind == Kind::chunked_one ? 1 : (int)a.requests.size();
+        const int          n = a.kind == Kind::chunked_one ? 1 : (int)a.requests.size();  // (fork: ONE request)
         try {
             if (a.install_hook) {
                 hook_ev          = &between;
@@ -1439,6 +1633,9 @@ struct ftcf_batcher : BatcherSched {
             }
             if (a.kind == Kind::beam) {
                 admit_beam(a.slots[0], a.requests[0], own);
+            }
+            else if (a.kind == Kind::fork) {
+                admit_fork(a.slots, a.requests[0], own, a.hit.empty() ? nullptr : &a.hit);
             }
             else {
                 admit(a.slots, a.requests, n, own, a.kind == Kind::hit ? &a.hit : nullptr);
@@ -1463,7 +1660,10 @@ struct ftcf_batcher : BatcherSched {
         }
         e->prefill_hook = nullptr;
         hook_ev         = nullptr;
-        if (a.kind != Kind::beam) {  // (beam requests neither read nor populate the prefix cache)
+        if (a.kind == Kind::fork) {
+            count_fork(a.requests[0], (int)a.hit.size() * P);
+        }
+        if (a.kind != Kind::beam) {  // (beam requests neither read nor populate the prefix cache; a fork's prompt blocks enter once)
             commit(a.slots, a.requests, n, (int)a.hit.size() * P);
         }
         ev.insert(ev.end(), between.begin(), between.end());
@@ -1618,24 +1818,57 @@ extern "C" int ftcf_batcher_submit_ex(ftcf_batcher_t b, const int* prompt_ids, i
                                 repetition_penalty, stop_words, stop_len);
     });
 }
+// a request's logit processors out of the C struct (NULL: none), checked
+static ftcf_batcher::LogitOptions logit_options_of(ftcf_batcher_t b, const ftcf_logit_options* opts)
+{
+    ftcf_batcher::LogitOptions o;
+    // (a zeroed struct, struct_size included, asks for nothing)
+    const bool zeroed = opts && opts->struct_size == 0 && opts->presence_penalty == 0.f && opts->frequency_penalty == 0.f
+                        && opts->min_new_tokens == 0 && !opts->bias_ids && !opts->bias_values && opts->n_bias == 0
+                        && !opts->bad_words && opts->bad_words_len == 0;
+    if (opts && !zeroed) {
+        FTCF_CHECK_ARG(opts->struct_size == (int)sizeof(ftcf_logit_options), "struct_size is not sizeof(ftcf_logit_options)");
+        o = b->make_logit_options(opts->presence_penalty, opts->frequency_penalty, opts->min_new_tokens, opts->bias_ids,
+                                  opts->bias_values, opts->n_bias, opts->bad_words, opts->bad_words_len);
+    }
+    return o;
+}
 extern "C" int ftcf_batcher_submit_opts(ftcf_batcher_t b, const int* prompt_ids, int prompt_len, int max_new_tokens, int top_k,
                                         float top_p, float temperature, float repetition_penalty, unsigned long long seed,
                                         const int* stop_words, int stop_len, const ftcf_logit_options* opts, long* request_id)
 {
     return guarded([&] {
         FTCF_CHECK_ARG(b && request_id, "NULL argument");
-        ftcf_batcher::LogitOptions o;
-        // (a zeroed struct, struct_size included, asks for nothing)
-        const bool zeroed = opts && opts->struct_size == 0 && opts->presence_penalty == 0.f && opts->frequency_penalty == 0.f
-                            && opts->min_new_tokens == 0 && !opts->bias_ids && !opts->bias_values && opts->n_bias == 0
-                            && !opts->bad_words && opts->bad_words_len == 0;
-        if (opts && !zeroed) {
-            FTCF_CHECK_ARG(opts->struct_size == (int)sizeof(ftcf_logit_options), "struct_size is not sizeof(ftcf_logit_options)");
-            o = b->make_logit_options(opts->presence_penalty, opts->frequency_penalty, opts->min_new_tokens, opts->bias_ids,
-                                      opts->bias_values, opts->n_bias, opts->bad_words, opts->bad_words_len);
-        }
         *request_id = b->submit_opts(prompt_ids, prompt_len, max_new_tokens, top_k, top_p, temperature, (uint64_t)seed,
-                                     repetition_penalty, stop_words, stop_len, std::move(o));
+                                     repetition_penalty, stop_words, stop_len, logit_options_of(b, opts));
+    });
+}
+extern "C" int ftcf_batcher_submit_n(ftcf_batcher_t b, const int* prompt_ids, int prompt_len, int max_new_tokens, int top_k, float top_p,
+                                     float temperature, float repetition_penalty, unsigned long long seed, const int* stop_words,
+                                     int stop_len, const ftcf_logit_options* opts, int n_samples, long* request_ids)
+{
+    return guarded([&] {
+        FTCF_CHECK_ARG(b && request_ids, "NULL argument");
+        b->submit_n(prompt_ids, prompt_len, max_new_tokens, top_k, top_p, temperature, (uint64_t)seed, repetition_penalty, stop_words,
+                    stop_len, logit_options_of(b, opts), n_samples, request_ids);
+    });
+}
+extern "C" int ftcf_batcher_fork_stats(ftcf_batcher_t b, long* requests, long* siblings, long* shared_pages, long* prompt_tokens_computed)
+{
+    return guarded([&] {
+        FTCF_CHECK_ARG(b, "NULL argument");
+        if (requests) {
+            *requests = b->fk_requests;
+        }
+        if (siblings) {
+            *siblings = b->fk_siblings;
+        }
+        if (shared_pages) {
+            *shared_pages = b->fk_shared_pages;
+        }
+        if (prompt_tokens_computed) {
+            *prompt_tokens_computed = b->fk_prompt_tokens;
+        }
     });
 }
 extern "C" int ftcf_batcher_set_token_mask(ftcf_batcher_t b, long request_id, const unsigned* allowed_bits, int n_words)
@@ -1788,12 +2021,8 @@ extern "C" int ftcf_batcher_cancel(ftcf_batcher_t b, long request_id, int* found
     return guarded([&] {
         FTCF_CHECK_ARG(b, "NULL argument");
         int hit = 0;
-        for (auto it = b->waiting.begin(); it != b->waiting.end(); ++it) {
-            if (it->id == request_id) {
-                b->waiting.erase(it);
-                hit = 1;
-                break;
-            }
+        if (b->cancel_waiting(request_id)) {  // (a waiting fork request: the sibling alone)
+            hit = 1;
         }
         if (!hit && b->drop_swapped(request_id)) {  // a swapped-out request: its host pages return
             hit = 1;

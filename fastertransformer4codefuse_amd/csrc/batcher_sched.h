@@ -1,7 +1,8 @@
 // What the continuous batcher (batcher.hip) decides on the host: the request queue, the slots' host
 // fields, page accounting and the admission policy.  Plain C++ (no HIP): tools/check_batcher_sched.cc drives it with a fake
 // prompt phase that fails at seeded points and checks the page accounting, the queue order and the rollbacks.
-// tools/check_batcher_preempt.cc does the same for the overcommit policy (pages on demand, preemption by swap, resume).
+// tools/check_batcher_preempt.cc does the same for the overcommit policy (pages on demand, preemption by swap, resume),
+// tools/check_batcher_fork.cc for fork requests (submit_n: n samples of one prompt, the prompt's full pages shared).
 //
 // ftcf_batcher derives from BatcherSched and adds the device side: buffers, launches and the mirrors of this state on the
 // device (d_fin, d_isbeam, page tables).  Where an operation has a device half the name here is the host half's.
@@ -54,6 +55,19 @@ struct BatcherSched {
         int              min_length = 0;     // beam requests: the end token is held back for this many new tokens
         LogitOptions          lopt;  // ordinary requests: logit processors
         std::vector<unsigned> mask;  // ... and the allowed-token mask set while it waits (empty: none)
+        // a fork request (submit_n): ONE prompt phase, n_samples siblings.  Sibling `index` is the plain request of seed + index
+        // with its own id and mask; `sibs` lists the ones still wanted (a cancelled sibling leaves it); `id` is the first one's.
+        struct Sibling {
+            long                  id;
+            int                   index;
+            std::vector<unsigned> mask;
+        };
+        int                  n_samples = 1;  // == sibs.size() for a fork request
+        std::vector<Sibling> sibs;           // (empty: not a fork request)
+        bool is_fork() const
+        {
+            return !sibs.empty();
+        }
     };
     struct Slot {
         bool             active = false;
@@ -112,14 +126,15 @@ struct BatcherSched {
     //   hit          1 (its cached pages in `hit`) slots ran BEFORE the decode step, the tail is long   its slot             yes
     //   chunked_one  the FIRST of `requests`       slots run NOW                                        all of `slots`       yes
     //   ragged       all, one batch                never                                                all of `slots`       yes
+    //   fork         1, in n_samples free slots    slots ran BEFORE the decode step, the tail is long   all of `slots`       yes
     // ("long": more than prefill_chunk tokens; chunked_one is chosen when slots ran before the decode step and one of the
     // requests is long.)  The requests have left the queue; rollback() puts them back.
-    enum class Kind { none, beam, hit, chunked_one, ragged };
+    enum class Kind { none, beam, hit, chunked_one, ragged, fork };
     struct Admission {
         Kind                 kind = Kind::none;
         std::vector<int>     slots;  // beam: its K slots
         std::vector<Request> requests;
-        std::vector<int>     hit;
+        std::vector<int>     hit;    // hit, fork: the cached pages of the prompt's first blocks
         bool                 install_hook = false;
     };
 
@@ -143,6 +158,9 @@ struct BatcherSched {
     std::vector<int> deferred;
     long             px_lookups = 0, px_prompt_tokens = 0, px_hit_tokens = 0, px_computed_tokens = 0, px_evictions = 0;
     long             next_id = 1;
+    // fork requests (submit_n) since creation: admissions, the siblings they opened, the page allocations sharing saved ((n - 1)
+    // per shared page) and the prompt tokens their prompt phases computed
+    long             fk_requests = 0, fk_siblings = 0, fk_shared_pages = 0, fk_prompt_tokens = 0;
     // host view of the running slots' sampling parameters (refresh_host_flags)
     int                host_max_top_k = 1, host_any_top_p = 0;
     bool               host_any_temperature = false, host_any_repetition = false;
@@ -552,6 +570,126 @@ struct BatcherSched {
         waiting.back().lopt = std::move(opts);
         return id;
     }
+    // ---- fork requests (submit_n): n samples of one prompt from ONE prompt phase -------------------------------------------------
+    // Page accounting of a fork of n siblings over a prompt of S tokens: the S / P full prompt pages are taken once and every
+    // sibling's page list references them; each sibling owns the rest of what the plain request would hold -- its first own page
+    // receives the prompt's S % P tail rows (fork_own_pages: at full length under reservation, ONE page under overcommit).
+    int fork_shared_pages(const Request& r) const
+    {
+        return (int)r.prompt.size() / P;
+    }
+    int fork_own_pages(const Request& r) const
+    {
+        return admission_pages(r) - fork_shared_pages(r);
+    }
+    // ONE request of n siblings at the queue's tail; ids[i] = sibling i's id (consecutive).  Refused: n outside [1, max_batch], a
+    // fork that can never be admitted -- reservation: shared + n * own pages at full length exceed the pool; overcommit: its
+    // admission (shared + n pages) or one sibling at full length does.  n == 1: the plain request.
+    void submit_n(const int* ids, int n, int max_new, int top_k, float top_p, float temperature, uint64_t seed, float repetition_penalty,
+                  const int* stop_words, int stop_len, LogitOptions opts, int n_samples, long* out_ids)
+    {
+        FTCF_CHECK_ARG(out_ids, "NULL argument");
+        FTCF_CHECK_ARG(n_samples >= 1 && n_samples <= max_batch, "n_samples must be in [1, max_batch]");
+        if (n_samples == 1) {
+            out_ids[0] = submit_opts(ids, n, max_new, top_k, top_p, temperature, seed, repetition_penalty, stop_words, stop_len, std::move(opts));
+            return;
+        }
+        FTCF_CHECK_ARG(ids && n >= 1 && max_new >= 1, "empty prompt or max_new_tokens < 1");
+        const int shared = n / P;
+        FTCF_CHECK_ARG(overcommit ? shared + 2 * n_samples - 1 <= num_pages  // (its pages and its watermark, plan_admission)
+                                  : (long)shared + (long)n_samples * (pages_needed(n, max_new) - shared) <= (long)num_pages,
+                       "the fork request needs more pages than the pool has");
+        const long first = next_id;
+        submit_opts(ids, n, max_new, top_k, top_p, temperature, seed, repetition_penalty, stop_words, stop_len, std::move(opts));
+        Request& r  = waiting.back();
+        r.n_samples = n_samples;
+        for (int i = 0; i < n_samples; i++) {
+            r.sibs.push_back(Request::Sibling{first + i, i, {}});
+            out_ids[i] = first + i;
+        }
+        next_id = first + n_samples;
+    }
+    // sibling `sib` of fork request r as the plain request it is from the fork on
+    static Request sibling_request(const Request& r, const Request::Sibling& sib)
+    {
+        Request q   = r;
+        q.id        = sib.id;
+        q.seed      = r.seed + (uint64_t)sib.index;
+        q.mask      = sib.mask;
+        q.n_samples = 1;
+        q.sibs.clear();
+        return q;
+    }
+    // a waiting request leaves (cancel): a plain or beam request as a whole, a fork request's sibling alone -- the last one takes
+    // the request with it; false: no waiting request has this id
+    bool cancel_waiting(const long id)
+    {
+        for (auto it = waiting.begin(); it != waiting.end(); ++it) {
+            if (!it->is_fork()) {
+                if (it->id == id) {
+                    waiting.erase(it);
+                    return true;
+                }
+                continue;
+            }
+            for (auto sb = it->sibs.begin(); sb != it->sibs.end(); ++sb) {
+                if (sb->id == id) {
+                    it->sibs.erase(sb);
+                    it->n_samples = (int)it->sibs.size();
+                    if (it->sibs.empty()) {
+                        waiting.erase(it);
+                    }
+                    else {
+                        it->id = it->sibs.front().id;
+                    }
+                    return true;
+                }
+            }
+        }
+        return false;
+    }
+    // the pages of a fork admission's slots `sis` (one per sibling, in sibling order): the shared ones -- the hit's cached pages
+    // first -- in sibling 0's list, referenced once more by every other sibling's, then each sibling's own.  Every page is in a
+    // slot's list the moment it is taken: a throw half way leaves nothing the rollback's release() does not find.
+    void take_fork_pages(const std::vector<int>& sis, const Request& r, const std::vector<int>* hit)
+    {
+        const int shared = fork_shared_pages(r), own = fork_own_pages(r);
+        for (const int si : sis) {
+            slots[si].pages.clear();
+        }
+        std::vector<int>& first = slots[sis[0]].pages;
+        if (hit) {
+            first = *hit;
+            for (const int pg : *hit) {
+                page_ref[pg]++;
+            }
+            pindex.touch(r.prompt.data(), (int)hit->size());
+        }
+        while ((int)first.size() < shared) {
+            first.push_back(take_page());
+        }
+        for (std::size_t i = 1; i < sis.size(); i++) {
+            std::vector<int>& l = slots[sis[i]].pages;
+            for (int k = 0; k < shared; k++) {
+                l.push_back(first[k]);
+                page_ref[first[k]]++;
+            }
+        }
+        for (const int si : sis) {
+            for (int k = 0; k < own; k++) {
+                slots[si].pages.push_back(take_page());
+            }
+        }
+    }
+    // a fork admission has succeeded (before commit()): its counters
+    void count_fork(const Request& r, const int hit_tokens)
+    {
+        fk_requests++;
+        fk_siblings += r.n_samples;
+        fk_shared_pages += (long)(r.n_samples - 1) * fork_shared_pages(r);
+        fk_prompt_tokens += (long)r.prompt.size() - hit_tokens;
+    }
+
     // the allowed-token mask of a waiting or running request (NULL clears it); the slot's device row follows before its next step
     void set_token_mask(long id, const unsigned* bits, int n_words)
     {
@@ -566,7 +704,13 @@ struct BatcherSched {
             FTCF_CHECK_ARG(std::any_of(m.begin(), m.end(), [](unsigned w) { return w != 0u; }), "token mask: no token of the vocabulary is allowed");
         }
         for (Request& r : waiting) {
-            if (r.id == id) {
+            for (Request::Sibling& sb : r.sibs) {  // (a fork request: the mask is the sibling's own)
+                if (sb.id == id) {
+                    sb.mask = std::move(m);
+                    return;
+                }
+            }
+            if (r.id == id && !r.is_fork()) {
                 FTCF_CHECK_ARG(r.beam_width == 1, "token mask: beam requests take no mask");
                 r.mask = std::move(m);
                 return;
@@ -618,6 +762,7 @@ struct BatcherSched {
     // BEFORE that step (a hit and the choice of chunked_one read it; beam and each chunked_one read what runs now).
     //   * FIFO: nobody overtakes the head of the queue;
     //   * a beam request: alone, K consecutive free slots and the group's whole page budget;
+    //   * a fork request (submit_n): alone, n free slots, its shared pages once and every sibling's own (take_fork_pages);
     //   * a prefix hit: alone, its budget computed with its own hit pages pinned;
     //   * else as many of the queue's head requests as there are free slots and pages: one at a time (chunked_one, see
     //     next_chunked) when slots were running and one of the prompts is long, else as ONE ragged batch.
@@ -658,12 +803,52 @@ struct BatcherSched {
             take_head(a);
             return a;
         }
+        if (waiting.front().is_fork()) {
+            // alone, in n free slots (any n: the siblings are ordinary sequences); the budget with the hit's pages pinned, as a hit's;
+            // overcommit: the watermark the last of n plain requests planned together would leave
+            const Request&   r = waiting.front();
+            const int        n = r.n_samples, S = (int)r.prompt.size();
+            std::vector<int> sis;
+            for (int si = 0; si < max_batch && (int)sis.size() < n; si++) {
+                if (!slots[si].active) {
+                    sis.push_back(si);
+                }
+            }
+            if ((int)sis.size() < n) {
+                return a;
+            }
+            std::vector<int> h;
+            if (prefix_on) {
+                h = pindex.lookup(r.prompt.data(), (S - 1) / P);
+            }
+            for (const int pg : h) {
+                page_ref[pg]++;
+            }
+            const int avail = pages_available();
+            for (const int pg : h) {
+                page_ref[pg]--;
+            }
+            const int need = fork_shared_pages(r) - (int)h.size() + n * fork_own_pages(r);
+            if (avail < need + (overcommit ? running + n - 1 : 0)) {
+                return a;
+            }
+            a.kind         = Kind::fork;
+            a.install_hook = any && prefill_chunk > 0 && S - (int)h.size() * P > prefill_chunk;
+            a.hit          = std::move(h);
+            for (const int si : sis) {
+                slot_topk[si] = keff(r.top_k, r.top_p);
+                slot_temp[si] = r.temperature;
+                a.slots.push_back(si);
+            }
+            take_head(a);
+            return a;
+        }
         for (int si = 0; si < max_batch && !waiting.empty(); si++) {
             if (slots[si].active) {
                 continue;
             }
             const Request& r = waiting.front();
-            if (r.beam_width > 1) {
+            if (r.beam_width > 1 || r.is_fork()) {
                 break;  // (admitted alone, by the next iteration)
             }
             int       need      = admission_pages(r);

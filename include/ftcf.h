@@ -596,7 +596,8 @@ int ftcf_batcher_create(ftcf_gptneox_t engine, int max_batch, int page_tokens, i
  * computed -- and its prompt phase computes only the rest.  Cached pages nobody uses are evicted, least recently used and
  * leaves first, only when an allocation cannot be served from the free list; ftcf_batcher_status's free_pages counts the
  * free list only.  Streams equal those of a cold admission up to fp16 rounding of the prompt phase (token exact unless a
- * near tie).  Requests admitted in the same batch do not share with each other; beam requests neither read nor populate
+ * near tie).  Requests admitted in the same batch do not share with each other (n samples of ONE prompt do, with or without
+ * the cache: ftcf_batcher_submit_n); beam requests neither read nor populate
  * the cache.  Refused (an error, not a silent no-op) for tensor_para_size > 1, fp32 engines, sequential residual and
  * hidden sizes without the dual LayerNorm. */
 int ftcf_batcher_create_ex(ftcf_gptneox_t engine, int max_batch, int page_tokens, int num_pages, int max_seq_len, int prefix_cache,
@@ -682,6 +683,27 @@ int ftcf_batcher_submit_opts(ftcf_batcher_t b, const int* prompt_ids, int prompt
  * changed.  A mask without a bit in [0, V), a wrong n_words, an unknown or finished request and a beam request are
  * FTCF_ERR_INVALID_ARG.  A request whose options and mask leave no token ends with end_id. */
 int ftcf_batcher_set_token_mask(ftcf_batcher_t b, long request_id, const unsigned* allowed_bits, int n_words);
+/* n SAMPLES OF ONE PROMPT (OpenAI's `n`, self-consistency, pass@k): the arguments of ftcf_batcher_submit_opts (opts may be NULL)
+ * queue ONE fork request and return n_samples consecutive ids in request_ids [n_samples].  Sibling i is the request a plain
+ * submission of the same prompt and options with seed + i (mod 2^64) would be -- its draw counter starts at 0, draw 0 gives its
+ * first token -- and produces exactly the tokens that submission produces alone; greedy siblings are identical streams.  The
+ * prompt runs through the model ONCE (one prompt phase of one row, from the hit offset with the prefix cache on); its
+ * floor(prompt_len / page_tokens) full pages are held once and shared by all siblings, each sibling owns the rest of what the
+ * plain request holds (reservation: up to full length; overcommit: one page), the first of which receives the prompt's
+ * prompt_len % page_tokens last rows.  The request is admitted alone, into any n_samples free slots; with sequences running, a
+ * long prompt is prefilled in chunks as a single request's is.  From the admission on a sibling is an ordinary request in every
+ * respect: own events and callback calls (the admission reports n_samples events in sibling order), cancel, token mask, stop
+ * words, logit processors, log-probabilities, swap-out and resume.  While the request waits the ids are valid already:
+ * ftcf_batcher_cancel of one shrinks the fork (the last one removes it), ftcf_batcher_set_token_mask sets that sibling's own mask,
+ * which governs its first token.  n_samples == 1 is exactly ftcf_batcher_submit_opts.  FTCF_ERR_INVALID_ARG, nothing queued:
+ * n_samples < 1 or > max_batch, or a fork that cannot fit the pool alone -- shared + n_samples * own pages at full length
+ * (overcommit: its admission's pages and watermark, shared + 2 n_samples - 1, and one sibling at full length). */
+int ftcf_batcher_submit_n(ftcf_batcher_t b, const int* prompt_ids, int prompt_len, int max_new_tokens, int top_k, float top_p,
+                          float temperature, float repetition_penalty, unsigned long long seed, const int* stop_words, int stop_len,
+                          const ftcf_logit_options* opts, int n_samples, long* request_ids);
+/* Fork counters since creation (any pointer may be NULL): fork admissions, the siblings they opened, the page allocations
+ * sharing saved (n_samples - 1 per shared page) and the prompt tokens their prompt phases computed (one prompt's, less its hit). */
+int ftcf_batcher_fork_stats(ftcf_batcher_t b, long* requests, long* siblings, long* shared_pages, long* prompt_tokens_computed);
 /* A beam-search request (GptNeoXOp.forward with beam_width > 1: OnlineBeamSearchLayer semantics, the engine's own beam kernels):
  * it occupies `beam_width` consecutive slots, its beams share the prompt's pages and every page they have in common (copy on
  * write).  ftcf_batcher_step reports ONE event for it, when it has finished: token = -1, finished = 1; the hypotheses are
