@@ -131,15 +131,113 @@ __device__ __forceinline__ u64 ld_granule(const u64* g)
 constexpr int MMHA_MAX_SPLIT = 16;
 constexpr int MMHA_SPIN_LIMIT = 1 << 22;  // bounded: a protocol bug must not hang the GPU
 
-// Split `sp` of (row b, head h): computes the un-normalised partial (max, sum, out[DH]) over its key range and
-// publishes it as granules.  Latency chain: ONE round trip for {finished, seq_len, step, q, bias, K rows, V rows}
-// (the K/V rows of the whole fixed chunk are requested before tlength is known and masked afterwards), then math.
-// BEAMS (beam search, beam_width > 1): the key / value of time t < tlength is read from the row the cache indirection
+// the score of one 16-byte piece: four packed dot2 in element order, fp32 accumulate (MMHA_USE_FP32_ACUM_FOR_FMA)
+__device__ __forceinline__ float dot8(const f16x8 q, const f16x8 k, float a)
+{
+    a = dot2(f16x2{q[0], q[1]}, f16x2{k[0], k[1]}, a);
+    a = dot2(f16x2{q[2], q[3]}, f16x2{k[2], k[3]}, a);
+    a = dot2(f16x2{q[4], q[5]}, f16x2{k[4], k[5]}, a);
+    a = dot2(f16x2{q[6], q[7]}, f16x2{k[6], k[7]}, a);
+    return a;
+}
+
+// LDS of one partial: q, new k, new v [3][DH] halves; 4 wave maxima + 4 wave sums; the waves' outputs [4][DH]; the scores
+struct MmhaLds {
+    f16*   qkv;
+    float *red, *out, *score;
+};
+
+// Key-row addressing of mmha_partial: what differs between the ways of finding a key row, and nothing else.
+//   k_row / v_row(t)  the cached row of time t;  k_new / v_new(tl)  where the new row is appended
+//   length / finished / rotary_pos   of the row
+//   EARLY_ROWS   rows up to s_max may be requested before the length is known (the all-in-registers form)
+//   lds(smem)    where the partial's LDS arrays are (the paged kernel keeps its page table among them)
+// Dense: the row's own cache line [B, nh, s_max, dh].
+template<int DH>
+struct KvDense {
+    static constexpr bool EARLY_ROWS = true;
+    const MmhaParams&     p;
+    const int             b, h;
+    const f16 *           kc, *vc;
+    __device__ __forceinline__ KvDense(const MmhaParams& p_, const int b_, const int h_):
+        KvDense(p_, b_, h_, ((size_t)b_ * p_.nh + h_) * p_.s_max * DH)
+    {
+    }
+    // (own: the offset of (b, h)'s cache line, one value for both caches)
+    __device__ __forceinline__ KvDense(const MmhaParams& p_, const int b_, const int h_, const size_t own):
+        p(p_), b(b_), h(h_), kc(p_.k_cache + own), vc(p_.v_cache + own)
+    {
+    }
+    __device__ __forceinline__ const f16* k_row(const int t) const { return kc + (size_t)t * DH; }
+    __device__ __forceinline__ const f16* v_row(const int t) const { return vc + (size_t)t * DH; }
+    __device__ __forceinline__ f16* k_new(const int tl) const { return p.k_cache + (((size_t)b * p.nh + h) * p.s_max + tl) * DH; }
+    __device__ __forceinline__ f16* v_new(const int tl) const { return p.v_cache + (((size_t)b * p.nh + h) * p.s_max + tl) * DH; }
+    __device__ __forceinline__ bool finished() const { return p.finished && p.finished[b]; }
+    __device__ __forceinline__ int  length() const { return p.seq_len[b]; }  // tlength: the new token goes to index tl
+    __device__ __forceinline__ int  rotary_pos(const int step) const { return (step - 1) - (p.pad_count ? p.pad_count[b] : 0); }  // :1303,:1343-1344
+    __device__ __forceinline__ MmhaLds lds(char* smem) const  // mmha_smem_bytes: [q k v][red 8][out 4 * DH][score chunk]
+    {
+        f16*   qkv = reinterpret_cast<f16*>(smem);
+        float* red = reinterpret_cast<float*>(qkv + 3 * DH);
+        return MmhaLds{qkv, red, red + 8, red + 8 + 4 * DH};
+    }
+};
+// Beams (beam search, beam_width > 1): the key / value of time t < tlength is read from the row the cache indirection
 // names, (b / beam_width) * beam_width + cache_indir[b][t] (decoder_masked_multihead_attention_template.hpp:1290-1296,
 // :1509-1512, :1733-1736); the new key / value always goes to the row's own cache line.
-template<int DH, bool BEAMS = false>
-__device__ __forceinline__ bool mmha_partial(const MmhaParams& p, char* smem, u64* gout, const unsigned tag, int h,
-                                             int b, int sp)
+template<int DH>
+struct KvBeams: KvDense<DH> {
+    const ptrdiff_t row_kv;  // from a row's cache line to the next row's
+    const int*      indir;
+    const int       b_first;
+    // source plane of this step: (step - max_input_len) % 2 (GptNeoX.cc:778-780)
+    __device__ __forceinline__ KvBeams(const MmhaParams& p_, const int b_, const int h_):
+        KvDense<DH>(p_, b_, h_),
+        row_kv((ptrdiff_t)p_.nh * p_.s_max * DH),
+        indir(p_.cache_indir + (size_t)(((p_.d_step ? *p_.d_step : p_.step) - p_.max_input_len) & 1) * p_.indir_plane
+              + (size_t)b_ * p_.s_max),
+        b_first(b_ / p_.beam_width * p_.beam_width)
+    {
+    }
+    __device__ __forceinline__ const f16* k_row(const int t) const
+    {
+        return this->kc + (ptrdiff_t)(b_first + indir[t] - this->b) * row_kv + (size_t)t * DH;
+    }
+    __device__ __forceinline__ const f16* v_row(const int t) const
+    {
+        return this->vc + (ptrdiff_t)(b_first + indir[t] - this->b) * row_kv + (size_t)t * DH;
+    }
+};
+// Paged (the continuous batcher): rows live in P-token pages of a pool [page][nh][P][dh], found through the slot's page table
+// (pt: the kernel's LDS copy of it).  A slot's tokens are dense from position 0, so the new token's position is its length.
+// No EARLY_ROWS: a table entry at or beyond ceil((len + 1) / P) need not name a page of this slot, so every load is clamped to the
+// last cached key.  Finished slots never get here (k_mmha_paged returns before it reads anything).
+template<int DH>
+struct KvPaged {
+    static constexpr bool EARLY_ROWS = false;
+    f16 *                 kpool, *vpool;
+    const int*            pt;
+    int                   P, h, len;
+    size_t                page_elems;  // nh * P * DH
+    MmhaLds               at;          // the kernel's own carve-up, with the page table in it (mmha_paged_smem_bytes)
+    __device__ __forceinline__ size_t row(const int t) const { return (size_t)pt[t / P] * page_elems + ((size_t)h * P + (t % P)) * DH; }
+    __device__ __forceinline__ const f16* k_row(const int t) const { return kpool + row(t); }
+    __device__ __forceinline__ const f16* v_row(const int t) const { return vpool + row(t); }
+    __device__ __forceinline__ f16* k_new(const int tl) const { return kpool + row(tl); }
+    __device__ __forceinline__ f16* v_new(const int tl) const { return vpool + row(tl); }
+    __device__ __forceinline__ bool finished() const { return false; }
+    __device__ __forceinline__ int  length() const { return len; }
+    __device__ __forceinline__ int  rotary_pos(int) const { return len; }
+    __device__ __forceinline__ MmhaLds lds(char*) const { return at; }
+};
+
+// Split `sp` of (row b, head h): computes the un-normalised partial (max, sum, out[DH]) over its key range and
+// publishes it as granules.  Latency chain: ONE round trip for {finished, seq_len, step, q, bias, K rows, V rows}
+// (with ADDR::EARLY_ROWS the K/V rows of the whole fixed chunk are requested before tlength is known and masked afterwards),
+// then math.  make_addr() returns one of the key-row addressings above (ADDR); smem: the dynamic LDS that ADDR::lds lays out.
+template<int DH, class MAKE_ADDR>
+__device__ __forceinline__ bool mmha_partial(const MmhaParams& p, MAKE_ADDR&& make_addr, char* smem, u64* gout,
+                                             const unsigned tag, int h, int b, int sp)
 {
     // lanes per key/value row (16 B each): DH / 8 of them carry data, rounded up to a power of two so that the groups tile a
     // wave -- the reference's head sizes 48, 80, 96, 144 ... 224 (DecoderSelfAttentionLayer.cc:280-282) leave lanes of a
@@ -154,40 +252,25 @@ __device__ __forceinline__ bool mmha_partial(const MmhaParams& p, char* smem, u6
     const int  sub = act ? lane % LPK : 0;
     const int chunk = (((p.s_max + p.nsplit - 1) / p.nsplit) + 15) & ~15;
     const int t_beg = sp * chunk;
-    const f16* kc = p.k_cache + ((size_t)b * p.nh + h) * p.s_max * DH;
-    const f16* vc = p.v_cache + ((size_t)b * p.nh + h) * p.s_max * DH;
-    const int*      indir   = nullptr;
-    const ptrdiff_t row_kv  = (ptrdiff_t)p.nh * p.s_max * DH;
-    int             b_first = 0;
-    if constexpr (BEAMS) {
-        const int step0 = p.d_step ? *p.d_step : p.step;
-        // source plane of this step: (step - max_input_len) % 2 (GptNeoX.cc:778-780)
-        indir   = p.cache_indir + (size_t)((step0 - p.max_input_len) & 1) * p.indir_plane + (size_t)b * p.s_max;
-        b_first = b / p.beam_width * p.beam_width;
-    }
-    auto row_of = [&](const f16* own, const int t) -> const f16* {
-        if constexpr (BEAMS) {
-            return own + (ptrdiff_t)(b_first + indir[t] - b) * row_kv + (size_t)t * DH;
-        }
-        else {
-            return own + (size_t)t * DH;
-        }
-    };
+    // (the addressing is formed here, behind the split arithmetic, and not by the caller: the dense and beam kernels keep the
+    // instruction streams they had with the row pointers computed at this point, profiles/paged_attention_shared_partial.md)
+    const auto addr = make_addr();
+    using ADDR      = decltype(make_addr());
     constexpr int UK   = 8;
-    const bool    fast = (chunk <= 4 * KPI * UK);
+    const bool    fast = ADDR::EARLY_ROWS && (chunk <= 4 * KPI * UK);
     u32x4         kreg[UK], vreg[UK];
     if (fast) {
 #pragma unroll
         for (int u = 0; u < UK; u++) {
             int t   = t_beg + u * 4 * KPI + wid * KPI + grp;
             t       = t < p.s_max ? t : p.s_max - 1;  // always inside the cache; rows >= tlength are masked below
-            kreg[u] = *reinterpret_cast<const u32x4*>(row_of(kc, t) + sub * 8);
+            kreg[u] = *reinterpret_cast<const u32x4*>(addr.k_row(t) + sub * 8);
         }
 #pragma unroll
         for (int u = 0; u < UK; u++) {
             int t   = t_beg + u * 4 * KPI + wid * KPI + grp;
             t       = t < p.s_max ? t : p.s_max - 1;
-            vreg[u] = *reinterpret_cast<const u32x4*>(row_of(vc, t) + sub * 8);
+            vreg[u] = *reinterpret_cast<const u32x4*>(addr.v_row(t) + sub * 8);
         }
     }
     const int  hl = p.nh * DH;
@@ -214,10 +297,10 @@ __device__ __forceinline__ bool mmha_partial(const MmhaParams& p, char* smem, u6
             mask_bits |= (p.masked_tokens[(size_t)b * p.s_max + t] ? 1u : 0u) << u;
         }
     }
-    const bool fin  = p.finished && p.finished[b];
-    const int  tl   = p.seq_len[b];  // tlength: number of cached keys; the new token goes to index tl
+    const bool fin  = addr.finished();
+    const int  tl   = addr.length();  // tlength: number of cached keys; the new token goes to index tl
     const int  step = p.d_step ? *p.d_step : p.step;
-    const int  pos  = (step - 1) - (p.pad_count ? p.pad_count[b] : 0);  // :1303,:1343-1344
+    const int  pos  = addr.rotary_pos(step);
     __builtin_amdgcn_sched_barrier(0);
     if (fin) {
         return false;  // :1176 (ctx of a finished row is never consumed); uniform for all splits of the row
@@ -239,11 +322,12 @@ __device__ __forceinline__ bool mmha_partial(const MmhaParams& p, char* smem, u6
     const bool owns_cur     = (tl >= t_beg && tl < t_end);
     const int  t_cached_end = owns_cur ? tl : t_end;  // cached keys of this split: [t_beg, t_cached_end)
 
-    f16*   s_q    = reinterpret_cast<f16*>(smem);       // [DH]
-    f16*   s_k    = s_q + DH;                            // [DH] new key
-    f16*   s_v    = s_k + DH;                            // [DH] new value
-    float* s_red  = reinterpret_cast<float*>(s_v + DH);  // [8 + 4*DH]
-    float* s_p    = s_red + 8 + 4 * DH;                  // [chunk]
+    const MmhaLds lds = addr.lds(smem);
+    f16*   s_q   = lds.qkv;   // [DH]
+    f16*   s_k   = s_q + DH;  // [DH] new key
+    f16*   s_v   = s_k + DH;  // [DH] new value
+    float* s_red = lds.red;   // [8]
+    float* s_p   = lds.score;  // [chunk]
     if (threadIdx.x < DH) {
         s_q[threadIdx.x] = q_in;
         s_k[threadIdx.x] = k_in;
@@ -273,8 +357,8 @@ __device__ __forceinline__ bool mmha_partial(const MmhaParams& p, char* smem, u6
     }
     __syncthreads();
     if (owns_cur && threadIdx.x < DH) {  // append to the cache (:1397, :1837)
-        p.k_cache[(((size_t)b * p.nh + h) * p.s_max + tl) * DH + threadIdx.x] = s_k[threadIdx.x];
-        p.v_cache[(((size_t)b * p.nh + h) * p.s_max + tl) * DH + threadIdx.x] = s_v[threadIdx.x];
+        addr.k_new(tl)[threadIdx.x] = s_k[threadIdx.x];
+        addr.v_new(tl)[threadIdx.x] = s_v[threadIdx.x];
     }
 
     const float inv_sqrt_dh = rsqrtf((float)DH);  // DecoderSelfAttentionLayer.cc:118 with q_scaling 1
@@ -290,7 +374,7 @@ __device__ __forceinline__ bool mmha_partial(const MmhaParams& p, char* smem, u6
     // looped form (key ranges beyond the all-in-registers one): rounds of U rows per lane, two rounds in flight (the loads
     // of round i + 1 are requested before round i is consumed; clamped, never conditional)
     constexpr int U = 8;
-    auto stream_rows = [&](const f16* base, auto&& consume) {
+    auto stream_rows = [&](auto&& row_of, auto&& consume) {
         constexpr int STEP = 4 * KPI * U;
         int           t0   = t_beg + wid * KPI;
         if (t0 >= t_cached_end) {
@@ -302,7 +386,7 @@ __device__ __forceinline__ bool mmha_partial(const MmhaParams& p, char* smem, u6
             for (int u = 0; u < U; u++) {
                 int t = tt + u * 4 * KPI + grp;
                 t     = t < t_cached_end ? t : t_cached_end - 1;
-                r[u]  = *reinterpret_cast<const u32x4*>(row_of(base, t) + sub * 8);
+                r[u]  = *reinterpret_cast<const u32x4*>(row_of(t) + sub * 8);
             }
         };
         ld(ra, t0);
@@ -328,13 +412,7 @@ __device__ __forceinline__ bool mmha_partial(const MmhaParams& p, char* smem, u6
         }
     };
     auto qk_one = [&](const u32x4 raw, const int t, const int u_fast) {
-        const f16x8 kv = __builtin_bit_cast(f16x8, raw);
-        float       a  = 0.f;
-        a              = dot2(f16x2{qv[0], qv[1]}, f16x2{kv[0], kv[1]}, a);
-        a              = dot2(f16x2{qv[2], qv[3]}, f16x2{kv[2], kv[3]}, a);
-        a              = dot2(f16x2{qv[4], qv[5]}, f16x2{kv[4], kv[5]}, a);
-        a              = dot2(f16x2{qv[6], qv[7]}, f16x2{kv[6], kv[7]}, a);
-        a              = group_sum(a, LPK) * inv_sqrt_dh;
+        const float a = group_sum(dot8(qv, __builtin_bit_cast(f16x8, raw), 0.f), LPK) * inv_sqrt_dh;
         if (t < t_cached_end && sub0) {
             const bool m = (u_fast >= 0) ? ((mask_bits >> u_fast) & 1u) != 0u : (mask && mask[t]);
             s_p[t - t_beg] = m ? -INFINITY : a;  // masked keys get probability 0 (:1570,:1610-1622)
@@ -350,17 +428,14 @@ __device__ __forceinline__ bool mmha_partial(const MmhaParams& p, char* smem, u6
         }
     }
     else {
-        stream_rows(kc, [&](const u32x4 raw, const int t) { qk_one(raw, t, -1); });
+        stream_rows([&](const int t) { return addr.k_row(t); }, [&](const u32x4 raw, const int t) { qk_one(raw, t, -1); });
     }
     if (owns_cur && wid == 0) {  // current token from LDS (:1407-1437)
         float a = 0.f;
         if (lane < NSUB) {
             const f16x8 kv = *reinterpret_cast<const f16x8*>(s_k + lane * 8);
             const f16x8 q8 = *reinterpret_cast<const f16x8*>(s_q + lane * 8);
-            a              = dot2(f16x2{q8[0], q8[1]}, f16x2{kv[0], kv[1]}, a);
-            a              = dot2(f16x2{q8[2], q8[3]}, f16x2{kv[2], kv[3]}, a);
-            a              = dot2(f16x2{q8[4], q8[5]}, f16x2{kv[4], kv[5]}, a);
-            a              = dot2(f16x2{q8[6], q8[7]}, f16x2{kv[6], kv[7]}, a);
+            a              = dot8(q8, kv, a);
         }
         a = wave_sum(a) * inv_sqrt_dh;
         if (lane == 0) {
@@ -409,7 +484,7 @@ __device__ __forceinline__ bool mmha_partial(const MmhaParams& p, char* smem, u6
         }
     }
     else {
-        stream_rows(vc, [&](const u32x4 raw, const int t) { pv_one(raw, t); });
+        stream_rows([&](const int t) { return addr.v_row(t); }, [&](const u32x4 raw, const int t) { pv_one(raw, t); });
     }
     if (owns_cur && wid == 0 && grp == 0 && act) {
         const float pt = s_p[tl - t_beg];
@@ -426,7 +501,7 @@ __device__ __forceinline__ bool mmha_partial(const MmhaParams& p, char* smem, u6
             acc[j] += __shfl_xor(acc[j], o, 64);
         }
     }
-    float* s_o = s_red + 8;  // [4][DH]
+    float* s_o = lds.out;  // [4][DH]
     if (grp == 0 && act) {
 #pragma unroll
         for (int j = 0; j < 8; j++) {
@@ -464,14 +539,14 @@ __device__ __forceinline__ bool mmha_partial(const MmhaParams& p, char* smem, u6
 // after its other splits: a merger never holds a slot that a producer it waits for still needs (with split 0 as the merger and
 // more workgroups than slots -- 16 rows x 40 heads x 2 splits -- the first wave of workgroups spun until their limit:
 // 10..80 ms per step).  Every spin is bounded.
-template<int DH, bool BEAMS = false>
+template<int DH, class ADDR = KvDense<DH>>
 __device__ __forceinline__ void mmha_block(const MmhaParams& p, char* smem, int& s_last, const int h, const int b, const int sp)
 {
     (void)s_last;
     const int      step = p.d_step ? *p.d_step : p.step;
     const unsigned tag  = (unsigned)(step * 1024 + p.layer) + 1u;  // salt < 1024: layer + row group * num_layer
     u64*           gall = p.gran + ((size_t)b * p.nh + h) * p.nsplit * (DH + 2);
-    const bool     live = mmha_partial<DH, BEAMS>(p, smem, gall + (size_t)sp * (DH + 2), tag, h, b, sp);
+    const bool     live = mmha_partial<DH>(p, [&] { return ADDR(p, b, h); }, smem, gall + (size_t)sp * (DH + 2), tag, h, b, sp);
     if (!live || sp != p.nsplit - 1) {
         return;
     }

@@ -19,7 +19,7 @@
 // slots.  Admission runs the prompt through the engine's own context path (ftcf_gptneox_forward with output_len 1: prefill +
 // first token sampled by the engine's dynamic decode) and scatters the prompt's K/V into the slot's pages; the decode
 // step is the general layer sequence of the engine (§4a: dual LayerNorm, burst / tiled GEMMs, fused residual) with the
-// attention replaced by k_mmha_paged, the LM head, and the engine's sampling kernels on per-slot arrays.  A sequence leaves
+// attention replaced by k_mmha_paged (the engine's mmha_partial over the page table, one split), the LM head, and the engine's sampling kernels on per-slot arrays.  A sequence leaves
 // when it emits end_id or reaches max_new_tokens; its pages return to the free list at once.
 // Scope: parallel-residual models, any tensor_para_size (round 4: one batcher per rank), fp16 / int8 engines; top-k / top-p /
 // temperature sampling with repetition penalty, stop words and a token callback; beam search (round 4: BeamGroup below).
@@ -59,7 +59,7 @@ __global__ void k_batcher_tick(DecodeState* gemm_state)
 
 // the rows kernel inside the batcher (round 5): its step counter (the hand-off tags are step * 256 + layer + 1) and the rotary table
 // of the step -- a slot's new token sits at position len[slot] (decoder_masked_multihead_attention_utils.h:1325-1345 coefficients,
-// as k_mmha_paged computes them in place)
+// as mmha_partial computes them in place for k_mmha_paged, whose rotary position is the slot's length)
 __global__ void k_batcher_rows_prep(int* step, float* rot_table, const int* len, int rot)
 {
     if (blockIdx.x == 0 && threadIdx.x == 0) {

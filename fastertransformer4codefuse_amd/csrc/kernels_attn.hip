@@ -26,7 +26,7 @@ __global__ __launch_bounds__(256) void k_mmha_split(const MmhaParams p)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ int s_last;
-    mmha_block<DH, BEAMS>(p, smem, s_last, blockIdx.x, blockIdx.y, blockIdx.z);
+    mmha_block<DH, std::conditional_t<BEAMS, KvBeams<DH>, KvDense<DH>>>(p, smem, s_last, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 
 size_t mmha_workspace_bytes(int B, int nh, int dh, int nsplit)
@@ -610,149 +610,36 @@ void launch_context_attention(const f16* qkv, const f16* qkv_bias, const int* in
 // ---------------------------------------------------------------------------------------------------------------
 // Paged decoder attention (the continuous-batching front end, engine.hip `ftcf_batcher`): the K/V of a
 // sequence live in fixed-size pages of a pool shared by all sequences, [page][head][P tokens][dh], found through the
-// sequence's page table.  Same arithmetic as mmha_partial with one split (attn_device.hip.h): half q/k/v + bias, NeoX rotary
-// at position = number of cached tokens, fp32 scores, exp against the row maximum, fp32 PV, one normalisation with the
-// reference's +1e-6 (decoder_masked_multihead_attention_template.hpp:1632).  One workgroup per (head, slot); a sequence's
-// length is its own (no padding, no masks: a slot's tokens are dense from position 0).
+// sequence's page table.  The attention itself is mmha_partial (attn_device.hip.h) with paged addressing and one split: on the
+// same keys its ctx and appended rows are the dense kernel's, bit for bit.  One workgroup per (head, slot); a sequence's length
+// is its own (no padding, no masks: a slot's tokens are dense from position 0, the new one at position = its length).
 // ---------------------------------------------------------------------------------------------------------------
 template<int DH>
 __global__ __launch_bounds__(256) void k_mmha_paged(const MmhaPagedParams p)
 {
-    constexpr int LPK = DH / 8;    // lanes per key/value row (16 B each)
-    constexpr int KPI = 64 / LPK;  // rows per wave-load
-    extern __shared__ __attribute__((aligned(16))) char smem_pg[];
-    __shared__ float s_red[16];
+    extern __shared__ __attribute__((aligned(16))) char smem_pg[];  // mmha_paged_smem_bytes: [q k v][out 4 * DH][page table][scores]
+    __shared__ float s_red[8];
     const int h = blockIdx.x, b = blockIdx.y;
     if (p.finished[b]) {
-        return;
+        return;  // nothing read, nothing written
     }
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int sub = lane % LPK, grp = lane / LPK;
-    const int tl  = p.len[b];  // cached tokens = position of the current one
-    f16*      s_q = reinterpret_cast<f16*>(smem_pg);
-    f16*      s_k = s_q + DH;
-    f16*      s_v = s_k + DH;
-    float*    s_o = reinterpret_cast<float*>(s_v + DH);  // [4][DH]
-    int*      s_pt = reinterpret_cast<int*>(s_o + 4 * DH);  // [max_pages]
-    float*    s_p = reinterpret_cast<float*>(s_pt + p.max_pages);  // [tl + 1]
-    const int hl  = p.nh * DH;
-    for (int i = threadIdx.x; i < p.max_pages; i += 256) {
+    f16*   s_qkv = reinterpret_cast<f16*>(smem_pg);
+    float* s_o   = reinterpret_cast<float*>(s_qkv + 3 * DH);
+    int*   s_pt  = reinterpret_cast<int*>(s_o + 4 * DH);
+    for (int i = threadIdx.x; i < p.max_pages; i += 256) {  // (visible after the partial's first barrier, before its first use)
         s_pt[i] = p.page_table[(size_t)b * p.max_pages + i];
     }
-    if (threadIdx.x < DH) {
-        const int    d    = threadIdx.x;
-        const size_t base = (size_t)b * 3 * hl + h * DH + d;
-        s_q[d] = p.qkv[base] + p.qkv_bias[h * DH + d];
-        s_k[d] = p.qkv[base + hl] + p.qkv_bias[hl + h * DH + d];
-        s_v[d] = p.qkv[base + 2 * hl] + p.qkv_bias[2 * hl + h * DH + d];
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < p.rot / 2) {
-        float cs, sn;
-        rotary_coef(threadIdx.x, p.rot, tl, cs, sn);
-        const int j = threadIdx.x, j2 = j + p.rot / 2;
-        f16       a = s_q[j], c = s_q[j2];
-        rotary_apply(a, c, cs, sn);
-        s_q[j]  = a;
-        s_q[j2] = c;
-        f16 ka = s_k[j], kc = s_k[j2];
-        rotary_apply(ka, kc, cs, sn);
-        s_k[j]  = ka;
-        s_k[j2] = kc;
-    }
-    __syncthreads();
-    const size_t page_elems = (size_t)p.nh * p.P * DH;
-    auto row_ptr = [&](const f16* pool, const int t) -> const f16* {
-        return pool + (size_t)s_pt[t / p.P] * page_elems + ((size_t)h * p.P + (t % p.P)) * DH;
-    };
-    if (threadIdx.x < DH) {  // append the current token (its page was allocated by the scheduler)
-        f16* kd = const_cast<f16*>(row_ptr(p.kpool, tl));
-        f16* vd = const_cast<f16*>(row_ptr(p.vpool, tl));
-        kd[threadIdx.x] = s_k[threadIdx.x];
-        vd[threadIdx.x] = s_v[threadIdx.x];
-    }
-    const float inv_sqrt_dh = rsqrtf((float)DH);
-    const f16x8 qv          = *reinterpret_cast<const f16x8*>(s_q + sub * 8);
-    float       lmax        = -INFINITY;
-    for (int t0 = 0; t0 < tl; t0 += 4 * KPI) {
-        const int   t  = t0 + wid * KPI + grp;
-        const int   tc = t < tl ? t : tl - 1;
-        const f16x8 kv = *reinterpret_cast<const f16x8*>(row_ptr(p.kpool, tc) + sub * 8);
-        float       a  = 0.f;
-        a              = dot2(f16x2{qv[0], qv[1]}, f16x2{kv[0], kv[1]}, a);
-        a              = dot2(f16x2{qv[2], qv[3]}, f16x2{kv[2], kv[3]}, a);
-        a              = dot2(f16x2{qv[4], qv[5]}, f16x2{kv[4], kv[5]}, a);
-        a              = dot2(f16x2{qv[6], qv[7]}, f16x2{kv[6], kv[7]}, a);
-        a              = group_sum(a, LPK) * inv_sqrt_dh;
-        if (t < tl && sub == 0) {
-            s_p[t] = a;
-            lmax   = fmaxf(lmax, a);
-        }
-    }
-    if (wid == 0) {  // current token from LDS
-        float a = 0.f;
-        if (lane < LPK) {
-            const f16x8 kv = *reinterpret_cast<const f16x8*>(s_k + lane * 8);
-            const f16x8 q8 = *reinterpret_cast<const f16x8*>(s_q + lane * 8);
-            a              = dot2(f16x2{q8[0], q8[1]}, f16x2{kv[0], kv[1]}, a);
-            a              = dot2(f16x2{q8[2], q8[3]}, f16x2{kv[2], kv[3]}, a);
-            a              = dot2(f16x2{q8[4], q8[5]}, f16x2{kv[4], kv[5]}, a);
-            a              = dot2(f16x2{q8[6], q8[7]}, f16x2{kv[6], kv[7]}, a);
-        }
-        a = wave_sum(a) * inv_sqrt_dh;
-        if (lane == 0) {
-            s_p[tl] = a;
-            lmax    = fmaxf(lmax, a);
-        }
-    }
-    lmax = wave_max(lmax);
-    if (lane == 0) {
-        s_red[wid] = lmax;
-    }
-    __syncthreads();
-    const float m = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
-    float       lsum = 0.f;
-    for (int i = threadIdx.x; i <= tl; i += 256) {
-        const float e = __expf(s_p[i] - m);
-        s_p[i]        = e;
-        lsum += e;
-    }
-    lsum = wave_sum(lsum);
-    if (lane == 0) {
-        s_red[4 + wid] = lsum;
-    }
-    __syncthreads();
-    const float inv = 1.f / (((s_red[4] + s_red[5]) + (s_red[6] + s_red[7])) + 1.e-6f);
-    // PV: lane (grp, sub) accumulates dims sub*8 .. +7 over its keys, then the key groups of a wave and the waves are added
-    float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int t0 = 0; t0 < tl; t0 += 4 * KPI) {
-        const int   t  = t0 + wid * KPI + grp;
-        const int   tc = t < tl ? t : tl - 1;
-        const f16x8 vv = *reinterpret_cast<const f16x8*>(row_ptr(p.vpool, tc) + sub * 8);
-        const float w  = t < tl ? s_p[t] : 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            o[j] = fmaf(w, (float)vv[j], o[j]);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-        for (int off = LPK; off < 64; off <<= 1) {
-            o[j] += __shfl_xor(o[j], off, 64);
-        }
-    }
-    if (grp == 0) {
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            s_o[wid * DH + sub * 8 + j] = o[j];
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < DH) {
-        const int   d = threadIdx.x;
-        const float v = ((s_o[d] + s_o[DH + d]) + (s_o[2 * DH + d] + s_o[3 * DH + d])) + s_p[tl] * (float)s_v[d];
-        p.ctx[(size_t)b * hl + h * DH + d] = (f16)(v * inv);
-    }
+    MmhaParams mp{};  // what the partial reads of it; the rest stays null / zero and folds away
+    mp.qkv      = p.qkv;
+    mp.qkv_bias = p.qkv_bias;
+    mp.nh       = p.nh;
+    mp.rot      = p.rot;
+    mp.s_max    = p.max_pages * p.P;  // one split over every position a slot can reach
+    mp.nsplit   = 1;
+    mp.ctx      = p.ctx;
+    const MmhaLds at{s_qkv, s_red, s_o, reinterpret_cast<float*>(s_pt + p.max_pages)};
+    const auto    addr = [&] { return KvPaged<DH>{p.kpool, p.vpool, s_pt, p.P, h, p.len[b], (size_t)p.nh * p.P * DH, at}; };
+    mmha_partial<DH>(mp, addr, smem_pg, nullptr, 0u, h, b, 0);
 }
 
 size_t mmha_paged_smem_bytes(int dh, int max_pages, int max_len)

@@ -271,6 +271,71 @@ def test_paged_attention_reads_and_writes_pages_above_2_to_the_31_elements():
     torch.cuda.empty_cache()
 
 
+@pytest.mark.parametrize("dh,rot,P,lens,s_max", [
+    (128, 32, 8, [0, 1, 15, 16, 17, 95], 96),    # dense: all in registers (<= 128 keys)
+    (128, 32, 8, [127, 128, 129, 300], 304),     # dense: the looped form
+    (128, 32, 8, [600], 608),                    # ... past one 512-key step of its two rounds in flight
+    (64, 16, 24, [0, 31, 32, 33, 255], 256),     # dense: all in registers (<= 256 keys)
+    (64, 16, 24, [257, 700], 704)])              # dense: the looped form
+def test_paged_attention_equals_dense_attention_bit_for_bit(dh, rot, P, lens, s_max):
+    """One launch of ftcf_paged_attention and one of ftcf_masked_multihead_attention_beams (fp16, no indirection, one split, no
+    mask) over the same keys and values: both are mmha_partial, so ctx and the appended K / V rows are identical bits and neither
+    cache changes anywhere else.  Pages are permuted, unused table entries name a trap page; the dense cache [B, nh, s_max, dh]
+    holds exactly the rows the pages hold and a sentinel elsewhere; pad_count puts the dense row's rotary position at len[b]."""
+    nh = 2
+    rng = np.random.RandomState(dh + s_max)
+    lens = np.array(lens, dtype=np.int32)
+    B = len(lens)
+    fin = np.zeros(B, dtype=np.uint8)
+    pt, num_pages, trap = _layout(rng, lens, P, False, extra=3)
+    max_len = pt.shape[1] * P
+    assert smem_bytes(dh, pt.shape[1], max_len) <= LDS and int(lens.max()) < min(max_len, s_max)
+    kb = _sentinel(rng, num_pages * nh * P * dh).reshape(num_pages, nh, P, dh)
+    vb = _sentinel(rng, num_pages * nh * P * dh).reshape(num_pages, nh, P, dh)
+    kd = _sentinel(rng, B * nh * s_max * dh).reshape(B, nh, s_max, dh)
+    vd = _sentinel(rng, B * nh * s_max * dh).reshape(B, nh, s_max, dh)
+    for b in range(B):
+        n = int(lens[b])
+        t = np.arange(n)
+        kd[b, :, :n] = _half(rng.randn(nh, n, dh)).view(np.uint16)
+        vd[b, :, :n] = _half(rng.randn(nh, n, dh)).view(np.uint16)
+        kb[pt[b, t // P], :, t % P] = kd[b, :, :n].transpose(1, 0, 2)
+        vb[pt[b, t // P], :, t % P] = vd[b, :, :n].transpose(1, 0, 2)
+    qkv = _half(rng.randn(B, 3, nh, dh))
+    bias = _half(0.1 * rng.randn(3, nh, dh))
+    ctx0 = _sentinel(rng, B * nh * dh).reshape(B, nh, dh)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.int16).copy()).cuda()
+
+    Kp, Vp, ctx_p = dev(kb), dev(vb), dev(ctx0)
+    _run(qkv, bias, Kp, Vp, pt, lens, fin, nh, dh, rot, P, max_len, ctx_p)
+
+    Kd, Vd, ctx_d = dev(kd), dev(vd), dev(ctx0)
+    step = s_max + 1
+    keep = [dev(qkv), dev(bias), torch.from_numpy(lens).cuda(), torch.from_numpy((step - 1 - lens).astype(np.int32)).cuda(),
+            torch.from_numpy(fin).cuda()]
+    wsb = B * nh * (dh + 2) * 8
+    ws = torch.empty(wsb, dtype=torch.uint8, device="cuda")
+    capi.check(capi.lib().ftcf_masked_multihead_attention_beams(
+        capi.FP16, capi.vp(keep[0]), capi.vp(keep[1]), capi.vp(Kd), capi.vp(Vd), capi.vp(keep[2]), capi.vp(keep[3]), capi.vp(None),
+        capi.vp(keep[4]), capi.vp(None), 1, 0, B, nh, dh, rot, s_max, step, 1, capi.vp(ctx_d), capi.vp(ws), C.c_size_t(wsb), sp()))
+    torch.cuda.synchronize()
+
+    u16 = lambda t: t.cpu().numpy().view(np.uint16)
+    cp, kp, vp, cd, kda, vda = (u16(t) for t in (ctx_p, Kp, Vp, ctx_d, Kd, Vd))
+    assert np.array_equal(cp, cd), ("ctx differs (slot, head, dim)", np.argwhere(cp != cd)[:8].tolist())
+    assert (cp != ctx0).any(axis=2).all(), "a (slot, head) whose ctx was not written"
+    for b in range(B):
+        n = int(lens[b])
+        pg, r = pt[b, n // P], n % P
+        assert np.array_equal(kp[pg, :, r], kda[b, :, n]), ("appended k differs", b, n)
+        assert np.array_equal(vp[pg, :, r], vda[b, :, n]), ("appended v differs", b, n)
+        kb[pg, :, r], vb[pg, :, r] = kp[pg, :, r], vp[pg, :, r]  # what the caches must hold now: one appended row per slot
+        kd[b, :, n], vd[b, :, n] = kda[b, :, n], vda[b, :, n]
+    for name, got, want in (("k_pool", kp, kb), ("v_pool", vp, vb), ("k_cache", kda, kd), ("v_cache", vda, vd)):
+        bad = np.argwhere(got != want)
+        assert bad.size == 0, (name, "stray writes", bad[:8].tolist())
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # scatter (a prompt's dense K/V -> its pages) and gather (the prefix cache: pages -> the dense cache), bit for bit
 # ---------------------------------------------------------------------------------------------------------------------
