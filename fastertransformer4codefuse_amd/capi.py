@@ -137,7 +137,7 @@ EXPORTED = [
     "ftcf_gemm_smallm_group", "ftcf_gemm_smallm_workspace_bytes", "ftcf_gemm_smallm_ticket_bytes",
     "ftcf_residual_dual_layernorm", "ftcf_add_bias_residual", "ftcf_ln_gemv", "ftcf_residual_gemv", "ftcf_residual_gemv_workspace_bytes", "ftcf_layernorm", "ftcf_add_bias_attn_ffn_residual",
     "ftcf_masked_multihead_attention", "ftcf_masked_multihead_attention_workspace", "ftcf_masked_multihead_attention_beams",
-    "ftcf_context_attention",
+    "ftcf_context_attention", "ftcf_context_attention_range",
     "ftcf_verify_attention", "ftcf_verify_attention_workspace", "ftcf_ngram_draft",
     "ftcf_paged_attention", "ftcf_scatter_kv_to_pages", "ftcf_gather_pages_to_kv", "ftcf_pages_pack", "ftcf_pages_unpack",
     "ftcf_dynamic_decode_step", "ftcf_beam_search_step", "ftcf_logit_process",

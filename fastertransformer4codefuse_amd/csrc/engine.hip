@@ -538,6 +538,31 @@ extern "C" int ftcf_context_attention(const void* qkv, const void* qkv_bias, con
                                  S, nh, dh, rot, s_max, (f16*)ctx, (hipStream_t)stream);
     });
 }
+extern "C" int ftcf_context_attention_range(ftcf_dtype dtype, void* qkv, const void* qkv_bias, const int* input_lengths,
+                                            void* k_cache, void* v_cache, int B, int S, int nh, int dh, int rot, int s_max,
+                                            int cache_row_mult, int s_lo, int s_hi, void* ctx, void* stream)
+{
+    return guarded([&] {
+        require_device();
+        FTCF_CHECK_ARG(dtype == FTCF_FP16 || dtype == FTCF_FP32, "context attention: dtype fp16 or fp32");
+        FTCF_CHECK_ARG(qkv && qkv_bias && input_lengths && k_cache && v_cache && ctx, "NULL tensor");
+        FTCF_CHECK_ARG(B >= 1 && nh >= 1 && cache_row_mult >= 1 && mmha_head_size_supported(dh) && rot >= 0 && rot % 2 == 0
+                           && rot <= dh && S >= 1 && S <= s_max,
+                       "context attention: bad geometry");
+        if (dtype == FTCF_FP32) {
+            FTCF_CHECK_ARG(s_lo == 0 && (s_hi == -1 || s_hi == S), "fp32 context attention: the whole prompt only");
+            FTCF_CHECK_ARG((size_t)(S + dh + 4) * sizeof(float) <= ABI_MAX_DYNAMIC_LDS,
+                           "fp32 context attention: a query's scores do not fit the LDS");
+            launch32_context_attention((float*)qkv, (const float*)qkv_bias, input_lengths, (float*)k_cache, (float*)v_cache, B, S,
+                                       nh, dh, rot, s_max, (float*)ctx, (hipStream_t)stream, cache_row_mult);
+            FTCF_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+            return;
+        }
+        FTCF_CHECK_ARG(s_lo >= 0 && s_lo < s_hi && s_hi <= S, "context attention: bad token range");
+        launch_context_attention((const f16*)qkv, (const f16*)qkv_bias, input_lengths, (f16*)k_cache, (f16*)v_cache, B, S, nh,
+                                 dh, rot, s_max, (f16*)ctx, (hipStream_t)stream, cache_row_mult, s_lo, s_hi);
+    });
+}
 // the batcher's paged kernels, one call each (the batcher itself launches them through the same launchers)
 extern "C" int ftcf_paged_attention(const void* qkv, const void* qkv_bias, void* k_pool, void* v_pool, const int* page_table,
                                     const int* lengths, const uint8_t* finished, int B, int nh, int dh, int rot, int page_tokens,

@@ -224,6 +224,23 @@ int ftcf_ngram_draft(const int* tokens, int n, int K, int N, int* draft, int* n_
  * qkv [B*S, 3*Hl] fp16 (row = b*S+s), ctx [B*S, Hl] fp16. */
 int ftcf_context_attention(const void* qkv, const void* qkv_bias, const int* input_lengths, void* k_cache,
                            void* v_cache, int B, int S, int nh, int dh, int rot, int s_max, void* ctx, void* stream);
+/* The same prompt attention with every argument of its launcher: a token range [s_lo, s_hi) of each sequence (one chunk of a
+ * chunked prompt phase, or the tail of a prompt whose head is cached already) and a cache row multiplier.  dtype FTCF_FP16 or
+ * FTCF_FP32 (qkv, qkv_bias, caches and ctx all of that type).  qkv [B*S, 3*Hl] (row = b*S+s), ctx [B*S, Hl], caches
+ * [B * cache_row_mult, nh, s_max, dh]: the K/V of sequence b live in cache row b * cache_row_mult.  len = input_lengths[b].
+ * Read: qkv rows [s_lo, s_hi) of each sequence and, of its cache row, positions [0, s_lo) below len -- the keys and values of
+ * the earlier chunks, which must be there; no other cache element's value reaches a result.
+ * Written: for the positions s of [s_lo, s_hi) below len, the q part of qkv row s (bias + NeoX rotary at position s, in place),
+ * the K/V rows of position s (V = v + bias, bit exact) and ctx row s = soft-max attention of that q over positions [0, s];
+ * for the positions of [s_lo, s_hi) at or above len, zeros into the K/V rows and into the q part of the qkv row.  Nothing
+ * else: the k and v parts of qkv, the qkv rows outside the range, the ctx rows outside the range or at and above len, the cache
+ * positions outside the range and every other cache row keep their bits.  Deterministic: two calls give identical bits.  fp16: 0 <= s_lo < s_hi <= S.  fp32: the whole prompt only (s_lo
+ * = 0, s_hi = S or -1), S + dh + 4 floats must fit 64 KiB of LDS, and the call returns after the launch has finished.
+ * B, nh, cache_row_mult >= 1; dh one of 32, 48, 64, 80, 96, 128, 144, 160, 192, 224, 256; rot even, 0 <= rot <= dh; S <= s_max.
+ * A bad argument is an error return, never a failed launch. */
+int ftcf_context_attention_range(ftcf_dtype dtype, void* qkv, const void* qkv_bias, const int* input_lengths, void* k_cache,
+                                 void* v_cache, int B, int S, int nh, int dh, int rot, int s_max, int cache_row_mult, int s_lo,
+                                 int s_hi, void* ctx, void* stream);
 /* The continuous batcher's decode attention over paged K/V (one layer): the arithmetic of ftcf_masked_multihead_attention for
  * slot b at position lengths[b] (NeoX rotary at that position), the keys of positions [0, lengths[b]) read through
  * page_table[b][t / page_tokens] at row t % page_tokens, the new key / value row appended there.  qkv [B, 3*nh*dh] fp16,

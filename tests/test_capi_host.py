@@ -57,6 +57,7 @@ def test_engine_form_entry_points_fail_loudly_without_a_gpu():
         lambda: L.ftcf_beam_search_step(C.byref(beam), None),
         lambda: L.ftcf_masked_multihead_attention_beams(1, None, None, None, None, None, None, None, None, None, 2, 1, 2, 1, 64, 16, 64, 2, 1,
                                                         None, None, C.c_size_t(0), None),
+        lambda: L.ftcf_context_attention_range(1, None, None, None, None, None, 1, 8, 1, 64, 16, 8, 1, 0, 8, None, None),
     ]
     for call in calls:
         assert call() == -5 and b"no HIP device" in L.ftcf_last_error()
