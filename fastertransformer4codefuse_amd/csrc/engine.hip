@@ -965,6 +965,40 @@ __global__ void k_scale_by_tp(T* buf, size_t n, float tp)
 template __global__ void k_scale_by_tp<f16>(f16*, size_t, float);
 template __global__ void k_scale_by_tp<float>(float*, size_t, float);
 
+// The prompt phase of a request (GptNeoX.cc:640-735): embedding -> context decoder -> the last token's hidden state into x, for
+// fp32 or fp16 / int8 rows, with or without beams (a beam request prefills ONE row per request into cache row b * K and tiles its
+// last hidden state); a prompt of one token has no prompt phase, its token is the first decode step's input.
+// in_ids / in_len: the inputs per ROW (tiled for beams)
+void ftcf_gptneox::prompt_phase(const ftcf_forward_args& a, const int* in_ids, const int* in_len)
+{
+    const int K = a.beam_width, batch = a.batch_size, B = batch * K, S = a.max_input_len, s_max = S + a.output_len;
+    if (S > 1 && K > 1 && fp32) {
+        launch32_prompt_embedding(F(px), nullptr, F(wte), a.input_ids, batch, S, H, stream);
+        launch_tile_prompt_ids(step_ids, a.input_ids, batch, K, S, stream);
+        context_decoder32(batch, S, a.input_lengths, s_max, K);
+        launch32_gather_last_token(F(x), F(px), a.input_lengths, batch, S, H, stream, K);
+    }
+    else if (S > 1 && fp32) {
+        launch32_prompt_embedding(F(px), step_ids, F(wte), in_ids, B, S, H, stream);
+        context_decoder32(B, S, in_len, s_max, 1);
+        launch32_gather_last_token(F(x), F(px), in_len, B, S, H, stream);
+    }
+    else if (S > 1 && K > 1) {
+        launch_prompt_embedding(px, nullptr, wte, a.input_ids, batch, S, H, stream);
+        launch_tile_prompt_ids(step_ids, a.input_ids, batch, K, S, stream);
+        context_decoder(batch, S, a.input_lengths, s_max, K);
+        launch_gather_last_token(x, px, a.input_lengths, batch, S, H, stream, K);
+    }
+    else if (S > 1) {
+        launch_prompt_embedding(px, step_ids, wte, in_ids, B, S, H, stream);
+        context_decoder(B, S, in_len, s_max, 1);
+        launch_gather_last_token(x, px, in_len, B, S, H, stream);
+    }
+    else {
+        FTCF_HIP_CHECK(hipMemcpyAsync(step_ids, in_ids, (size_t)B * 4, hipMemcpyDeviceToDevice, stream));
+    }
+}
+
 void ftcf_gptneox::begin(const ftcf_forward_args& a)
 {
     {  // (once per request, not per token)
@@ -1137,31 +1171,10 @@ void ftcf_gptneox::begin(const ftcf_forward_args& a)
     if (B <= 2 && !fp32) {  // the tagged partials of k_lm_head_greedy: a tag is the step, and steps repeat from request to request
         FTCF_HIP_CHECK(hipMemsetAsync(samp_ws, 0, lm_head_greedy_partial_bytes(B), stream));
     }
-    if (S > 1 && K > 1 && fp32) {
-        launch32_prompt_embedding(F(px), nullptr, F(wte), a.input_ids, batch, S, H, stream);
-        launch_tile_prompt_ids(step_ids, a.input_ids, batch, K, S, stream);
-        context_decoder32(batch, S, a.input_lengths, s_max, K);
-        launch32_gather_last_token(F(x), F(px), a.input_lengths, batch, S, H, stream, K);
-    }
-    else if (S > 1 && fp32) {
-        launch32_prompt_embedding(F(px), step_ids, F(wte), in_ids, B, S, H, stream);
-        context_decoder32(B, S, in_len, s_max, 1);
-        launch32_gather_last_token(F(x), F(px), in_len, B, S, H, stream);
-    }
-    else if (S > 1 && K > 1) {
-        launch_prompt_embedding(px, nullptr, wte, a.input_ids, batch, S, H, stream);
-        launch_tile_prompt_ids(step_ids, a.input_ids, batch, K, S, stream);
-        context_decoder(batch, S, a.input_lengths, s_max, K);
-        launch_gather_last_token(x, px, a.input_lengths, batch, S, H, stream, K);
-    }
-    else if (S > 1) {
-        launch_prompt_embedding(px, step_ids, wte, in_ids, B, S, H, stream);
-        context_decoder(B, S, in_len, s_max, 1);
-        launch_gather_last_token(x, px, in_len, B, S, H, stream);
-    }
-    else {
-        FTCF_HIP_CHECK(hipMemcpyAsync(step_ids, in_ids, (size_t)B * 4, hipMemcpyDeviceToDevice, stream));
-    }
+    // what the stats will say of THIS request's overlapped forms: the prompt phase below and the token loop set them
+    ov_ran = ov_eligible = false;
+    dv_ran = dv_eligible = false;
+    prompt_phase(a, in_ids, in_len);
     if (a.context_log_probs) {
         // (ParallelGpt.cc:403-470) px holds the last layer's output of every prompt row, once per request (beams included, tensor
         // parallel ranks alike: the head is replicated): the final LayerNorm, then the fused LM head -> log-prob kernel
@@ -1292,7 +1305,6 @@ void ftcf_gptneox::begin(const ftcf_forward_args& a)
     ses.spec_N = a.speculative_ngram > 0 ? a.speculative_ngram : 3;
     ses.spec_nd = ses.spec_steps = ses.spec_drafted = ses.spec_accepted = 0;
     stats.decode_ms = 0.f;
-    dv_ran = dv_eligible = false;
 }
 
 // enqueues one iteration of the token loop (GptNeoX.cc:776-1048) on `stream` (and the side stream)

@@ -640,35 +640,45 @@ struct ftcf_gptneox {
         }
     }
 
-    // GptNeoXContextDecoder::forward (GptNeoXContextDecoder.cc:283-507), parallel residual only
-    // B prompt rows; their K/V go to cache rows b * tile of a cache with B * tile rows (beam search: tile = beam_width)
-    // Prompt phase under tensor parallelism with the per-layer all-reduce OVERLAPPED (GptNeoXContextDecoder.cc:462-465 calls
-    // ftNcclAllReduceSum on the compute stream, nothing runs under it).  The prompt is cut into two micro-batches -- whole
-    // sequences when there are several (their attention is independent), the first and the second half of the tokens of a
-    // single sequence (every GEMM / LayerNorm / residual is row wise, and the second half's attention reads the first half's
-    // K/V from the cache, where the first half's attention call has put them).  A layer runs micro-batch 0, then 1, on the
-    // engine stream; each micro-batch's all-reduce goes to the side stream behind an event, and the NEXT layer's work on that
-    // micro-batch waits for it: the reduction of one half runs under the GEMMs of the other.  Same arithmetic per row as
-    // context_decoder (the all-reduce sums the same values): results are bit-identical to the un-overlapped path.
-    // Chunked prompt phase of ONE sequence (the continuous-batching front end, section 4e of DESIGN.md): the prompt's tokens pass
-    // through all layers `prefill_chunk` at a time -- every GEMM / LayerNorm / residual is row wise, a chunk's attention reads
-    // the earlier chunks' K/V from the cache -- and `prefill_hook` runs between two chunks (the batcher enqueues one decode step
-    // of its running slots there: an admission delays them by one chunk, not by the whole prompt).  The row-wise arithmetic is
-    // that of context_decoder; the split-K form of the GEMMs depends on the row count, so results agree to fp16 rounding of
-    // the GEMM outputs, not bit for bit.
-    // The same from token `prefill_begin` on (the batcher's prefix cache): `prefill_prefix` runs first and puts the K/V of tokens
-    // [0, prefill_begin) into cache row 0, the prompt phase computes the tail only -- in one piece without a hook, in chunks of
-    // `prefill_chunk` with one.  The batcher sets these members before the request and resets them after it.
-    int                   prefill_chunk = 0;
-    std::function<void()> prefill_hook;
-    int                   prefill_begin = 0;
-    std::function<void()> prefill_prefix;
+    // ---- prompt phase: GptNeoXContextDecoder::forward (GptNeoXContextDecoder.cc:283-507) --------------------------------------
+    // The batcher's handles on the prompt phase of ONE sequence (context_decoder_chunked); it sets them before the request and
+    // resets them after it.
+    int                   prefill_chunk = 0;  // with a hook: the prompt's tokens pass through all layers this many at a time
+    std::function<void()> prefill_hook;       // ... and this runs between two chunks
+    int                   prefill_begin = 0;  // the prompt phase starts at this token (the prefix cache's hit length)
+    std::function<void()> prefill_prefix;     // ... after this has put the K/V of tokens [0, prefill_begin) into cache row 0
     // The batcher's logit processors on an admission's FIRST token: when set, every step of the request materialises its logits
     // [rows, V] (no one-launch LM head + greedy step, no captured graph, no speculation) and calls the hook on the engine's stream
     // between the LM head (all-gather included) and the dynamic decode -- the way top_logprobs leaves the one-launch greedy step.
     // Beam requests do not call it.  Set and reset around one forward() like the members above; unset, nothing changes.
     std::function<void(float* logits, int rows, hipStream_t stream)> logits_hook;
+    // the prompt-phase layers of a parallel-residual model (layers.hip.h) over this engine's prompt buffers, cache and streams:
+    // B prompt rows; their K/V go to cache rows b * tile of a cache with B * tile rows (beam search: tile = beam_width)
+    ParallelResidualContextDecoder context_walk(int B, int S, const int* input_lengths, int s_max, int tile)
+    {
+        bind_layers();
+        ParallelResidualContextDecoder d;
+        d.layers = layers.data();
+        d.L = L, d.H = H, d.hl = hl, d.il = il, d.tp = cfg.tensor_para_size;
+        d.px = px, d.pnrm = pnrm, d.pnrm2 = pnrm2, d.pqkv = pqkv, d.pctx = pctx, d.patt = patt, d.pmid = pmid, d.pffn = pffn;
+        d.k_cache = k_cache, d.v_cache = v_cache;
+        d.layer_stride  = (size_t)B * tile * nhl * s_max * dh;
+        d.input_lengths = input_lengths;
+        d.B = B, d.S = S, d.s_max = s_max, d.tile = tile;
+        d.attention = context_attention_layer, d.ffn = ffn_layer;
+        d.stream = stream, d.side = side, d.ov_done = ov_done, d.ov_red = ov_red;
+        return d;
+    }
+    auto prompt_allreduce()  // (what the walk is handed)
+    {
+        return [this](f16* buf, size_t count, hipStream_t st) { allreduce(buf, count, st); };
+    }
     static bool chunked_supported(bool fp32_, int tp, bool gptj, int H_) { return !fp32_ && tp == 1 && gptj && residual_dual_ln_supported(H_); }
+    // Chunked prompt phase of ONE sequence (the continuous-batching front end, section 4e of DESIGN.md): the prompt's tokens pass
+    // through all layers `prefill_chunk` at a time, as token spans of the walk, and `prefill_hook` runs between two chunks (the
+    // batcher enqueues one decode step of its running slots there: an admission delays them by one chunk, not by the whole
+    // prompt).  The same from token `prefill_begin` on (the batcher's prefix cache): `prefill_prefix` runs first, the prompt phase
+    // computes the tail only -- in one piece without a hook, in chunks of `prefill_chunk` with one.
     bool context_decoder_chunked(int S, const int* input_lengths, int s_max, int tile = 1)
     {
         const int sb = prefill_begin;
@@ -682,24 +692,15 @@ struct ftcf_gptneox {
             return false;
         }
         Range r("ftcf.GptNeoXContextDecoder.chunked");
-        bind_layers();
-        const size_t cache_l = (size_t)tile * nhl * s_max * dh;  // (tile = beam_width: the sequence's K/V go to cache row 0 of tile rows)
-        const int    chunk   = (prefill_hook && prefill_chunk > 0) ? prefill_chunk : S;
+        // (tile = beam_width: the sequence's K/V go to cache row 0 of tile rows)
+        const ParallelResidualContextDecoder walk  = context_walk(1, S, input_lengths, s_max, tile);
+        const int                            chunk = (prefill_hook && prefill_chunk > 0) ? prefill_chunk : S;
         if (sb > 0 && prefill_prefix) {
             prefill_prefix();
         }
         for (int s0 = sb; s0 < S; s0 += chunk) {
-            const int s1 = std::min(S, s0 + chunk), m = s1 - s0;
-            f16*      X  = px + (size_t)s0 * H;
-            for (int l = 0; l < L; l++) {
-                const LayerWeights& w = layers[l];
-                launch_residual_dual_ln(X, nullptr, nullptr, nullptr, 1, 0, w.ln1_g, w.ln1_b, w.ln2_g, w.ln2_b, pnrm + (size_t)s0 * H,
-                                        pnrm2 + (size_t)s0 * H, m, H, 1e-5f, stream);
-                context_attention_layer.forward(pnrm, pqkv, pctx, patt, w, input_lengths, k_cache + l * cache_l, v_cache + l * cache_l, 1,
-                                                S, s_max, tile, stream, s0, s1);
-                ffn_layer.forward(pnrm2 + (size_t)s0 * H, pmid + (size_t)s0 * il, pffn + (size_t)s0 * H, w, m, stream);
-                launch_add_bias_attn_ffn_residual(X, pffn + (size_t)s0 * H, patt + (size_t)s0 * H, X, w.ffn2.bias, m, H, 1, 1, true, stream);
-            }
+            const int s1 = std::min(S, s0 + chunk);
+            walk.forward(PromptSpan::token_range(s0, s1), prompt_allreduce());
             if (s1 < S) {
                 prefill_hook();
             }
@@ -707,11 +708,16 @@ struct ftcf_gptneox {
         return true;
     }
 
+    // Prompt phase under tensor parallelism in two micro-batches, the per-layer all-reduce on the side stream
+    // (ParallelResidualContextDecoder::forward_overlapped)
     hipEvent_t ov_done[2] = {nullptr, nullptr}, ov_red[2] = {nullptr, nullptr};
     int        ov_trial = 0;             // auto mode: 0 the next eligible prompt phase runs plain, 1 overlapped, 2 decided
     float      ov_ms[2] = {0.f, 0.f};    // ... what the two trials took (the slowest rank's time)
-    bool       ov_ran = false, ov_eligible = false;  // this request: ran overlapped / counts as a trial
-    bool context_decoder_overlapped(int B, int S, const int* input_lengths, int s_max)
+    bool       ov_ran = false, ov_eligible = false;  // this request (begin() resets them): ran overlapped / counts as a trial
+    // where a single sequence's tokens are cut in two (below 64: too short to be worth two micro-batches)
+    static int prefill_overlap_cut(int S) { return (S / 2) / 64 * 64; }
+    // (no side effects; auto_trial: this request counts as a trial of the auto mode, whichever form it runs)
+    bool prefill_overlap_wanted(int B, int S, bool* auto_trial) const
     {
         // OPT-IN (FTCF_PREFILL_OVERLAP=1; read per request, the tests flip it): on the one GPU the builder has, one rank's shard of
         // the 1024-token prompt phase takes 19.1 -> 27.6 ms (TP 2) / 10.3 -> 18.3 ms (TP 8) in two micro-batches -- GEMMs of 512
@@ -722,79 +728,50 @@ struct ftcf_gptneox {
         // runs plain and is timed, the second one overlapped, every rank learns the slower rank's times (comm_max) and the
         // engine keeps the faster form; ftcf_forward_stats says what ran and what the two trials took.
         const char* ev  = getenv("FTCF_PREFILL_OVERLAP");
-        const bool  aut = (!ev || !strcmp(ev, "auto")) && cfg.tensor_para_size > 1 && cfg.comm && cfg.comm->comm && !cfg.comm->local
-                         && !cfg.comm->hx && cfg.comm->world > 1;
+        const bool  aut = (!ev || !strcmp(ev, "auto")) && rccl_ranks();
         const int   env = (ev && strcmp(ev, "auto")) ? atoi(ev) : 0;
-        ov_ran      = false;
-        ov_eligible = false;
         if ((!env && !aut) || cfg.tensor_para_size == 1 || !cfg.use_gptj_residual || !residual_dual_ln_supported(H) || !side) {
             return false;
         }
+        const bool cut = B >= 2 || prefill_overlap_cut(S) >= 64;
         if (aut) {
-            ov_eligible = (long)B * S >= 512 && (B >= 2 || (S / 2) / 64 * 64 >= 64);
-            const bool want = ov_eligible && (ov_trial == 1 || (ov_trial == 2 && ov_ms[1] < ov_ms[0]));
-            if (!want) {
+            *auto_trial = (long)B * S >= 512 && cut;
+            if (!*auto_trial || !(ov_trial == 1 || (ov_trial == 2 && ov_ms[1] < ov_ms[0]))) {
                 return false;
             }
         }
-        // micro-batches: rows [r0[c], r1[c]) of the [B * S] row space; sequences [b0, b1) x tokens [s0, s1)
-        int b0[2] = {0, 0}, b1[2] = {B, B}, s0[2] = {0, 0}, s1[2] = {S, S};
-        if (B >= 2) {
-            b1[0] = b0[1] = B / 2;
-        }
-        else {
-            const int cut = (S / 2) / 64 * 64;
-            if (cut < 64) {
-                return false;  // too short to be worth two micro-batches
-            }
-            s1[0] = s0[1] = cut;
-        }
-        Range r("ftcf.GptNeoXContextDecoder.overlapped");
-        ov_ran = true;
-        bind_layers();
-        const size_t cache_l = (size_t)B * nhl * s_max * dh;
+        return cut;
+    }
+    void prefill_overlap_events()
+    {
         for (int c = 0; c < 2; c++) {
             if (!ov_done[c]) {
                 FTCF_HIP_CHECK(hipEventCreateWithFlags(&ov_done[c], hipEventDisableTiming));
                 FTCF_HIP_CHECK(hipEventCreateWithFlags(&ov_red[c], hipEventDisableTiming));
             }
         }
-        for (int l = 0; l < L; l++) {
-            const LayerWeights& w = layers[l];
-            for (int c = 0; c < 2; c++) {
-                const size_t row0 = (size_t)b0[c] * S + s0[c];
-                const int    m    = (B >= 2) ? (b1[c] - b0[c]) * S : s1[c] - s0[c];
-                if (l > 0) {
-                    FTCF_HIP_CHECK(hipStreamWaitEvent(stream, ov_red[c], 0));  // this micro-batch's x has been reduced
-                }
-                f16* X = px + row0 * H;
-                launch_residual_dual_ln(X, nullptr, nullptr, nullptr, 1, 0, w.ln1_g, w.ln1_b, w.ln2_g, w.ln2_b, pnrm + row0 * H,
-                                        pnrm2 + row0 * H, m, H, 1e-5f, stream);
-                if (B >= 2) {  // whole sequences [b0, b1): the attention layer on their rows of every buffer
-                    const size_t cb = (size_t)b0[c] * nhl * s_max * dh;
-                    context_attention_layer.forward(pnrm + row0 * H, pqkv + row0 * 3 * hl, pctx + row0 * hl, patt + row0 * H, w,
-                                                    input_lengths + b0[c], k_cache + l * cache_l + cb, v_cache + l * cache_l + cb,
-                                                    b1[c] - b0[c], S, s_max, 1, stream);
-                }
-                else {  // tokens [s0, s1) of the one sequence: the earlier tokens' K/V are in the cache
-                    context_attention_layer.forward(pnrm, pqkv, pctx, patt, w, input_lengths, k_cache + l * cache_l, v_cache + l * cache_l,
-                                                    1, S, s_max, 1, stream, s0[c], s1[c]);
-                }
-                ffn_layer.forward(pnrm2 + row0 * H, pmid + row0 * il, pffn + row0 * H, w, m, stream);
-                launch_add_bias_attn_ffn_residual(X, pffn + row0 * H, patt + row0 * H, X, w.ffn2.bias, m, H, cfg.tensor_para_size,
-                                                  1, true, stream);
-                FTCF_HIP_CHECK(hipEventRecord(ov_done[c], stream));
-                FTCF_HIP_CHECK(hipStreamWaitEvent(side, ov_done[c], 0));
-                allreduce(X, (size_t)m * H, side);
-                FTCF_HIP_CHECK(hipEventRecord(ov_red[c], side));
-            }
+    }
+    // whether this prompt phase ran overlapped: the halves of the sequences when there are several, else the tokens before and
+    // behind the cut of the single one
+    bool context_decoder_overlapped(int B, int S, const int* input_lengths, int s_max)
+    {
+        bool       aut  = false;
+        const bool want = prefill_overlap_wanted(B, S, &aut);
+        ov_eligible     = aut;
+        if (!want) {
+            return false;
         }
-        for (int c = 0; c < 2; c++) {
-            FTCF_HIP_CHECK(hipStreamWaitEvent(stream, ov_red[c], 0));
-        }
+        Range r("ftcf.GptNeoXContextDecoder.overlapped");
+        ov_ran = true;
+        prefill_overlap_events();
+        const int        cut = prefill_overlap_cut(S);
+        const PromptSpan sp0 = B >= 2 ? PromptSpan::sequences(0, B / 2) : PromptSpan::token_range(0, cut);
+        const PromptSpan sp1 = B >= 2 ? PromptSpan::sequences(B / 2, B) : PromptSpan::token_range(cut, S);
+        context_walk(B, S, input_lengths, s_max, 1).forward_overlapped(sp0, sp1, prompt_allreduce());
         return true;
     }
 
+    // B prompt rows; their K/V go to cache rows b * tile of a cache with B * tile rows (beam search: tile = beam_width)
     void context_decoder(int B, int S, const int* input_lengths, int s_max, int tile)
     {
         if (B == 1 && context_decoder_chunked(S, input_lengths, s_max, tile)) {  // (tile > 1: a beam request's prompt)
@@ -805,50 +782,26 @@ struct ftcf_gptneox {
             return;
         }
         Range r("ftcf.GptNeoXContextDecoder");
+        if (cfg.use_gptj_residual) {  // the whole batch on the engine stream
+            context_walk(B, S, input_lengths, s_max, tile).forward(PromptSpan::sequences(0, B), prompt_allreduce());
+            return;
+        }
         bind_layers();
         const int    M       = B * S;
         const size_t cache_l = (size_t)B * tile * nhl * s_max * dh;
-        // parallel-residual layers: both LayerNorms in one pass, fused with the previous layer's residual when no collective
-        // sits in between (as in the batched decode path)
-        const bool dual = cfg.use_gptj_residual && residual_dual_ln_supported(H);
-        const bool tp1  = cfg.tensor_para_size == 1;
         for (int l = 0; l < L; l++) {
             const LayerWeights& w = layers[l];
-            if (!dual) {
-                launch_layernorm(px, w.ln1_g, w.ln1_b, pnrm, M, H, 1e-5f, true, stream);
-            }
-            else if (l == 0 || !tp1) {
-                launch_residual_dual_ln(px, nullptr, nullptr, nullptr, 1, 0, w.ln1_g, w.ln1_b, w.ln2_g, w.ln2_b, pnrm, pnrm2,
-                                        M, H, 1e-5f, stream);
-            }
+            // sequential residual (GptNeoXContextDecoder.cc:401-418,463-470): the TensorParallel layers reduce their
+            // own outputs; h = attn + bias + x ; x' = ffn(LN2(h)) + bias + h
+            launch_layernorm(px, w.ln1_g, w.ln1_b, pnrm, M, H, 1e-5f, true, stream);
             context_attention_layer.forward(pnrm, pqkv, pctx, patt, w, input_lengths, k_cache + l * cache_l, v_cache + l * cache_l, B, S,
                                             s_max, tile, stream);
-            if (!cfg.use_gptj_residual) {
-                // sequential residual (GptNeoXContextDecoder.cc:401-418,463-470): the TensorParallel layers reduce their
-                // own outputs; h = attn + bias + x ; x' = ffn(LN2(h)) + bias + h
-                allreduce(patt, (size_t)M * H);
-                launch_add_bias_residual(patt, px, patt, w.attn_out.bias, M, H, stream);
-                launch_layernorm(patt, w.ln2_g, w.ln2_b, pnrm, M, H, 1e-5f, true, stream);
-                ffn_layer.forward(pnrm, pmid, pffn, w, M, stream);
-                allreduce(pffn, (size_t)M * H);
-                launch_add_bias_residual(px, pffn, patt, w.ffn2.bias, M, H, stream);
-                continue;
-            }
-            if (!dual) {
-                launch_layernorm(px, w.ln2_g, w.ln2_b, pnrm, M, H, 1e-5f, true, stream);
-            }
-            ffn_layer.forward(dual ? pnrm2 : pnrm, pmid, pffn, w, M, stream);
-            // layer_input == layer_output for every layer with padding removal -> fp32-sum variant (:311-322,:445-461)
-            if (dual && tp1) {
-                const LayerWeights* nx = l + 1 < L ? &layers[l + 1] : nullptr;
-                launch_residual_dual_ln(px, pffn, patt, w.ffn2.bias, 1, 1, nx ? nx->ln1_g : nullptr, nx ? nx->ln1_b : nullptr,
-                                        nx ? nx->ln2_g : nullptr, nx ? nx->ln2_b : nullptr, pnrm, pnrm2, M, H, 1e-5f, stream);
-            }
-            else {
-                launch_add_bias_attn_ffn_residual(px, pffn, patt, px, w.ffn2.bias, M, H, cfg.tensor_para_size, 1, true,
-                                                  stream);
-            }
-            allreduce(px, (size_t)M * H);
+            allreduce(patt, (size_t)M * H);
+            launch_add_bias_residual(patt, px, patt, w.attn_out.bias, M, H, stream);
+            launch_layernorm(patt, w.ln2_g, w.ln2_b, pnrm, M, H, 1e-5f, true, stream);
+            ffn_layer.forward(pnrm, pmid, pffn, w, M, stream);
+            allreduce(pffn, (size_t)M * H);
+            launch_add_bias_residual(px, pffn, patt, w.ffn2.bias, M, H, stream);
         }
     }
 
@@ -1364,6 +1317,7 @@ struct ftcf_gptneox {
         ses.active = false;
     }
     void begin(const ftcf_forward_args& a);
+    void prompt_phase(const ftcf_forward_args& a, const int* in_ids, const int* in_len);
     void enqueue_step(bool with_decoder);
     int  step(int max_steps);
     int  step_speculative(int max_steps);

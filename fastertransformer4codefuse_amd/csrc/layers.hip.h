@@ -2,18 +2,22 @@
 // HIP launches on a caller-given stream.  No layer owns memory (the reference's allocateBuffer / freeBuffer per call,
 // DecoderSelfAttentionLayer.cc:148-187, FfnLayer.cc:455-530, are the engine's one arena: engine.hip plan()), no layer
 // synchronises, and none calls a collective itself: a parallel-residual layer reduces x' ONCE, after the residual
-// (GptNeoXDecoder.cc:342-359), which is the decoder's business -- ParallelResidualDecoder is handed the all-reduce by its caller.
+// (GptNeoXDecoder.cc:342-359), which is the decoder's business -- the two walks are handed the all-reduce by their caller.
 //
 //   DecoderSelfAttentionLayer  <- layers/attention_layers/DecoderSelfAttentionLayer.cc:459-686 (+ TensorParallel wrapper :190-226)
 //   GptContextAttentionLayer   <- layers/attention_layers/GptContextAttentionLayer.cc:25-403
 //   FfnLayer (GeluFfnLayer)    <- layers/FfnLayer.cc:34-380, TensorParallelGeluFfnLayer.cc:33-63
 //   ParallelResidualDecoder    <- models/gptneox/GptNeoXDecoder.cc:245-384 (use_gptj_residual), the batched decode rows
+//   ParallelResidualContextDecoder <- models/gptneox/GptNeoXContextDecoder.cc:283-507 (use_gptj_residual), the prompt rows
 //   DynamicDecodeLayer         <- layers/DynamicDecodeLayer.cc:192-497 (sampling layers, online beam search)
 //
 // ParallelResidualDecoder is the ONE walk over the layers of a batched decode step: the engine's general path and its overlapped
 // form, the speculative verify pass and the continuous batcher (plain and overlapped) run it with their own attention launch,
-// buffers and GEMM binding.  The fused forms -- the persistent decode kernel (persist_device.hip.h), the rows kernel, the
-// per-stage GEMV launches -- cut ACROSS these units on purpose and stay in engine.hip.
+// buffers and GEMM binding.  ParallelResidualContextDecoder is the ONE walk over the layers of the prompt phase: the whole batch,
+// the token ranges of a chunked admission or of a prefix hit's tail, and the two micro-batches of the overlapped form are spans
+// (PromptSpan) of the same per-layer body.  The fused forms -- the persistent decode kernel (persist_device.hip.h), the rows
+// kernel, the per-stage GEMV launches -- cut ACROSS these units on purpose and stay in engine.hip; so do the sequential-residual
+// loops and the fp32 instantiation.
 #pragma once
 #include <functional>
 #include <vector>
@@ -304,6 +308,131 @@ private:
             launch_add_bias_attn_ffn_residual(xr, ffnc, attc, xr, w.ffn2.bias, M, H, tp, inplace, true, s);
             if (!tp1) {
                 reduce(xr, (size_t)M * H, false);
+            }
+        }
+    }
+};
+
+// The rows of the prompt buffers one call of the prompt-phase walk works on: whole sequences [b0, b1) of the batch, or tokens
+// [s0, s1) of the ONE sequence of a batch of one (the earlier tokens' K/V are in the cache: a chunk, a prefix hit's tail, a half)
+struct PromptSpan {
+    int  b0 = 0, b1 = 0, s0 = 0, s1 = 0;
+    bool tokens = false;
+    static PromptSpan sequences(int b0, int b1) { return {b0, b1, 0, 0, false}; }
+    static PromptSpan token_range(int s0, int s1) { return {0, 1, s0, s1, true}; }
+};
+
+// The layers of the prompt phase of a parallel-residual model (GptNeoXContextDecoder.cc:283-507) over the prompt buffers
+// [B * S, .] and a K/V cache of B * tile rows per layer (beam search: tile = beam_width, sequence b's K/V in cache row b * tile):
+// per layer the entry LayerNorms (one dual-LN pass over x), the context attention layer, the FFN and the closing residual -- fused
+// into the next layer's LayerNorm pass where no all-reduce of x' stands in between, the same rule for every span.  The callers pass
+//   allreduce(buf, count, s): the layer's all-reduce of x' on stream s
+struct ParallelResidualContextDecoder {
+    const LayerWeights* layers = nullptr;
+    int                 L = 0, H = 0, hl = 0, il = 0, tp = 1;
+    // the prompt buffers, row-major: px / pnrm / pnrm2 / patt / pffn [B * S, H], pqkv [B * S, 3 hl], pctx [B * S, hl], pmid [B * S, il]
+    f16 *px = nullptr, *pnrm = nullptr, *pnrm2 = nullptr, *pqkv = nullptr, *pctx = nullptr, *patt = nullptr, *pmid = nullptr, *pffn = nullptr;
+    f16 *                    k_cache = nullptr, *v_cache = nullptr;  // layer l's K/V at + l * layer_stride
+    size_t                   layer_stride = 0;                       // B * tile * heads of this rank * s_max * size_per_head
+    const int*               input_lengths = nullptr;
+    int                      B = 0, S = 0, s_max = 0, tile = 1;
+    GptContextAttentionLayer attention;
+    FfnLayer                 ffn;
+    hipStream_t              stream = nullptr, side = nullptr;      // side: the reductions of forward_overlapped
+    const hipEvent_t *       ov_done = nullptr, *ov_red = nullptr;  // [2] each, forward_overlapped
+
+    // all layers for one span on `stream`.  A token span [s0, s1) with s0 > 0 is a piece of a chunked prompt phase or the tail
+    // behind a prefix whose K/V the caller has put into the cache: every GEMM / LayerNorm / residual is row wise and the span's
+    // attention reads the earlier tokens' K/V from the cache, so the arithmetic per row is that of the whole prompt; the split-K
+    // form of the GEMMs depends on the row count, so the pieces agree with the whole to fp16 rounding of the GEMM outputs, not bit
+    // for bit.
+    template<typename AllReduce>
+    void forward(const PromptSpan& span, AllReduce&& allreduce) const
+    {
+        check(span);
+        for (int l = 0; l < L; l++) {
+            layer(l, span, stream, [&](f16* buf, size_t count) { allreduce(buf, count, stream); });
+        }
+    }
+
+    // Two micro-batches under tensor parallelism with the per-layer all-reduce OVERLAPPED (GptNeoXContextDecoder.cc:462-465 calls
+    // ftNcclAllReduceSum on the compute stream, nothing runs under it): whole sequences when there are several (their attention is
+    // independent), the first and the second part of the tokens of a single sequence (the second part's attention reads the first
+    // part's K/V from the cache, where the first part's attention call has put them).  A layer runs micro-batch 0, then 1, on
+    // `stream`; each micro-batch's all-reduce goes to `side` behind an event, and the NEXT layer's work on that micro-batch waits
+    // for it: the reduction of one runs under the GEMMs of the other.  Same arithmetic per row as forward() of the whole batch (the
+    // all-reduce sums the same values): bit-identical to it as long as the GEMMs take the same form.  Needs tp > 1.
+    template<typename AllReduce>
+    void forward_overlapped(const PromptSpan& span0, const PromptSpan& span1, AllReduce&& allreduce) const
+    {
+        const PromptSpan span[2] = {span0, span1};
+        check(span0);
+        check(span1);
+        for (int l = 0; l < L; l++) {
+            for (int c = 0; c < 2; c++) {
+                if (l > 0) {
+                    FTCF_HIP_CHECK(hipStreamWaitEvent(stream, ov_red[c], 0));  // this micro-batch's x has been reduced
+                }
+                layer(l, span[c], stream, [&](f16* buf, size_t count) {
+                    FTCF_HIP_CHECK(hipEventRecord(ov_done[c], stream));
+                    FTCF_HIP_CHECK(hipStreamWaitEvent(side, ov_done[c], 0));
+                    allreduce(buf, count, side);
+                    FTCF_HIP_CHECK(hipEventRecord(ov_red[c], side));
+                });
+            }
+        }
+        for (int c = 0; c < 2; c++) {
+            FTCF_HIP_CHECK(hipStreamWaitEvent(stream, ov_red[c], 0));
+        }
+    }
+
+private:
+    void check(const PromptSpan& sp) const
+    {
+        // (GptContextAttentionLayer::forward cuts a token range out of base pointers, and only for a single sequence)
+        FTCF_CHECK_ARG(sp.tokens ? (B == 1 && 0 <= sp.s0 && sp.s0 < sp.s1 && sp.s1 <= S) : (0 <= sp.b0 && sp.b0 < sp.b1 && sp.b1 <= B),
+                       "a prompt span is sequences [b0, b1) of the batch or a token range [s0, s1) of a batch of one sequence");
+    }
+
+    // layer l for the rows of `sp` on stream s; reduce(buf, count): the layer's all-reduce as the walk mode orders it
+    template<typename Reduce>
+    void layer(int l, const PromptSpan& sp, hipStream_t s, Reduce&& reduce) const
+    {
+        const LayerWeights& w  = layers[l];
+        const LayerWeights* nx = l + 1 < L ? &layers[l + 1] : nullptr;
+        const bool   dual = residual_dual_ln_supported(H), tp1 = tp == 1;
+        const size_t o = sp.tokens ? (size_t)sp.s0 : (size_t)sp.b0 * S;
+        const int    M = sp.tokens ? sp.s1 - sp.s0 : (sp.b1 - sp.b0) * S;
+        f16 *const   xr = px + o * H, *const n1 = pnrm + o * H, *const n2 = pnrm2 + o * H, *const at = patt + o * H, *const ff = pffn + o * H;
+        f16 *const   kl = k_cache + l * layer_stride, *const vl = v_cache + l * layer_stride;
+        // both LayerNorms of the layer come from one pass over x, fused with the previous layer's residual when there is no
+        // collective in between
+        if (!dual) {
+            launch_layernorm(xr, w.ln1_g, w.ln1_b, n1, M, H, 1e-5f, true, s);
+            launch_layernorm(xr, w.ln2_g, w.ln2_b, n2, M, H, 1e-5f, true, s);
+        }
+        else if (l == 0 || !tp1) {
+            launch_residual_dual_ln(xr, nullptr, nullptr, nullptr, 1, 0, w.ln1_g, w.ln1_b, w.ln2_g, w.ln2_b, n1, n2, M, H, 1e-5f, s);
+        }
+        if (sp.tokens) {  // base pointers + the range: the earlier tokens' K/V are in the cache
+            attention.forward(pnrm, pqkv, pctx, patt, w, input_lengths, kl, vl, 1, S, s_max, tile, s, sp.s0, sp.s1);
+        }
+        else {  // whole sequences: the attention layer on their rows of every buffer and their rows of the cache
+            const size_t cb = (size_t)sp.b0 * (layer_stride / B);
+            attention.forward(n1, pqkv + o * 3 * hl, pctx + o * hl, at, w, input_lengths + sp.b0, kl + cb, vl + cb, sp.b1 - sp.b0, S,
+                              s_max, tile, s);
+        }
+        ffn.forward(n2, pmid + o * il, ff, w, M, s);
+        // layer_input == layer_output for every layer with padding removal -> fp32-sum variant of the residual
+        // (GptNeoXContextDecoder.cc:311-322,:445-461), whatever l is
+        if (dual && tp1) {
+            launch_residual_dual_ln(xr, ff, at, w.ffn2.bias, 1, 1, nx ? nx->ln1_g : nullptr, nx ? nx->ln1_b : nullptr,
+                                    nx ? nx->ln2_g : nullptr, nx ? nx->ln2_b : nullptr, n1, n2, M, H, 1e-5f, s);
+        }
+        else {
+            launch_add_bias_attn_ffn_residual(xr, ff, at, xr, w.ffn2.bias, M, H, tp, 1, true, s);
+            if (!tp1) {
+                reduce(xr, (size_t)M * H);
             }
         }
     }

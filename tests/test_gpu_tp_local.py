@@ -38,7 +38,7 @@ def gh():
 
 
 def run_tp(gh, cfg, w, tp, int8_mode, ids, lens, out, **kw):
-    """All `tp` ranks in threads; returns the list of per-rank results (run_op dicts + 'decode_path')."""
+    """All `tp` ranks in threads; returns the list of per-rank results (run_op dicts + 'decode_path', 'prefill_overlap')."""
     from fastertransformer4codefuse_amd.gptneox_op import LocalTensorParallelGroup
     group = LocalTensorParallelGroup()
     res, err = [None] * tp, []
@@ -48,6 +48,7 @@ def run_tp(gh, cfg, w, tp, int8_mode, ids, lens, out, **kw):
             op = gh.make_op(cfg, shard_weights(cfg, w, tp, r), int8_mode=int8_mode, tp=tp, rank=r, comm=group)
             res[r] = gh.run_op(op, ids, lens, out, cfg["vocab_size"], **kw)
             res[r]["decode_path"] = op.stats()["decode_path"]
+            res[r]["prefill_overlap"] = op.stats()["prefill_overlap"]
         except BaseException as e:  # noqa: BLE001 (reported below; the other ranks are stuck in a collective then)
             err.append((r, e))
 
@@ -175,11 +176,58 @@ def test_prompt_phase_with_overlapped_all_reduce_is_bit_identical(gh, monkeypatc
     monkeypatch.setenv("FTCF_PREFILL_OVERLAP", "0")
     plain = run_tp(gh, cfg, w, 2, 0, ids, lens, out, top_k=1)
     for r in range(2):
+        # (the engine's own word that the overlapped form ran, and that the other leg is the plain path)
+        assert ov[r]["prefill_overlap"] == 1 and plain[r]["prefill_overlap"] == 0
         assert ov[r]["output_ids"].tolist() == plain[r]["output_ids"].tolist()
         np.testing.assert_array_equal(ov[r]["logits"], plain[r]["logits"])
     monkeypatch.delenv("FTCF_GEMM_SPLITK")
     monkeypatch.setenv("FTCF_PREFILL_OVERLAP", "1")
     ov = run_tp(gh, cfg, w, 2, 0, ids, lens, out, top_k=1)
+    assert [ov[r]["prefill_overlap"] for r in range(2)] == [1, 1]
     op1 = gh.make_op(cfg, w)
     r1 = gh.run_op(op1, ids, lens, out, cfg["vocab_size"], top_k=1)
     check_against(r1["output_ids"], r1["logits"], ov[0], S, f"overlapped prefill {shape} vs tp1 engine")
+
+
+def test_prefill_overlap_flag_does_not_outlive_its_request(gh, monkeypatch):
+    """`prefill_overlap` of the stats speaks of the request that just ran: an op whose first request ran the overlapped prompt
+    phase (two sequences: the sequence cut, no minimum length) and whose second one has no prompt phase at all (max_input_len = 1)
+    reports 1, then 0 -- and the second request's tokens are those of a fresh op."""
+    from fastertransformer4codefuse_amd.gptneox_op import LocalTensorParallelGroup
+    cfg = MID
+    w = random_model(cfg, seed=21)
+    ids = np.random.RandomState(10).randint(3, cfg["vocab_size"], size=(2, 8)).astype(np.int32)
+    monkeypatch.setenv("FTCF_PREFILL_OVERLAP", "1")
+
+    def run(requests):
+        """Both ranks in threads, ONE op per rank for all `requests`; per rank a list of (tokens, prefill_overlap)."""
+        group = LocalTensorParallelGroup()
+        res, err = [None] * 2, []
+
+        def worker(r):
+            try:
+                op = gh.make_op(cfg, shard_weights(cfg, w, 2, r), tp=2, rank=r, comm=group)
+                got = []
+                for q in requests:
+                    o = gh.run_op(op, q, [q.shape[1]] * 2, 2, cfg["vocab_size"], return_logits=False, top_k=1)
+                    got.append((o["output_ids"].tolist(), op.stats()["prefill_overlap"]))
+                res[r] = got
+            except BaseException as e:  # noqa: BLE001 (reported below; the other rank is stuck in a collective then)
+                err.append((r, e))
+
+        ths = [threading.Thread(target=worker, args=(r,), daemon=True) for r in range(2)]
+        for t in ths:
+            t.start()
+        for t in ths:
+            t.join(timeout=300)
+        assert not err, err
+        assert all(r is not None for r in res), "a rank did not finish (stuck in a collective?)"
+        return res
+
+    both = run([ids, ids[:, :1]])
+    fresh = run([ids[:, :1]])
+    for r in range(2):
+        assert both[r][0][1] == 1, "two sequences of 8 tokens run the overlapped prompt phase"
+        assert both[r][1][1] == 0, "a request without a prompt phase inherited the previous request's flag"
+        assert fresh[r][0][1] == 0
+        assert both[r][1][0] == fresh[r][0][0]
