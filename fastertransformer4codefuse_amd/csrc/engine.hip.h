@@ -1,9 +1,11 @@
 // The engine behind GptNeoXOp (models/gptneox/GptNeoX.cc:386-1052): the structure every engine translation unit sees --
-// engine.hip defines the request loop and the C ABI, batcher.hip the continuous-batching front end that borrows an engine.
+// engine.hip defines the request lifecycle (begin / step / finish as named stages) and its C ABI `ftcf_gptneox_*`, batcher.hip the
+// continuous-batching front end that borrows an engine, capi_kernels.hip the stand-alone kernel-level entry points.  Here: the
+// arena plan, the decoder paths and what the units share (GEMM dispatch, the routing of the sampling arguments, the knobs).
 #pragma once
 #include "comm.hip.h"
 
-// (engine.hip) GEMM / LM-head dispatch shared with the batcher
+// (engine.hip) GEMM / LM-head dispatch shared with the batcher and capi_kernels.hip
 void gemm_dispatch(const f16* A, const void* W, const f16* scale, const f16* bias, int act, f16* C, int m, int n, int k, bool int8,
                    hipStream_t s, float* smallm_ws = nullptr, size_t smallm_partial = 0, int num_cu = 256, const int* d_step = nullptr,
                    unsigned* smallm_seq = nullptr, float* tiled_ws = nullptr);
@@ -55,9 +57,83 @@ enum { KIND_LN_GEMV = 0, KIND_SPLITK = 1, KIND_LM_HEAD = 2, KIND_FUSED = 3, KIND
 
 }  // namespace
 
-__global__ void k_transpose_gathered_logits(float* out, const float* in, int tp, int B, int vl, int src);  // (defined below)
+// a runtime argument given once or per request, as a vector of B (engine.hip begin(), capi_kernels.hip's one-step entries)
 template<typename T>
-__global__ void k_scale_by_tp(T* buf, size_t n, float tp);  // (defined below)
+static std::vector<T> broadcast_arg(const T* p, int n, int B, T dflt, const char* name)
+{
+    std::vector<T> v((size_t)B, dflt);
+    if (n > 0) {
+        FTCF_CHECK_ARG(p != nullptr, std::string(name) + " pointer is NULL");
+        FTCF_CHECK_ARG(n == 1 || n == B, std::string(name) + " must have 1 or batch_size entries");
+        for (int b = 0; b < B; b++) {
+            v[b] = p[n == 1 ? 0 : b];
+        }
+    }
+    return v;
+}
+
+// The runtime-arg routing of TopKSamplingLayer.cu:27-77 / TopPSamplingLayer.cu:30-110 and the ALL_OF switches of
+// BaseSamplingLayer.cc:283-313, in ONE place (the engine's begin() and the kernel-level ftcf_dynamic_decode_step): from the
+// broadcast host arguments to what the decode kernels read.  k == 0 && p == 0 is greedy (k = 1), k is cut at 1024, a top-k row
+// without a p samples from all of its k, and a penalty switches on for the batch as soon as one row differs from its default.
+struct SamplingRouting {
+    std::vector<int>   k_eff;           // per row: the k of the top-k layer, 0 = the row belongs to the top-p layer
+    std::vector<float> p_topk, p_topp;  // per row: the p each layer uses
+    int  max_top_k = 1, any_top_p = 0, apply_temperature = 0, apply_repetition = 0;
+    bool any_min = false, rep_given = false;
+    // the host view of the batch; sp.repetition_penalty / sp.min_length hold the device copies and are dropped where not given
+    void apply(SamplingParams& sp) const
+    {
+        sp.max_top_k         = max_top_k;
+        sp.any_top_p         = any_top_p;
+        sp.apply_temperature = apply_temperature;
+        sp.apply_repetition  = apply_repetition;
+        if (!rep_given) {
+            sp.repetition_penalty = nullptr;
+        }
+        if (!any_min) {
+            sp.min_length = nullptr;
+        }
+    }
+};
+static SamplingRouting route_sampling_args(const std::vector<int>& top_k, const std::vector<float>& top_p, const std::vector<float>& temp,
+                                           const std::vector<float>& rep, const std::vector<int>& minl, bool rep_given)
+{
+    const int       batch = (int)top_k.size();
+    SamplingRouting r;
+    r.k_eff.resize(batch);
+    r.p_topk.resize(batch);
+    r.p_topp.resize(batch);
+    r.rep_given = rep_given;
+    bool temp_all_one = true, rep_all_default = true;
+    for (int b = 0; b < batch; b++) {
+        int   k = top_k[b];
+        float p = top_p[b];
+        FTCF_CHECK_ARG(k >= 0, "top_k must be >= 0");
+        if (k == 0 && p == 0.0f) {
+            k = 1;
+        }
+        float pk = p;
+        if (k > 0 && pk == 0.0f) {
+            pk = 1.0f;
+        }
+        r.k_eff[b]  = k > 1024 ? 1024 : k;
+        r.p_topk[b] = pk < 0.f ? 0.f : (pk > 1.f ? 1.f : pk);
+        r.p_topp[b] = p < 0.f ? 0.f : (p > 1.f ? 1.f : p);
+        temp_all_one &= (temp[b] == 1.0f);
+        rep_all_default &= (rep[b] == 1.0f);
+        r.any_min |= (minl[b] > 0);
+        r.max_top_k = std::max(r.max_top_k, r.k_eff[b]);
+        r.any_top_p |= (r.k_eff[b] == 0);
+    }
+    r.apply_temperature = temp_all_one ? 0 : 1;
+    r.apply_repetition  = (rep_given && !rep_all_default) ? 1 : 0;
+    return r;
+}
+
+__global__ void k_transpose_gathered_logits(float* out, const float* in, int tp, int B, int vl, int src);  // (engine.hip)
+template<typename T>
+__global__ void k_scale_by_tp(T* buf, size_t n, float tp);  // (engine.hip)
 
 struct ftcf_gptneox {
     ftcf_gptneox_config       cfg{};
@@ -134,7 +210,7 @@ struct ftcf_gptneox {
     int*                tp_scratch = nullptr;  // device int for the barrier all-reduce of the tensor-parallel windows
     long long*          ps_ts = nullptr;  // FTCF_PERSIST_TS=<file>: in-kernel stamps of the last token
     // persistent decode layers for 3..16 rows (kernels_rows.hip): on whenever the shape is eligible (FTCF_ROWS=0: general path)
-    int                 rows = 1, rows_nb = 0, rows_min = -1;  // rows_min < 0: see plan()
+    int                 rows = 1, rows_nb = 0;
     RowsPlan            rplan{};
     char*               rows_ws = nullptr;
     long long*          rows_ts = nullptr;
@@ -161,12 +237,7 @@ struct ftcf_gptneox {
         for (void* p : owned) {
             (void)hipFree(p);
         }
-        if (ses.graph_exec) {
-            (void)hipGraphExecDestroy(ses.graph_exec);
-        }
-        if (ses.graph_exec_n) {
-            (void)hipGraphExecDestroy(ses.graph_exec_n);
-        }
+        destroy_graphs();
         if (tp_scratch) {
             (void)hipFree(tp_scratch);
         }
@@ -255,6 +326,149 @@ struct ftcf_gptneox {
     }
 
     // ---- arena planning: everything a request of shape (B, S, total) needs, carved once ----
+    // The blocks of plan() below, in the order plan() carves them; each sets its own views (and plans) from the Carver it is given
+    // and is run twice, first over no memory to learn the size.
+
+    // Whether a request of B rows x K beams may take the one- / two-row persistent kernel.  planned = false is what begin() asks
+    // BEFORE the ranks' exchange window exists (is one worth building?): the knobs and the request's shape only; planned = true is
+    // plan()'s question: the engine's own limits and the window as well.
+    // (L <= 255: the hand-off tags carry the layer in their low byte; tpn <= 8: the exchange-window table of the kernel)
+    bool persist_eligible(int B, int K, bool planned) const
+    {
+        const int  tpn   = cfg.tensor_para_size;
+        const bool shape = persist && K == 1 && B <= 2 && cfg.use_gptj_residual && tpn <= PERSIST_MAX_TP && (tpn == 1 || persist_tp);
+        return shape && (!planned || (!fp32 && L <= 255 && (tpn == 1 || (cfg.comm && cfg.comm->win_ok))));
+    }
+    // With tensor parallelism the per-layer all-reduce happens INSIDE the persistent launch, through the ranks'
+    // exchange windows (persist_device.hip.h ps_tp_exchange); where the windows are not available (peer mapping or
+    // hand-shake failed, FTCF_TP_PERSIST=0) the per-stage launches + RCCL all-reduce stay in charge.
+    void plan_persistent(Carver& c, int B, int K, int s_max)
+    {
+        pplan = PersistPlan{};
+        const int  tpn      = cfg.tensor_para_size;
+        const bool tp_local = tpn > 1 && cfg.comm && cfg.comm->local;
+        if (persist_eligible(B, K, true)) {
+            // (a local group shares ONE device: every rank gets 1 / world of its compute units)
+            const int nb = tp_local ? std::max(1, (persist_nb > 0 ? persist_nb : num_cu) / tpn) : persist_nb;
+            pplan = persist_plan(B, H, hl, il, nhl, dh, s_max, int8, num_cu, nb, persist_cs1, persist_cs3, persist_own, L);
+            const bool resident = !pplan.ok ? false
+                                  : tp_local ? persist_group_resident(pplan, int8, B, dh, num_cu, tpn)
+                                             : persist_resident(pplan, int8, B, dh, num_cu, tpn);
+            if (!resident) {
+                pplan = PersistPlan{};  // not every workgroup would be resident: the hand-offs could never complete
+            }
+        }
+        if (pplan.ok) {
+            ps_slab_n   = (size_t)B * 3 * hl / 2 + (size_t)B * il / 2 + (size_t)B * hl / 2 + (size_t)B * H / 2
+                        + (size_t)pplan.gp_n + (size_t)B * nhl * pplan.nsplit * (dh + 2);
+            ps_gq       = c.take<unsigned long long>(ps_slab_n + 8);
+            ps_gm       = ps_gq ? ps_gq + (size_t)B * 3 * hl / 2 : nullptr;
+            ps_gc       = ps_gq ? ps_gm + (size_t)B * il / 2 : nullptr;
+            ps_gx       = ps_gq ? ps_gc + (size_t)B * hl / 2 : nullptr;
+            ps_gp       = ps_gq ? ps_gx + (size_t)B * H / 2 : nullptr;
+            ps_ga       = ps_gq ? ps_gp + (size_t)pplan.gp_n : nullptr;
+            ps_err      = ps_gq ? reinterpret_cast<int*>(ps_gq + ps_slab_n) : nullptr;
+            d_players   = c.take<PersistLayer>(L);
+            ps_tab      = c.take<char>(persist_table_bytes(pplan) * pplan.NB);
+            ps_tab_ready = false;
+            ps_ts       = ps_ts_file.empty() ? nullptr : c.take<long long>((size_t)pplan.NB * L * 128);
+        }
+    }
+    // 3..16 rows (and what the one- / two-row kernel does not take): the rows kernel, one launch per token.  With tensor
+    // parallelism it would be one launch per layer and the all-reduce of x' between them: a rank's shard of a layer is a few
+    // microseconds of HBM time behind five in-kernel hand-offs, and the paired launches of the general path are faster
+    // (one rank's shard of TP 8 at bs 16: 2.67 against 1.69 ms per step): tensor_para_size 1 only
+    void plan_rows(Carver& c, int B, int K, int s_max)
+    {
+        rplan = RowsPlan{};
+        rows_ws = nullptr;
+        rows_ts = nullptr;
+        // One and two rows are the one- / two-row kernel's; where ITS plan declines a request (fp16 weights at two rows, more than
+        // 1248 / 3072 tokens of context: its LDS) the rows kernel takes it -- 2.73 ms per token at one row against 3.2 on the
+        // per-stage launches, 3.10 at two rows against 3.48 on the general path (13B int8, 1024-in / 512-out) -- but not when
+        // that kernel has been switched off (FTCF_PERSIST=0, or after it gave up once): then the per-stage launches run, the path
+        // of a tensor-parallel rank
+        const int rmin = persist ? 1 : 3;
+        if (rows && cfg.tensor_para_size == 1 && !pplan.ok && !fp32 && K == 1 && B >= rmin && B <= 16
+            && cfg.use_gptj_residual && L <= 255) {
+            rplan = rows_plan(B, H, hl, il, nhl, dh, s_max, int8, num_cu, rows_nb > 0 ? rows_nb : persist_nb);
+            if (rplan.ok && !rows_resident(rplan, int8, dh, num_cu, false)) {
+                rplan = RowsPlan{};
+            }
+            if (rplan.ok) {
+                rows_ws   = c.take<char>(rows_workspace_bytes(rplan, B, H, hl, il, nhl, dh));
+                d_players = c.take<PersistLayer>(L);  // (the persistent plan, which has a table of its own, is off here)
+                rows_ts   = ps_ts_file.empty() ? nullptr : c.take<long long>((size_t)rplan.NB * L * 128);
+            }
+        }
+    }
+    // the split-K workspaces of the burst GEMM (5..16 rows per launch) and of the tiled GEMM (17..768 rows)
+    void plan_gemm_workspaces(Carver& c, int B, int S, int K)
+    {
+        // (the four GEMMs of a layer may be in flight together: one region each)
+        // (17..SMALLM_MAX_ROWS rows run the same kernel in chunks of 16 rows: sized for one chunk)
+        // (a prompt phase of up to SMALLM_MAX_ROWS tokens in all is HBM bound like a decode step: it takes the same kernel)
+        const int  bc         = 16;
+        const long prefill_m  = S > 1 ? (long)(B / K) * S : 0;
+        // (tensor parallel: up to 32 rows as two micro-batches of <= 16, each with its own regions -- decoder_overlapped)
+        const bool decode_ws  = B > STAGE_MAX_ROWS && (B <= SMALLM_MAX_ROWS || (cfg.tensor_para_size > 1 && B <= 32));
+        const bool prefill_ws = prefill_m > 4 && prefill_m <= SMALLM_MAX_ROWS;
+        smallm_partial = gemm_smallm_workspace_bytes(bc, 3 * hl, H, int8) + gemm_smallm_workspace_bytes(bc, il, H, int8)
+                         + gemm_smallm_workspace_bytes(bc, H, hl, int8) + gemm_smallm_workspace_bytes(bc, H, il, int8);
+        smallm_region  = smallm_partial;
+        smallm_partial *= cfg.tensor_para_size > 1 ? 2 : 1;
+        smallm_ws = (!fp32 && (decode_ws || prefill_ws)) ? c.take<float>((smallm_partial + gemm_smallm_ticket_bytes()) / 4) : nullptr;
+        const bool tiled_rows = prefill_m > 16 || (B > 16 && B <= gemm_tiled_splitk_max_m());
+        tiled_ws              = (!fp32 && tiled_rows) ? c.take<float>(gemm_tiled_workspace_bytes() / 4) : nullptr;
+    }
+    // beam search (rows = batch * K)
+    void plan_beams(Carver& c, int B, int S, int total, int K)
+    {
+        const int s_max = total;
+        tiled_ids   = c.take<int>((size_t)B * S);
+        tiled_len   = c.take<int>(B);
+        parent_ids  = c.take<int>((size_t)total * B);
+        cache_indir = c.take<int>((size_t)2 * B * s_max);
+        beam_ws     = c.take<char>(beam_workspace_bytes(B / K, K));
+        d_div       = c.take<float>(B);
+        d_lenpen    = c.take<float>(B);
+    }
+    // the prompt phase's buffers over M = batch * S tokens (beam search prefills one row per request)
+    void plan_prompt(Carver& c, size_t M)
+    {
+        px             = c.take<f16>(M * H * (fp32 ? 2 : 1));
+        pnrm           = c.take<f16>(M * H * (fp32 ? 2 : 1));
+        pnrm2          = c.take<f16>(M * H * (fp32 ? 2 : 1));
+        pqkv           = c.take<f16>(M * 3 * hl * (fp32 ? 2 : 1));
+        pctx           = c.take<f16>(M * hl * (fp32 ? 2 : 1));
+        patt           = c.take<f16>(M * H * (fp32 ? 2 : 1));
+        pmid           = c.take<f16>(M * il * (fp32 ? 2 : 1));
+        pffn           = c.take<f16>(M * H * (fp32 ? 2 : 1));
+        ctx_tgt        = c.take<int>(M);
+        ctx_lp         = c.take<float>(M);
+    }
+    // the buffers of a verify pass (speculative decoding)
+    void plan_speculative(Carver& c, int s_max)
+    {
+        const int R  = VERIFY_MAX_ROWS;
+        vx           = c.take<f16>((size_t)R * H);
+        vnrm         = c.take<f16>((size_t)R * H);
+        vnrm2        = c.take<f16>((size_t)R * H);
+        vqkv         = c.take<f16>((size_t)R * 3 * hl);
+        vctx         = c.take<f16>((size_t)R * hl);
+        vatt         = c.take<f16>((size_t)R * H);
+        vffn         = c.take<f16>((size_t)R * H);
+        vmid         = c.take<f16>((size_t)R * il);
+        vlogits      = c.take<float>((size_t)R * V);
+        vrot         = c.take<float>((size_t)R * 256);
+        spec_aws     = c.take<float>(verify_attention_workspace_bytes(R, nhl, dh, s_max) / 4);
+        spec_partial = gemm_smallm_workspace_bytes(R, 3 * hl, H, int8) + gemm_smallm_workspace_bytes(R, il, H, int8)
+                       + gemm_smallm_workspace_bytes(R, H, hl, int8) + gemm_smallm_workspace_bytes(R, H, il, int8);
+        spec_gws     = c.take<float>((spec_partial + gemm_smallm_ticket_bytes()) / 4);
+        spec_draft   = c.take<int>(R);
+        spec_ndraft  = c.take<int>(4);
+        spec_argmax  = c.take<int>(2 * R);
+    }
     // B = rows of the request (batch * beam_width)
     void plan(int B, int S, int total, int K)
     {
@@ -280,87 +494,9 @@ struct ftcf_gptneox {
             samp_ws            = c.take<char>(sampling_workspace_bytes(B, V));
             rot_table          = c.take<float>((size_t)B * 256);
             chunk_ws           = c.take<unsigned long long>(chunk_workspace_bytes(H, std::min(B, 4), 8) / 8);
-            pplan = PersistPlan{};
-            // With tensor parallelism the per-layer all-reduce happens INSIDE the persistent launch, through the ranks'
-            // exchange windows (persist_device.hip.h ps_tp_exchange); where the windows are not available (peer mapping or
-            // hand-shake failed, FTCF_TP_PERSIST=0) the per-stage launches + RCCL all-reduce stay in charge.
-            const int  tpn      = cfg.tensor_para_size;
-            const bool tp_local = tpn > 1 && cfg.comm && cfg.comm->local;
-            // (L <= 255: the hand-off tags carry the layer in their low byte; tpn <= 8: the exchange-window table of the kernel)
-            if (persist && !fp32 && K == 1 && B <= 2 && cfg.use_gptj_residual && L <= 255 && tpn <= PERSIST_MAX_TP
-                && (tpn == 1 || (persist_tp && cfg.comm && cfg.comm->win_ok))) {
-                // (a local group shares ONE device: every rank gets 1 / world of its compute units)
-                const int nb = tp_local ? std::max(1, (persist_nb > 0 ? persist_nb : num_cu) / tpn) : persist_nb;
-                pplan = persist_plan(B, H, hl, il, nhl, dh, s_max, int8, num_cu, nb, persist_cs1, persist_cs3, persist_own, L);
-                const bool resident = !pplan.ok ? false
-                                      : tp_local ? persist_group_resident(pplan, int8, B, dh, num_cu, tpn)
-                                                 : persist_resident(pplan, int8, B, dh, num_cu, tpn);
-                if (!resident) {
-                    pplan = PersistPlan{};  // not every workgroup would be resident: the hand-offs could never complete
-                }
-            }
-            if (pplan.ok) {
-                ps_slab_n   = (size_t)B * 3 * hl / 2 + (size_t)B * il / 2 + (size_t)B * hl / 2 + (size_t)B * H / 2
-                            + (size_t)pplan.gp_n + (size_t)B * nhl * pplan.nsplit * (dh + 2);
-                ps_gq       = c.take<unsigned long long>(ps_slab_n + 8);
-                ps_gm       = ps_gq ? ps_gq + (size_t)B * 3 * hl / 2 : nullptr;
-                ps_gc       = ps_gq ? ps_gm + (size_t)B * il / 2 : nullptr;
-                ps_gx       = ps_gq ? ps_gc + (size_t)B * hl / 2 : nullptr;
-                ps_gp       = ps_gq ? ps_gx + (size_t)B * H / 2 : nullptr;
-                ps_ga       = ps_gq ? ps_gp + (size_t)pplan.gp_n : nullptr;
-                ps_err      = ps_gq ? reinterpret_cast<int*>(ps_gq + ps_slab_n) : nullptr;
-                d_players   = c.take<PersistLayer>(L);
-                ps_tab      = c.take<char>(persist_table_bytes(pplan) * pplan.NB);
-                ps_tab_ready = false;
-                ps_ts       = ps_ts_file.empty() ? nullptr : c.take<long long>((size_t)pplan.NB * L * 128);
-            }
-            // 3..16 rows (and what the one- / two-row kernel does not take): the rows kernel, one launch per token.  With tensor
-            // parallelism it would be one launch per layer and the all-reduce of x' between them: a rank's shard of a layer is a few
-            // microseconds of HBM time behind five in-kernel hand-offs, and the paired launches of the general path are faster
-            // (one rank's shard of TP 8 at bs 16: 2.67 against 1.69 ms per step): tensor_para_size 1 only
-            rplan = RowsPlan{};
-            rows_ws = nullptr;
-            rows_ts = nullptr;
-            // One and two rows are the one- / two-row kernel's; where ITS plan declines a request (fp16 weights at two rows, more than
-            // 1248 / 3072 tokens of context: its LDS) the rows kernel takes it -- 2.73 ms per token at one row against 3.2 on the
-            // per-stage launches, 3.10 at two rows against 3.48 on the general path (13B int8, 1024-in / 512-out) -- but not when
-            // that kernel has been switched off (FTCF_PERSIST=0, or after it gave up once): then the per-stage launches run, the path
-            // of a tensor-parallel rank
-            const int rmin = rows_min >= 1 ? rows_min : (persist ? 1 : 3);
-            if (rows && cfg.tensor_para_size == 1 && !pplan.ok && !fp32 && K == 1 && B >= rmin && B <= 16
-                && cfg.use_gptj_residual && L <= 255) {
-                // (ranks that share ONE device -- a local group's threads, the two-process tests -- must be resident together)
-                int nb = rows_nb > 0 ? rows_nb : persist_nb;
-                if (tp_local) {
-                    nb = std::max(1, (nb > 0 ? nb : num_cu) / tpn);
-                }
-                rplan = rows_plan(B, H, hl, il, nhl, dh, s_max, int8, num_cu, nb);
-                if (rplan.ok && !rows_resident(rplan, int8, dh, num_cu, false)) {
-                    rplan = RowsPlan{};
-                }
-                if (rplan.ok) {
-                    rows_ws = c.take<char>(rows_workspace_bytes(rplan, B, H, hl, il, nhl, dh));
-                    if (!d_players || !pplan.ok) {
-                        d_players = c.take<PersistLayer>(L);
-                    }
-                    rows_ts = ps_ts_file.empty() ? nullptr : c.take<long long>((size_t)rplan.NB * L * 128);
-                }
-            }
-            // (the four GEMMs of a layer may be in flight together: one region each)
-            // (17..SMALLM_MAX_ROWS rows run the same kernel in chunks of 16 rows: sized for one chunk)
-            // (a prompt phase of up to SMALLM_MAX_ROWS tokens in all is HBM bound like a decode step: it takes the same kernel)
-            const int  bc         = 16;
-            const long prefill_m  = S > 1 ? (long)(B / K) * S : 0;
-            // (tensor parallel: up to 32 rows as two micro-batches of <= 16, each with its own regions -- decoder_overlapped)
-            const bool decode_ws  = B > STAGE_MAX_ROWS && (B <= SMALLM_MAX_ROWS || (cfg.tensor_para_size > 1 && B <= 32));
-            const bool prefill_ws = prefill_m > 4 && prefill_m <= SMALLM_MAX_ROWS;
-            smallm_partial = gemm_smallm_workspace_bytes(bc, 3 * hl, H, int8) + gemm_smallm_workspace_bytes(bc, il, H, int8)
-                             + gemm_smallm_workspace_bytes(bc, H, hl, int8) + gemm_smallm_workspace_bytes(bc, H, il, int8);
-            smallm_region  = smallm_partial;
-            smallm_partial *= cfg.tensor_para_size > 1 ? 2 : 1;
-            smallm_ws = (!fp32 && (decode_ws || prefill_ws)) ? c.take<float>((smallm_partial + gemm_smallm_ticket_bytes()) / 4) : nullptr;
-            const bool tiled_rows = prefill_m > 16 || (B > 16 && B <= gemm_tiled_splitk_max_m());
-            tiled_ws              = (!fp32 && tiled_rows) ? c.take<float>(gemm_tiled_workspace_bytes() / 4) : nullptr;
+            plan_persistent(c, B, K, s_max);
+            plan_rows(c, B, K, s_max);
+            plan_gemm_workspaces(c, B, S, K);
             state              = c.take<DecodeState>(1);
             finished           = c.take<uint8_t>(B);
             masked             = c.take<uint8_t>((size_t)B * s_max);
@@ -378,46 +514,13 @@ struct ftcf_gptneox {
             draws              = c.take<uint64_t>(B);
             d_seed             = c.take<uint64_t>(B);
             if (K > 1) {
-                tiled_ids   = c.take<int>((size_t)B * S);
-                tiled_len   = c.take<int>(B);
-                parent_ids  = c.take<int>((size_t)total * B);
-                cache_indir = c.take<int>((size_t)2 * B * s_max);
-                beam_ws     = c.take<char>(beam_workspace_bytes(B / K, K));
-                d_div       = c.take<float>(B);
-                d_lenpen    = c.take<float>(B);
+                plan_beams(c, B, S, total, K);
             }
             if (S > 1) {
-                const size_t M = (size_t)(B / K) * S;  // beam search prefills one row per request
-                px             = c.take<f16>(M * H * (fp32 ? 2 : 1));
-                pnrm           = c.take<f16>(M * H * (fp32 ? 2 : 1));
-                pnrm2          = c.take<f16>(M * H * (fp32 ? 2 : 1));
-                pqkv           = c.take<f16>(M * 3 * hl * (fp32 ? 2 : 1));
-                pctx           = c.take<f16>(M * hl * (fp32 ? 2 : 1));
-                patt           = c.take<f16>(M * H * (fp32 ? 2 : 1));
-                pmid           = c.take<f16>(M * il * (fp32 ? 2 : 1));
-                pffn           = c.take<f16>(M * H * (fp32 ? 2 : 1));
-                ctx_tgt        = c.take<int>(M);
-                ctx_lp         = c.take<float>(M);
+                plan_prompt(c, (size_t)(B / K) * S);
             }
             if (spec_plan) {  // (behind everything else: the views of a request that does not speculate are where they were)
-                const int R  = VERIFY_MAX_ROWS;
-                vx           = c.take<f16>((size_t)R * H);
-                vnrm         = c.take<f16>((size_t)R * H);
-                vnrm2        = c.take<f16>((size_t)R * H);
-                vqkv         = c.take<f16>((size_t)R * 3 * hl);
-                vctx         = c.take<f16>((size_t)R * hl);
-                vatt         = c.take<f16>((size_t)R * H);
-                vffn         = c.take<f16>((size_t)R * H);
-                vmid         = c.take<f16>((size_t)R * il);
-                vlogits      = c.take<float>((size_t)R * V);
-                vrot         = c.take<float>((size_t)R * 256);
-                spec_aws     = c.take<float>(verify_attention_workspace_bytes(R, nhl, dh, s_max) / 4);
-                spec_partial = gemm_smallm_workspace_bytes(R, 3 * hl, H, int8) + gemm_smallm_workspace_bytes(R, il, H, int8)
-                               + gemm_smallm_workspace_bytes(R, H, hl, int8) + gemm_smallm_workspace_bytes(R, H, il, int8);
-                spec_gws     = c.take<float>((spec_partial + gemm_smallm_ticket_bytes()) / 4);
-                spec_draft   = c.take<int>(R);
-                spec_ndraft  = c.take<int>(4);
-                spec_argmax  = c.take<int>(2 * R);
+                plan_speculative(c, s_max);
             }
             if (pass == 0) {
                 arena.reserve(c.off + 4096);
@@ -948,22 +1051,12 @@ struct ftcf_gptneox {
             return;
         }
         if (rplan.ok) {
-            // every stage of every layer inside ONE launch for up to 16 rows (kernels_rows.hip); with tensor parallelism one
-            // launch per layer and the all-reduce of its output between them (GptNeoXDecoder.cc:357-359)
+            // every stage of every layer inside ONE launch for up to 16 rows (kernels_rows.hip; plan_rows(): tensor_para_size 1 only)
             RowsParams   rp          = rows_params(B, s_max);
             const double layer_bytes = wbytes * ((double)H * 3 * hl + (double)H * il + (double)hl * H + (double)il * H)
                                        + 4.0 * ses.next_step * hl * B;
             stats.decode_path = 3;
-            if (cfg.tensor_para_size == 1) {
-                timed(KIND_PERSIST, layer_bytes * L, [&] { launch_decode_rows(rp, int8, stream); });
-                return;
-            }
-            for (int l = 0; l < L; l++) {
-                rp.l_begin = l;
-                rp.l_end   = l + 1;
-                timed(KIND_PERSIST, layer_bytes, [&] { launch_decode_rows(rp, int8, stream); });
-                allreduce(x, (size_t)B * H);
-            }
+            timed(KIND_PERSIST, layer_bytes * L, [&] { launch_decode_rows(rp, int8, stream); });
             return;
         }
         if (!staged && cfg.use_gptj_residual) {
@@ -1287,8 +1380,42 @@ struct ftcf_gptneox {
         bool              spec = false;
         int               spec_K = 0, spec_N = 0, spec_nd = 0;
         int               spec_steps = 0, spec_drafted = 0, spec_accepted = 0;
+        // the state a request starts its token loop from: everything above as declared (no step taken; no graph captured: the
+        // previous request's were destroyed by abandon_session() / finish()) but what the request itself says.  [e0, e1] time
+        // the prompt phase.
+        void open(const ftcf_forward_args& args, const SamplingParams& sampling, const BeamParams& beams, hipEvent_t t0, hipEvent_t t1,
+                  bool speculate)
+        {
+            Session s;
+            s.active    = true;
+            s.a         = args;
+            s.sp        = sampling;
+            s.bp        = beams;
+            s.K         = args.beam_width;
+            s.batch     = args.batch_size;
+            s.B         = args.batch_size * args.beam_width;
+            s.S         = args.max_input_len;
+            s.total     = args.max_input_len + args.output_len;
+            s.s_max     = s.total;
+            s.next_step = s.S;
+            s.e0        = t0;
+            s.e1        = t1;
+            s.spec      = speculate;
+            s.spec_K    = args.speculative_tokens;
+            s.spec_N    = args.speculative_ngram > 0 ? args.speculative_ngram : 3;
+            *this       = s;
+        }
     } ses;
     bool use_graph = true;
+    void destroy_graphs()
+    {
+        for (hipGraphExec_t* g : {&ses.graph_exec, &ses.graph_exec_n}) {
+            if (*g) {
+                (void)hipGraphExecDestroy(*g);
+                *g = nullptr;
+            }
+        }
+    }
     // drops whatever an unfinished request left behind: the captured graph holds the OLD arena pointers, shapes and sampling
     // flags, and plan() may free that arena -- replaying it for the next request would corrupt memory silently
     void abandon_session()
@@ -1297,14 +1424,7 @@ struct ftcf_gptneox {
             return;
         }
         (void)hipStreamSynchronize(stream);
-        if (ses.graph_exec) {
-            (void)hipGraphExecDestroy(ses.graph_exec);
-            ses.graph_exec = nullptr;
-        }
-        if (ses.graph_exec_n) {
-            (void)hipGraphExecDestroy(ses.graph_exec_n);
-            ses.graph_exec_n = nullptr;
-        }
+        destroy_graphs();
         if (ses.e0) {
             event_pool.push_back(ses.e0);
             ses.e0 = nullptr;
@@ -1316,13 +1436,61 @@ struct ftcf_gptneox {
         drain_events();
         ses.active = false;
     }
+    // ---- the request lifecycle (engine.hip), each of begin / step / finish a sequence of the stages declared under it ----
+    void bind_weights(const ftcf_gptneox_weights& w);  // (create: the layer table; fp16 kernels are re-tiled on `stream`)
+    void read_env_knobs();                             // (create: every knob that is read once per engine)
     void begin(const ftcf_forward_args& a);
+    void check_request(const ftcf_forward_args& a) const;
+    void ensure_exchange_window(int B, int K);
+    void clear_exchange_window();
+    bool speculation_wanted(const ftcf_forward_args& a, int total);
+    SamplingRouting upload_sampling_args(const ftcf_forward_args& a);
+    void reset_workspaces(int B);
+    void tile_beam_inputs(const ftcf_forward_args& a);
+    void upload_layer_tables(int B, int s_max);
     void prompt_phase(const ftcf_forward_args& a, const int* in_ids, const int* in_len);
+    void score_prompt(const ftcf_forward_args& a);
+    void ensure_top_logprob_buffers(size_t pairs);
+    SamplingParams session_sampling_params(const ftcf_forward_args& a, const SamplingRouting& route, const int* in_len) const;
+    BeamParams     session_beam_params(const ftcf_forward_args& a, const SamplingRouting& route, const int* in_len) const;
     void enqueue_step(bool with_decoder);
+    void enqueue_decoder(bool with_decoder);
+    bool enqueue_lm_head();
+    hipGraphExec_t capture_steps(int tokens);
     int  step(int max_steps);
     int  step_speculative(int max_steps);
     void verify_pass(int step, int drafts);
     void finish();
+    void write_outputs();
+    struct ErrorWords {  // what the kernels' sticky give-up words held when the request ended
+        int ps = 0, smallm = 0, rows = 0;
+    };
+    void read_error_words(ErrorWords& w);
+    void close_overlap_trials(float prefill_ms);
+    void dump_timestamps(int NB, const long long* ts);
+    void raise_give_ups(ErrorWords w);
+    // the stopwatch of one step() call: [start, stop] on the stream; stop waits for the stream and adds to stats.decode_ms
+    struct DecodeStopwatch {
+        ftcf_gptneox& e;
+        hipEvent_t    ea, eb;
+        explicit DecodeStopwatch(ftcf_gptneox& eng): e(eng), ea(eng.get_event()), eb(eng.get_event())
+        {
+            FTCF_HIP_CHECK(hipEventRecord(ea, e.stream));
+        }
+        void stop(const char* what)
+        {
+            FTCF_HIP_CHECK(hipEventRecord(eb, e.stream));
+            comm_event_sync(e.cfg.comm, eb, what);
+        }
+        void add_to_stats()
+        {
+            float ms = 0.f;
+            FTCF_HIP_CHECK(hipEventElapsedTime(&ms, ea, eb));
+            e.stats.decode_ms += ms;
+            e.event_pool.push_back(ea);
+            e.event_pool.push_back(eb);
+        }
+    };
     bool persist_failed = false;  // the persistent kernel gave up on a hand-off during the last request
     bool winar_failed = false;    // ... or the exchange-window all-reduce of the prompt phase did
     int  persist_fail_once = 0;

@@ -1,5 +1,6 @@
-// Shared preamble of the engine's translation units (engine.hip, comm.hip, batcher.hip): includes, the error plumbing of the
-// C ABI (every entry point runs under guarded(): exceptions become status codes + ftcf_last_error()).
+// Shared preamble of the engine's translation units (engine.hip, capi_kernels.hip, comm.hip, batcher.hip): includes, the error
+// plumbing of the C ABI (every entry point runs under guarded(): exceptions become status codes + ftcf_last_error()) and
+// env_int(), the one reader of the integer environment knobs.
 #pragma once
 #include <rccl/rccl.h>
 #include <roctracer/roctx.h>
@@ -26,7 +27,7 @@ using namespace ftcf;
 // ---------------------------------------------------------------------------------------------------------------
 // error plumbing
 // ---------------------------------------------------------------------------------------------------------------
-extern thread_local std::string g_last_error;  // (engine.hip)
+extern thread_local std::string g_last_error;  // (capi_kernels.hip)
 
 template<typename F>
 static int guarded(F&& f)
@@ -53,4 +54,11 @@ static void require_device()
         throw Error(FTCF_ERR_NO_DEVICE,
                     "no HIP device visible: the MI355X kernels cannot run (there is no CPU fallback in this library)");
     }
+}
+
+// an integer knob of the environment: atoi of the variable when it is set (an empty string is 0), else `fallback`
+static int env_int(const char* name, int fallback)
+{
+    const char* v = getenv(name);
+    return v ? atoi(v) : fallback;
 }

@@ -9,7 +9,7 @@ namespace ftcf {
 // out_scale in the weight dtype.
 void host_symmetric_quantize_int8(const void* weight, int dtype, size_t E, size_t K, size_t N, int8_t* out_q,
                                   void* out_scale);
-// the argument rule of the quantiser, shared by the host function and its device form (engine.hip): throws ftcf::Error(-1)
+// the argument rule of the quantiser, shared by the host function and its device form (capi_kernels.hip): throws ftcf::Error(-1)
 void check_symmetric_quantize_args(const void* weight, int dtype, size_t E, size_t K, size_t N, const int8_t* out_q,
                                    const void* out_scale);
 void host_int8_rowmajor_to_tiled(const int8_t* q, size_t K, size_t N, int8_t* out);

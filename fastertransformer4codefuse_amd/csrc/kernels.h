@@ -385,6 +385,17 @@ void   launch_transpose_top_logprobs(int* out_ids, float* out_values, const int*
                                      hipStream_t s);
 
 // ---- dynamic decode : kernels_sampling.hip ----
+// the words of `h_flags`, the pinned mailbox through which the step-closing kernels tell the host how the step ended (the host
+// reads it behind an event or a synchronisation of the stream, never while a launch runs)
+enum HostFlag {
+    FLAG_ALL_FINISHED      = 0,  // every row has finished
+    FLAG_LAST_STEP         = 1,  // the last step written (the step that produced FLAG_ALL_FINISHED)
+    FLAG_LM_GREEDY_GAVE_UP = 2,  // k_lm_head_greedy's finishing workgroup gave up waiting for a partial (the host clears it)
+    FLAG_SPEC_EMITTED      = 3,  // tokens emitted by a verify pass
+    FLAG_SPEC_NEXT_DRAFTS  = 4,  // the draft kernel's count for the next step
+    FLAG_SPEC_ACCEPTED     = 5,  // drafts of the verify pass that became output tokens
+    FLAG_COUNT             = 6
+};
 struct DecodeState {  // device resident, one per engine
     int step;         // current step (max_input_len .. total-1)
     int all_finished;
@@ -420,7 +431,7 @@ struct SamplingParams {
     float*          output_log_probs;
     int*            pad_count;
     DecodeState*    state;
-    int*            h_flags;  // pinned host mirror: [0] = all_finished, [1] = step that produced it
+    int*            h_flags;  // pinned host mirror, indexed by HostFlag: FLAG_ALL_FINISHED, FLAG_LAST_STEP, FLAG_LM_GREEDY_GAVE_UP
     void*           ws;       // workspace (see sampling_workspace_bytes)
     // continuous batching: every row has its OWN step -- row b's token history is output_ids[0 .. row_len[b]] (time-major
     // as always), the new token goes to position row_len[b] + 1.  NULL: the batch-wide state->step
@@ -524,7 +535,8 @@ void launch_verify_embed(f16* x, const f16* wte, const int* tokens, const int* d
 // acceptance: a[i] = argmax of logits row i (value descending, index ascending on ties); m = longest prefix with
 // draft[i] == a[i]; emits a[0 .. m] cut after the first end_id, appends them at output_ids[step ...], advances seq_len[0] and
 // the device step, sets finished / all_finished, and leaves all_finished, the last step written, the tokens emitted and the
-// drafts accepted in h_flags[0], [1], [3], [5] (pinned; [4] is the draft kernel's count).  argmax_ws: 2 * R words.
+// drafts accepted in h_flags (pinned, HostFlag: FLAG_ALL_FINISHED, FLAG_LAST_STEP, FLAG_SPEC_EMITTED, FLAG_SPEC_ACCEPTED;
+// FLAG_SPEC_NEXT_DRAFTS is the draft kernel's).  argmax_ws: 2 * R words.
 struct VerifyAcceptParams {
     const float* logits;  // [R, V]
     int          R, V, step, end_id;

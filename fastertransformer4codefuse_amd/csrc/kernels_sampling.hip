@@ -1159,9 +1159,9 @@ __device__ __forceinline__ int decode_finish_body(const SamplingParams& p, const
         p.state->all_finished = all;
         p.state->steps_done   = (steps_done >= 0 ? steps_done : p.state->steps_done) + 1;
         if constexpr (!DEFER_HOST) {
-            p.h_flags[1] = step;
+            p.h_flags[FLAG_LAST_STEP] = step;
             __threadfence_system();
-            p.h_flags[0] = all;
+            p.h_flags[FLAG_ALL_FINISHED] = all;
         }
         p.state->step = step + 1;
     }
@@ -1171,8 +1171,8 @@ __device__ __forceinline__ int decode_finish_body(const SamplingParams& p, const
 __device__ __forceinline__ void decode_publish_host(const SamplingParams& p, const int step, const int all)
 {
     if (threadIdx.x == 0) {
-        p.h_flags[1] = step;
-        p.h_flags[0] = all;
+        p.h_flags[FLAG_LAST_STEP] = step;
+        p.h_flags[FLAG_ALL_FINISHED] = all;
     }
 }
 
@@ -1287,7 +1287,7 @@ __device__ __forceinline__ bool last_ticket(DecodeState* state, const int total)
 // as the token is known, the pinned host flags are the last stores.
 // TAGGED: the partials are granules {tag, value} (part: [B][nsl][4] 8-byte words, the value in the low half) written by
 // workgroups that may still be running: a batch of partials is re-read until every tag is `tag` (bounded: a give-up sets
-// p.h_flags[2] and the step is finished on what is there).
+// p.h_flags[FLAG_LM_GREEDY_GAVE_UP] and the step is finished on what is there).
 constexpr int GREEDY_MAXQ = 4;  // partials of a row a thread requests together
 constexpr int GREEDY_SPINS = 1 << 20;
 template<bool TAGGED = false>
@@ -1398,7 +1398,7 @@ __device__ __forceinline__ void greedy_finish(const SamplingParams& p, const flo
                     }
                     if (++spins > GREEDY_SPINS) {
                         if (threadIdx.x == 0) {
-                            p.h_flags[2] = 1;
+                            p.h_flags[FLAG_LM_GREEDY_GAVE_UP] = 1;
                         }
                         break;
                     }

@@ -549,11 +549,11 @@ __global__ void k_verify_accept(const VerifyAcceptParams p)
     p.state->all_finished = fin;
     p.state->steps_done += e;
     p.state->step = p.step + e;
-    p.h_flags[1]  = p.step + e - 1;
-    p.h_flags[3]  = e;
-    p.h_flags[5]  = m < e ? m : e;  // drafts that became output tokens
+    p.h_flags[FLAG_LAST_STEP]     = p.step + e - 1;
+    p.h_flags[FLAG_SPEC_EMITTED]  = e;
+    p.h_flags[FLAG_SPEC_ACCEPTED] = m < e ? m : e;  // drafts that became output tokens
     __threadfence_system();
-    p.h_flags[0] = fin;
+    p.h_flags[FLAG_ALL_FINISHED] = fin;
 }
 
 void launch_verify_accept(const VerifyAcceptParams& p, hipStream_t s)
