@@ -105,6 +105,7 @@ class ContinuousBatcher:
         self._fin = (C.c_int * n)()
         self._lp = (C.c_float * n)()
         self._cb = None
+        self._beam_log_probs = {}  # request id -> max_new_tokens of the beam requests submitted with token_log_probs
 
     def __del__(self):
         try:
@@ -201,9 +202,11 @@ class ContinuousBatcher:
                                                           int(words.size)))
 
     def submit_beam(self, prompt_ids, max_new_tokens, beam_width, beam_search_diversity_rate=0.0, len_penalty=0.0, temperature=1.0,
-                    repetition_penalty=1.0, min_length=0, stop_words=None):
+                    repetition_penalty=1.0, min_length=0, stop_words=None, token_log_probs=False):
         """A beam-search request (GptNeoXOp.forward with beam_width > 1).  step() reports one event for it, (request_id, -1, True),
-        when it has finished; beam_result(request_id) then returns what forward returns for one prompt."""
+        when it has finished; beam_result(request_id) then returns what forward returns for one prompt.  token_log_probs=True
+        (ftcf_batcher_submit_beam_opts): beam_result also returns every hypothesis' per-token log-probabilities
+        (GptNeoXOp.beam_log_probs)."""
         ids = np.ascontiguousarray(prompt_ids, dtype=np.int32).reshape(-1)
         rid = C.c_long(0)
         sw, sw_len = None, 0
@@ -215,6 +218,14 @@ class ContinuousBatcher:
             arr[1] = -1
             arr[1, :len(stop_words)] = np.cumsum([len(w) for w in stop_words])
             sw = np.ascontiguousarray(arr)
+        if token_log_probs:
+            o = capi.BeamOptions(C.sizeof(capi.BeamOptions), int(beam_width), beam_search_diversity_rate, len_penalty, temperature,
+                                 repetition_penalty, int(min_length),
+                                 sw.ctypes.data_as(C.POINTER(C.c_int)) if sw is not None else None, int(sw_len), 1)
+            capi.check(capi.lib().ftcf_batcher_submit_beam_opts(self._h, ids.ctypes.data, int(ids.size), int(max_new_tokens),
+                                                                C.byref(o), C.byref(rid)))
+            self._beam_log_probs[int(rid.value)] = int(max_new_tokens)
+            return int(rid.value)
         capi.check(capi.lib().ftcf_batcher_submit_beam_ex(
             self._h, ids.ctypes.data_as(C.POINTER(C.c_int)), int(ids.size), int(max_new_tokens), int(beam_width),
             C.c_float(beam_search_diversity_rate), C.c_float(len_penalty), C.c_float(temperature), C.c_float(repetition_penalty),
@@ -223,7 +234,9 @@ class ContinuousBatcher:
 
     def beam_result(self, request_id):
         """(output_ids [beam_width, prompt_len + max_new_tokens], sequence_lengths [beam_width], cum_log_probs [beam_width]) of a
-        finished beam request, once; None while it is running or when the id is unknown."""
+        finished beam request, once; None while it is running or when the id is unknown.  A request submitted with
+        token_log_probs=True returns a fourth array, token_log_probs [beam_width, max_new_tokens] float32: entry i belongs to
+        output_ids[:, prompt_len + i]; 0 behind a hypothesis' first end token and in the end_id padding."""
         k, t = C.c_int(0), C.c_int(0)
         capi.check(capi.lib().ftcf_batcher_beam_result(self._h, C.c_long(int(request_id)), None, None, None, 0, C.byref(k), C.byref(t)))
         if k.value == 0:
@@ -231,6 +244,13 @@ class ContinuousBatcher:
         ids = np.zeros((k.value, t.value), dtype=np.int32)
         lens = np.zeros(k.value, dtype=np.int32)
         cum = np.zeros(k.value, dtype=np.float32)
+        if int(request_id) in self._beam_log_probs:
+            lp = np.zeros((k.value, self._beam_log_probs[int(request_id)]), dtype=np.float32)
+            capi.check(capi.lib().ftcf_batcher_beam_result_ex(
+                self._h, int(request_id), ids.ctypes.data, lens.ctypes.data, cum.ctypes.data, lp.ctypes.data, int(ids.size),
+                C.byref(k), C.byref(t)))
+            del self._beam_log_probs[int(request_id)]
+            return ids, lens, cum, lp
         capi.check(capi.lib().ftcf_batcher_beam_result(
             self._h, C.c_long(int(request_id)), ids.ctypes.data_as(C.POINTER(C.c_int)), lens.ctypes.data_as(C.POINTER(C.c_int)),
             cum.ctypes.data_as(C.POINTER(C.c_float)), int(ids.size), C.byref(k), C.byref(t)))
@@ -307,6 +327,7 @@ class ContinuousBatcher:
         """Drops a waiting or running request; returns False when the id is unknown or already finished."""
         found = C.c_int(0)
         capi.check(capi.lib().ftcf_batcher_cancel(self._h, C.c_long(int(request_id)), C.byref(found)))
+        self._beam_log_probs.pop(int(request_id), None)  # (a cancelled beam request has no result to fetch)
         return bool(found.value)
 
     def busy(self):

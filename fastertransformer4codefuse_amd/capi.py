@@ -114,7 +114,15 @@ class BeamSearchArgs(C.Structure):  # ftcf_beam_search_args
         "len_penalty", "min_length")] + [
         (n, C.c_int) for n in (
             "n_temperature", "n_repetition_penalty", "n_beam_search_diversity_rate", "n_len_penalty", "n_min_length",
-            "stop_len", "optional_count", "B", "K", "V", "step", "max_input_len", "total_len", "s_max", "end_id")]
+            "stop_len", "optional_count", "B", "K", "V", "step", "max_input_len", "total_len", "s_max", "end_id")] + [
+        ("step_log_probs", C.c_void_p)]
+
+
+class BeamOptions(C.Structure):  # ftcf_beam_options
+    _fields_ = [("struct_size", C.c_int), ("beam_width", C.c_int), ("beam_search_diversity_rate", C.c_float),
+                ("len_penalty", C.c_float), ("temperature", C.c_float), ("repetition_penalty", C.c_float),
+                ("min_length", C.c_int), ("stop_words", C.POINTER(C.c_int)), ("stop_len", C.c_int),
+                ("token_log_probs", C.c_int)]
 
 
 class ForwardStats(C.Structure):
@@ -144,9 +152,17 @@ EXPORTED = [
     "ftcf_comm_get_unique_id", "ftcf_comm_init", "ftcf_comm_destroy", "ftcf_comm_local_unique_id",
     "ftcf_comm_init_local", "ftcf_comm_init_host_exchange", "ftcf_comm_allreduce_sum",
     "ftcf_comm_allgather", "ftcf_gptneox_create", "ftcf_gptneox_forward", "ftcf_gptneox_begin", "ftcf_gptneox_step", "ftcf_gptneox_finish",
-    "ftcf_gptneox_get_stats",
+    "ftcf_gptneox_beam_log_probs", "ftcf_gptneox_get_stats",
     "ftcf_gptneox_set_profiling", "ftcf_gptneox_destroy",
-    "ftcf_batcher_create", "ftcf_batcher_create_ex", "ftcf_batcher_create_opts", "ftcf_batcher_preempt_stats", "ftcf_batcher_prefix_stats", "ftcf_batcher_clear_prefix_cache", "ftcf_batcher_submit", "ftcf_batcher_submit_ex", "ftcf_batcher_submit_opts", "ftcf_batcher_submit_n", "ftcf_batcher_fork_stats", "ftcf_batcher_set_token_mask", "ftcf_batcher_submit_beam", "ftcf_batcher_submit_beam_ex", "ftcf_batcher_beam_result", "ftcf_batcher_step", "ftcf_batcher_step_ex", "ftcf_batcher_step_top", "ftcf_batcher_set_token_callback", "ftcf_batcher_status", "ftcf_batcher_cancel", "ftcf_batcher_destroy"]
+    "ftcf_batcher_create", "ftcf_batcher_create_ex", "ftcf_batcher_create_opts", "ftcf_batcher_preempt_stats", "ftcf_batcher_prefix_stats", "ftcf_batcher_clear_prefix_cache", "ftcf_batcher_submit", "ftcf_batcher_submit_ex", "ftcf_batcher_submit_opts", "ftcf_batcher_submit_n", "ftcf_batcher_fork_stats", "ftcf_batcher_set_token_mask", "ftcf_batcher_submit_beam", "ftcf_batcher_submit_beam_ex", "ftcf_batcher_beam_result", "ftcf_batcher_submit_beam_opts", "ftcf_batcher_beam_result_ex", "ftcf_batcher_step", "ftcf_batcher_step_ex", "ftcf_batcher_step_top", "ftcf_batcher_set_token_callback", "ftcf_batcher_status", "ftcf_batcher_cancel", "ftcf_batcher_destroy"]
+
+# the entry points of the beam hypotheses' per-token log-probabilities
+BEAM_LOG_PROB_ARGTYPES = {
+    "ftcf_gptneox_beam_log_probs": [C.c_void_p, C.c_void_p, C.c_size_t],
+    "ftcf_batcher_submit_beam_opts": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(BeamOptions), C.POINTER(C.c_long)],
+    "ftcf_batcher_beam_result_ex": [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                    C.POINTER(C.c_int), C.POINTER(C.c_int)],
+}
 
 _lib = None
 
@@ -167,6 +183,10 @@ def lib():
                      "ftcf_symmetric_quantize_int8_device_workspace"):
             if hasattr(_lib, name):
                 getattr(_lib, name).restype = C.c_size_t
+        for name, argtypes in BEAM_LOG_PROB_ARGTYPES.items():
+            if hasattr(_lib, name):
+                getattr(_lib, name).argtypes = argtypes
+                getattr(_lib, name).restype = C.c_int
     return _lib
 
 

@@ -174,6 +174,8 @@ struct ftcf_batcher : BatcherSched {
         int                K = 0, total = 0;
         std::vector<int>   ids, lens;
         std::vector<float> cum;
+        bool               has_lp = false;  // the request asked for token_log_probs
+        std::vector<float> lp;              // [K][max_new]
     };
     std::map<long, BeamResult> beam_results;  // finished beam requests until they are fetched
     ftcf_gptneox* e = nullptr;
@@ -190,6 +192,8 @@ struct ftcf_batcher : BatcherSched {
     uint8_t *    d_sfin = nullptr, *d_isbeam = nullptr;
     int *        d_bout = nullptr, *d_bpar = nullptr, *d_bseq = nullptr, *d_bin = nullptr, *d_pairs = nullptr, *d_bres = nullptr,
         *d_bres_len = nullptr;
+    // every group's step log-probabilities (a region like d_bout's) and the finished group's [K][max_new] values
+    float *      d_blp = nullptr, *d_bres_lp = nullptr;
     float *      d_btemp = nullptr, *d_brep = nullptr, *d_bdiv = nullptr, *d_blen = nullptr;
     int *        d_bsw = nullptr, *d_bmin = nullptr;  // a group's stop words ([2][STOP_LW], the reference's layout) and min_length
     DecodeState* d_bstate = nullptr;
@@ -440,6 +444,8 @@ struct ftcf_batcher : BatcherSched {
         d_bpar = dmalloc<int>(B * (max_len + 2));
         d_bres = dmalloc<int>(B * (max_len + 2));
         d_bres_len = dmalloc<int>(B);
+        d_blp = dmalloc<float>(B * (max_len + 2));
+        d_bres_lp = dmalloc<float>(B * (max_len + 2));
         d_bseq = dmalloc<int>(B);
         d_bin = dmalloc<int>(B);
         d_pairs = dmalloc<int>(2 * B);
@@ -1093,6 +1099,13 @@ struct ftcf_batcher : BatcherSched {
         FTCF_HIP_CHECK(hipMemcpyAsync(r.ids.data(), d_bres + reg, r.ids.size() * 4, hipMemcpyDeviceToHost, st));
         FTCF_HIP_CHECK(hipMemcpyAsync(r.lens.data(), d_bres_len + si, (size_t)g.K * 4, hipMemcpyDeviceToHost, st));
         FTCF_HIP_CHECK(hipMemcpyAsync(r.cum.data(), d_cum + si, (size_t)g.K * 4, hipMemcpyDeviceToHost, st));
+        if (g.token_log_probs) {  // (only a request that asked pays the walk and the copy)
+            launch_gather_tree_beam_log_probs(d_bres_lp + reg, d_blp + reg, d_bout + reg, d_bpar + reg, d_bseq + si, d_bin + si, 1, g.K,
+                                              g.n, total, e->cfg.end_id, st);
+            r.has_lp = true;
+            r.lp.resize((size_t)g.K * g.max_new);
+            FTCF_HIP_CHECK(hipMemcpyAsync(r.lp.data(), d_bres_lp + reg, r.lp.size() * 4, hipMemcpyDeviceToHost, st));
+        }
         FTCF_HIP_CHECK(hipStreamSynchronize(st));
         const long id    = g.id;
         beam_results[id] = std::move(r);
@@ -1181,6 +1194,9 @@ struct ftcf_batcher : BatcherSched {
         const size_t reg = beam_region(si);
         FTCF_HIP_CHECK(hipMemcpyAsync(d_bout + reg, e->step_ids, (size_t)(n + 1) * K * 4, hipMemcpyDeviceToDevice, st));
         FTCF_HIP_CHECK(hipMemcpyAsync(d_bpar + reg, e->parent_ids, (size_t)(n + 1) * K * 4, hipMemcpyDeviceToDevice, st));
+        // the first step's log-probabilities (row n; the prompt's rows are 0), and 0 in the rows the group's own steps may not reach
+        FTCF_HIP_CHECK(hipMemcpyAsync(d_blp + reg, e->step_log_probs, (size_t)(n + 1) * K * 4, hipMemcpyDeviceToDevice, st));
+        FTCF_HIP_CHECK(hipMemsetAsync(d_blp + reg + (size_t)(n + 1) * K, 0, (size_t)(max_len + 2 - (n + 1)) * K * 4, st));
         FTCF_HIP_CHECK(hipMemcpyAsync(d_bseq + si, e->seq_len, (size_t)K * 4, hipMemcpyDeviceToDevice, st));
         FTCF_HIP_CHECK(hipMemcpyAsync(d_cum + si, e->cum, (size_t)K * 4, hipMemcpyDeviceToDevice, st));
         FTCF_HIP_CHECK(hipMemcpyAsync(d_tok + si, e->step_ids + (size_t)n * K, (size_t)K * 4, hipMemcpyDeviceToDevice, st));
@@ -1236,6 +1252,7 @@ struct ftcf_batcher : BatcherSched {
             bp.finished = d_fin + si;
             bp.seq_len = d_bseq + si;
             bp.cum_log_probs = d_cum + si;
+            bp.step_log_probs = d_blp + reg;
             bp.cache_indir = d_zero;
             bp.state = d_bstate + si;
             bp.ws = beam_ws;
@@ -1899,28 +1916,58 @@ extern "C" int ftcf_batcher_submit_beam_ex(ftcf_batcher_t b, const int* prompt_i
                                      temperature, repetition_penalty, min_length, stop_words, stop_len);
     });
 }
+// the parked result of a beam request, fetched once; token_log_probs: ftcf_batcher_beam_result_ex's array or NULL
+static void fetch_beam_result(ftcf_batcher_t b, long request_id, int* output_ids, int* sequence_lengths, float* cum_log_probs,
+                              float* token_log_probs, int capacity, int* beam_width, int* total_len)
+{
+    FTCF_CHECK_ARG(b && beam_width && total_len, "NULL argument");
+    auto it = b->beam_results.find(request_id);
+    if (it == b->beam_results.end()) {
+        *beam_width = 0;
+        *total_len  = 0;
+        return;
+    }
+    const ftcf_batcher::BeamResult& r = it->second;
+    *beam_width = r.K;
+    *total_len  = r.total;
+    if (!output_ids) {
+        return;  // (a size query)
+    }
+    FTCF_CHECK_ARG(capacity >= r.K * r.total && sequence_lengths && cum_log_probs, "beam result: arrays too small");
+    FTCF_CHECK_ARG(!token_log_probs || r.has_lp, "beam result: the request was not submitted with token_log_probs");
+    std::copy(r.ids.begin(), r.ids.end(), output_ids);
+    std::copy(r.lens.begin(), r.lens.end(), sequence_lengths);
+    std::copy(r.cum.begin(), r.cum.end(), cum_log_probs);
+    if (token_log_probs) {
+        std::copy(r.lp.begin(), r.lp.end(), token_log_probs);
+    }
+    b->beam_results.erase(it);
+}
 extern "C" int ftcf_batcher_beam_result(ftcf_batcher_t b, long request_id, int* output_ids, int* sequence_lengths,
                                         float* cum_log_probs, int capacity, int* beam_width, int* total_len)
 {
     return guarded([&] {
-        FTCF_CHECK_ARG(b && beam_width && total_len, "NULL argument");
-        auto it = b->beam_results.find(request_id);
-        if (it == b->beam_results.end()) {
-            *beam_width = 0;
-            *total_len  = 0;
-            return;
-        }
-        const ftcf_batcher::BeamResult& r = it->second;
-        *beam_width = r.K;
-        *total_len  = r.total;
-        if (!output_ids) {
-            return;  // (a size query)
-        }
-        FTCF_CHECK_ARG(capacity >= r.K * r.total && sequence_lengths && cum_log_probs, "beam result: arrays too small");
-        std::copy(r.ids.begin(), r.ids.end(), output_ids);
-        std::copy(r.lens.begin(), r.lens.end(), sequence_lengths);
-        std::copy(r.cum.begin(), r.cum.end(), cum_log_probs);
-        b->beam_results.erase(it);
+        fetch_beam_result(b, request_id, output_ids, sequence_lengths, cum_log_probs, nullptr, capacity, beam_width, total_len);
+    });
+}
+extern "C" int ftcf_batcher_submit_beam_opts(ftcf_batcher_t b, const int* prompt_ids, int prompt_len, int max_new_tokens,
+                                             const ftcf_beam_options* o, long* request_id)
+{
+    return guarded([&] {
+        require_device();  // (no batcher exists without one)
+        FTCF_CHECK_ARG(b && o && request_id, "NULL argument");
+        FTCF_CHECK_ARG(o->struct_size == (int)sizeof(ftcf_beam_options), "struct_size is not sizeof(ftcf_beam_options)");
+        *request_id = b->submit_beam(prompt_ids, prompt_len, max_new_tokens, o->beam_width, o->beam_search_diversity_rate, o->len_penalty,
+                                     o->temperature, o->repetition_penalty, o->min_length, o->stop_words, o->stop_len,
+                                     o->token_log_probs != 0);
+    });
+}
+extern "C" int ftcf_batcher_beam_result_ex(ftcf_batcher_t b, long request_id, int* output_ids, int* sequence_lengths,
+                                           float* cum_log_probs, float* token_log_probs, int capacity, int* beam_width, int* total_len)
+{
+    return guarded([&] {
+        require_device();  // (no batcher exists without one)
+        fetch_beam_result(b, request_id, output_ids, sequence_lengths, cum_log_probs, token_log_probs, capacity, beam_width, total_len);
     });
 }
 static int batcher_step(ftcf_batcher_t b, long* request_ids, int* tokens, int* finished, float* log_probs, int capacity, int* n_events,

@@ -53,6 +53,7 @@ struct BatcherSched {
         int              beam_width = 1;     // > 1: a beam group (submit_beam)
         float            diversity = 0.f, len_penalty = 0.f;
         int              min_length = 0;     // beam requests: the end token is held back for this many new tokens
+        bool             token_log_probs = false;  // beam requests: the result carries every hypothesis' per-token log-probabilities
         LogitOptions          lopt;  // ordinary requests: logit processors
         std::vector<unsigned> mask;  // ... and the allowed-token mask set while it waits (empty: none)
         // a fork request (submit_n): ONE prompt phase, n_samples siblings.  Sibling `index` is the plain request of seed + index
@@ -118,6 +119,7 @@ struct BatcherSched {
         int  si = 0, K = 0, n = 0, max_new = 0, generated = 0, budget = 0;
         bool penalised = false;  // repetition_penalty != 1
         bool has_stop = false, has_min = false;
+        bool token_log_probs = false;  // the request asked for its hypotheses' per-token log-probabilities
         std::vector<std::vector<int>> lists;  // page list of every beam
     };
     // The next admission, as plan_admission() describes it and ftcf_batcher::run_admission() carries it out.
@@ -735,7 +737,8 @@ struct BatcherSched {
     // a beam-search request (GptNeoXOp.forward with beam_width > 1: OnlineBeamSearchLayer): K consecutive slots; one event when
     // it has finished (token = -1), the K hypotheses through beam_result()
     long submit_beam(const int* ids, int n, int max_new, int beam_width, float diversity, float len_penalty, float temperature,
-                     float repetition_penalty, int min_length = 0, const int* stop_words = nullptr, int stop_len = 0)
+                     float repetition_penalty, int min_length = 0, const int* stop_words = nullptr, int stop_len = 0,
+                     bool token_log_probs = false)
     {
         FTCF_CHECK_ARG(min_length >= 0, "min_length must not be negative");
         FTCF_CHECK_ARG(stop_len >= 0 && stop_len <= STOP_LW && (stop_len == 0 || stop_words), "bad stop word list");
@@ -754,6 +757,7 @@ struct BatcherSched {
         r.diversity = diversity;
         r.len_penalty = len_penalty;
         r.min_length = min_length;
+        r.token_log_probs = token_log_probs;
         return enqueue(r, ids, n, stop_words, stop_len);
     }
 
@@ -1024,6 +1028,7 @@ struct BatcherSched {
         g.penalised = r.repetition_penalty != 1.f;
         g.has_min   = r.min_length > 0;
         g.has_stop  = !r.stop.empty();
+        g.token_log_probs = r.token_log_probs;
         std::vector<int> shared;
         try {
             for (int i = 0; i < (n + P - 1) / P; i++) {

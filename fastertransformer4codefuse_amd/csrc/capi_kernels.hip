@@ -812,6 +812,7 @@ extern "C" int ftcf_beam_search_step(const ftcf_beam_search_args* a, void* strea
         bp.finished             = a->finished;
         bp.seq_len              = a->seq_len;
         bp.cum_log_probs        = a->cum_log_probs;
+        bp.step_log_probs       = a->step_log_probs;
         bp.cache_indir          = a->cache_indir;
         bp.ws                   = mem.alloc<char>(beam_workspace_bytes(B, K));
         bp.state                = mem.state(a->step, s);  // (synchronises: the host vectors above have been copied)

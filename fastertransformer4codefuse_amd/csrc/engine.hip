@@ -290,6 +290,7 @@ void ftcf_gptneox::tile_beam_inputs(const ftcf_forward_args& a)
     launch_tile_inputs(tiled_ids, tiled_len, a.input_ids, a.input_lengths, batch, K, S, stream);
     FTCF_HIP_CHECK(hipMemsetAsync(cache_indir, 0, (size_t)2 * B * total * 4, stream));
     FTCF_HIP_CHECK(hipMemsetAsync(parent_ids, 0, (size_t)total * B * 4, stream));
+    FTCF_HIP_CHECK(hipMemsetAsync(step_log_probs, 0, (size_t)total * B * 4, stream));  // (rows no step writes hold 0)
 }
 
 // context_log_probs (ParallelGpt.cc:403-470): px holds the last layer's output of every prompt row, once per request (beams
@@ -410,6 +411,7 @@ BeamParams ftcf_gptneox::session_beam_params(const ftcf_forward_args& a, const S
         bp.finished = finished;
         bp.seq_len = seq_len;
         bp.cum_log_probs = cum;
+        bp.step_log_probs = step_log_probs;
         bp.cache_indir = cache_indir;
         bp.state = state;
         bp.ws = beam_ws;
@@ -432,6 +434,7 @@ void ftcf_gptneox::begin(const ftcf_forward_args& a)
     const int total = S + out_len;  // max_output_seq_len == max_seq_len == max_cache_seq_len (GptNeoX.cc:520-523)
     const int s_max = total;
     FTCF_HIP_CHECK(hipSetDevice(cfg.device));
+    beam_request_done = false;
     abandon_session();  // (a request left open -- begin / step without finish, or a step that threw -- must not leak its graph)
     stats.window_allreduces = 0;
     // everything the caller enqueued on its stream (input tensors) happens-before the engine's work
@@ -963,6 +966,7 @@ void ftcf_gptneox::finish()
     event_pool.push_back(ses.e1);
     ses.e0 = ses.e1 = nullptr;
     ses.active = false;
+    beam_request_done = ses.K > 1;
     destroy_graphs();
     drain_events();
     if (pplan.ok && ps_ts) {
@@ -972,6 +976,19 @@ void ftcf_gptneox::finish()
         dump_timestamps(rplan.NB, rows_ts);
     }
     raise_give_ups(err);
+}
+
+// output_log_probs [batch, beam, output_len] of a beam request (GptNeoX.cc:418), behind the request: the step values that
+// k_beam_batch recorded, carried along the gather tree's parent chain.  The request's buffers live until the next begin().
+void ftcf_gptneox::beam_log_probs(float* log_probs, size_t capacity)
+{
+    FTCF_CHECK_ARG(log_probs, "NULL argument");
+    FTCF_CHECK_ARG(beam_request_done, "beam_log_probs: the last request was not a finished beam-search request");
+    FTCF_CHECK_ARG(capacity >= (size_t)ses.B * (ses.total - ses.S), "beam_log_probs: capacity is below batch * beam_width * output_len");
+    FTCF_HIP_CHECK(hipSetDevice(cfg.device));
+    launch_gather_tree_beam_log_probs(log_probs, step_log_probs, step_ids, parent_ids, seq_len, tiled_len, ses.batch, ses.K, ses.S,
+                                      ses.total, cfg.end_id, stream);
+    comm_stream_sync(cfg.comm, stream);
 }
 
 // ---- create: configuration, streams and events, the weights, the knobs, the pinned flags --------------------------------------
@@ -1207,6 +1224,15 @@ extern "C" int ftcf_gptneox_finish(ftcf_gptneox_t h)
     return guarded([&] {
         FTCF_CHECK_ARG(h, "NULL argument");
         h->finish();
+    });
+}
+
+extern "C" int ftcf_gptneox_beam_log_probs(ftcf_gptneox_t h, float* log_probs, size_t capacity)
+{
+    return guarded([&] {
+        require_device();  // (no engine exists without one)
+        FTCF_CHECK_ARG(h, "NULL argument");
+        h->beam_log_probs(log_probs, capacity);
     });
 }
 

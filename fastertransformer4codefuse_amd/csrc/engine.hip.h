@@ -191,6 +191,8 @@ struct ftcf_gptneox {
     unsigned  smallm_seq = 0;       // launch counter: part of the granule tag of its in-launch reduction
     // beam search (beam_width K > 1; rows = batch * K everywhere above)
     int *  tiled_ids = nullptr, *tiled_len = nullptr, *parent_ids = nullptr, *cache_indir = nullptr;
+    float* step_log_probs = nullptr;  // [total, B] like parent_ids: every beam step's cum - the parent's old cum (beam_log_probs)
+    bool   beam_request_done = false;  // a beam request has finished and no begin() has touched its buffers since
     void*  beam_ws = nullptr;
     float *d_div = nullptr, *d_lenpen = nullptr;
     int*      h_flags = nullptr;  // pinned
@@ -428,6 +430,7 @@ struct ftcf_gptneox {
         tiled_ids   = c.take<int>((size_t)B * S);
         tiled_len   = c.take<int>(B);
         parent_ids  = c.take<int>((size_t)total * B);
+        step_log_probs = c.take<float>((size_t)total * B);
         cache_indir = c.take<int>((size_t)2 * B * s_max);
         beam_ws     = c.take<char>(beam_workspace_bytes(B / K, K));
         d_div       = c.take<float>(B);
@@ -1462,6 +1465,7 @@ struct ftcf_gptneox {
     void verify_pass(int step, int drafts);
     void finish();
     void write_outputs();
+    void beam_log_probs(float* log_probs, size_t capacity);  // (of the last request, until the next begin)
     struct ErrorWords {  // what the kernels' sticky give-up words held when the request ended
         int ps = 0, smallm = 0, rows = 0;
     };

@@ -474,6 +474,9 @@ struct BeamParams {
     uint8_t*     finished;
     int*         seq_len;
     float*       cum_log_probs;
+    // the step's log-probability of every row's token, cum_new[bb] - cum_old[parent] (+0 for a beam that had finished),
+    // time-major [total, B*K] like output_ids, row `step` written; or NULL
+    float*       step_log_probs;
     int*         cache_indir;  // [2][B*K][s_max]: plane (step - max_input_len) % 2 is read, the other one written
     DecodeState* state;
     void*        ws;  // beam_workspace_bytes
@@ -486,6 +489,11 @@ void   launch_tile_inputs(int* tiled_ids, int* tiled_len, const int* ids, const 
 void   launch_gather_tree_beam(int* output_ids, int* sequence_lengths, const int* step_ids, const int* parent_ids,
                                const int* seq_len, const int* input_lengths, int B, int K, int max_input_len, int total,
                                int end_id, hipStream_t s);
+// the log-probabilities of the hypotheses launch_gather_tree_beam returns, [B, K, total - max_input_len], from the rows
+// BeamParams::step_log_probs recorded
+void   launch_gather_tree_beam_log_probs(float* log_probs, const float* step_log_probs, const int* step_ids, const int* parent_ids,
+                                         const int* seq_len, const int* input_lengths, int B, int K, int max_input_len, int total,
+                                         int end_id, hipStream_t s);
 size_t sampling_workspace_bytes(int B, int V);
 void   launch_dynamic_decode(const SamplingParams& p, hipStream_t s, bool finish = true);
 // LM head (final LayerNorm fused, as launch_lm_head with gamma) + the all-greedy dynamic decode of the token + the next token's

@@ -133,7 +133,7 @@ __global__ __launch_bounds__(256) void k_beam_batch(const BeamParams p, const fl
     __shared__ float red[8];
     __shared__ int   redi[8];
     __shared__ int   s_parent[BEAM_MAX_K], s_word[BEAM_MAX_K], s_seq[BEAM_MAX_K], s_fin[BEAM_MAX_K];
-    __shared__ float s_cum[BEAM_MAX_K];
+    __shared__ float s_cum[BEAM_MAX_K], s_lp[BEAM_MAX_K];
     const int        b = blockIdx.x, K = p.K, V = p.V, BK = p.B * K, KK = K * K;
     const int        tid = threadIdx.x, nt = blockDim.x;
     const int        step = p.state->step;
@@ -178,11 +178,19 @@ __global__ __launch_bounds__(256) void k_beam_batch(const BeamParams p, const fl
             const int pb = b * K + pk;
             s_seq[r]     = old_fin[pb] ? old_seq[pb] : old_seq[pb] + 1;
             s_fin[r]     = (z % V) == p.end_id;
+            // the step's log-probability (online_softmax_beamsearch_kernels.cu:241-243): new cum - the parent's old cum, read
+            // here because cum_log_probs[pb] is overwritten below; a finished parent offered cum + 0, so the value is +0
+            if (p.step_log_probs) {
+                s_lp[r] = cy[e] - p.cum_log_probs[pb];
+            }
         }
         __syncthreads();
     }
     if (tid < K) {
         const int bb                         = b * K + tid;
+        if (p.step_log_probs) {
+            p.step_log_probs[(size_t)step * BK + bb] = s_lp[tid];
+        }
         p.seq_len[bb]                        = s_seq[tid];
         p.finished[bb]                       = (uint8_t)s_fin[tid];
         p.parent_ids[(size_t)step * BK + bb] = s_parent[tid];
@@ -330,6 +338,84 @@ void launch_gather_tree_beam(int* output_ids, int* sequence_lengths, const int* 
 {
     hipLaunchKernelGGL(k_gather_tree_beam, dim3(B * K), dim3(64), 0, s, output_ids, sequence_lengths, step_ids, parent_ids,
                        seq_len, input_lengths, B, K, max_input_len, total, end_id);
+    FTCF_HIP_CHECK(hipGetLastError());
+}
+
+// The log-probabilities of the tokens k_gather_tree_beam returns: out [B, K, total - max_input_len], entry i for the i-th
+// generated token of hypothesis (b, k).  The same levels and parents as the tree above, as written: the value of the cell a
+// token was read from, 0 where the tree takes no token from a cell (the end_id fill past the longest beam, the rewrite behind the
+// hypothesis' first end token).  One wave per hypothesis: the chain of parents is lane 0's, the fills and the scan for the first
+// end token are everybody's.  `tok` restates the generated part of the tree's own row, because the rewrite is decided on it.
+__global__ __launch_bounds__(64) void k_gather_tree_beam_log_probs(float* out, const float* step_log_probs, const int* step_ids,
+                                                                   const int* parent_ids, const int* seq_len,
+                                                                   const int* input_lengths, int B, int K, int max_input_len,
+                                                                   int total, int end_id)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ int s_first;
+    int*           tok = reinterpret_cast<int*>(smem);  // [total]
+    const int      bb = blockIdx.x, b = bb / K, BK = B * K, tid = threadIdx.x, nt = blockDim.x;
+    const int      out_len = total - max_input_len;
+    float*         lp      = out + (size_t)bb * out_len;
+    int            max_len = -1;
+    for (int j = 0; j < K; j++) {
+        const int tmp_len = seq_len[b * K + j] + 1;
+        max_len           = tmp_len > max_len ? tmp_len : max_len;
+    }
+    const int msl = max_len < total ? max_len : total;
+    for (int t = tid; t < total; t += nt) {
+        tok[t] = 0;
+    }
+    for (int i = tid; i < out_len; i += nt) {
+        lp[i] = 0.f;
+    }
+    if (tid == 0) {
+        s_first = total;
+    }
+    __syncthreads();
+    if (msl <= 0) {
+        return;
+    }
+    const int in_len  = input_lengths[bb];
+    const int pad_off = max_input_len - in_len;
+    // generated level `level` is the tree's beams[level - pad_off], the (level - max_input_len)-th generated token.  The walk
+    // stops where the prompt begins: its levels carry no value, and the rewrite below reads rows >= max_input_len only
+    if (tid == 0 && msl - 1 >= max_input_len) {
+        size_t cell = (size_t)(msl - 1) * BK + bb;
+        for (int level = msl - 1; level >= max_input_len; level--) {
+            tok[level - pad_off]      = step_ids[cell];
+            lp[level - max_input_len] = step_log_probs[cell];
+            cell                      = (size_t)(level - 1) * BK + b * K + parent_ids[cell] % K;
+        }
+    }
+    __syncthreads();
+    for (int index = (max_len > pad_off ? max_len - pad_off : 0) + tid; index < total; index += nt) {
+        tok[index] = end_id;
+    }
+    __syncthreads();
+    int first = total;  // the first end token the tree's rewrite loop meets: everything behind it, up to msl, is rewritten
+    for (int t = max_input_len + tid; t < msl; t += nt) {
+        if (tok[t] == end_id) {
+            first = t;
+            break;
+        }
+    }
+    atomicMin(&s_first, first);
+    __syncthreads();
+    for (int t = s_first + 1 + tid; t < msl; t += nt) {
+        if (t - in_len < out_len) {
+            lp[t - in_len] = 0.f;
+        }
+    }
+}
+
+void launch_gather_tree_beam_log_probs(float* log_probs, const float* step_log_probs, const int* step_ids, const int* parent_ids,
+                                       const int* seq_len, const int* input_lengths, int B, int K, int max_input_len, int total,
+                                       int end_id, hipStream_t s)
+{
+    FTCF_CHECK_ARG((size_t)total * 4 <= 60 * 1024, "sequence too long for the gather tree's staging row");
+    hipLaunchKernelGGL(k_gather_tree_beam_log_probs, dim3(B * K), dim3(64), (size_t)total * 4, s, log_probs, step_log_probs,
+                       step_ids, parent_ids, seq_len, input_lengths, B, K, max_input_len, total, end_id);
     FTCF_HIP_CHECK(hipGetLastError());
 }
 

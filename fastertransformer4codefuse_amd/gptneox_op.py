@@ -141,6 +141,7 @@ class GptNeoXOp:
         self.vocab_size_ = int(vocab_size)
         self.tensor_para_size_ = int(tensor_para_size)
         self.device_ = weights[0].device.index if weights[0].device.index is not None else torch.cuda.current_device()
+        self._last_beam_shape = None  # (batch, beam_width, output_len) of the last forward when it was a beam request
         # keep the tensors alive, like GptNeoXOp.h:402-404
         self.weights = list(weights)
         self.int8_weights = list(int8_weights)
@@ -285,6 +286,7 @@ class GptNeoXOp:
             a.draft_ids = draft_ids.data_ptr()
         if top_n:
             a.top_logprobs, a.top_logprob_ids, a.top_logprob_values = top_n, top_ids.data_ptr(), top_values.data_ptr()
+        self._last_beam_shape = (B, beam_width, int(output_len)) if beam_width > 1 else None
         capi.check(capi.lib().ftcf_gptneox_forward(self._h, C.byref(a)))
         out = [output_ids, sequence_lengths]
         for t in (cum_log_probs, output_log_probs, context_log_probs, top_ids, top_values):
@@ -293,6 +295,16 @@ class GptNeoXOp:
         return out
 
     # --- extras (not part of the reference surface) ---
+    def beam_log_probs(self):
+        """Per-token log-probabilities of the hypotheses of the last forward(), which must have run with beam_width > 1
+        (ftcf_gptneox_beam_log_probs): float32 [batch, beam_width, output_len]; entry i belongs to
+        output_ids[b, k, input_lengths[b] + i] and is the step's new cum_log_probs minus the parent beam's old one; 0 behind a
+        hypothesis' first end token and in the end_id padding.  Raises FtcfError when the last request was not a beam request."""
+        shape = self._last_beam_shape
+        out = torch.empty(shape if shape else (1,), dtype=torch.float32, device=f"cuda:{self.device_}")
+        capi.check(capi.lib().ftcf_gptneox_beam_log_probs(self._h, out.data_ptr(), out.numel() if shape else 0))
+        return out
+
     def stats(self):
         s = capi.ForwardStats()
         capi.check(capi.lib().ftcf_gptneox_get_stats(self._h, C.byref(s)))

@@ -347,6 +347,11 @@ typedef struct {
     int n_temperature, n_repetition_penalty, n_beam_search_diversity_rate, n_len_penalty, n_min_length;
     int stop_len, optional_count;
     int B, K, V, step, max_input_len, total_len, s_max, end_id;
+    /* appended: the step's log-probability of every row's token (online_softmax_beamsearch_kernels.cu:241-243: the new
+     * cumulative score minus the PARENT's old one, one fp32 subtraction; exactly +0 for a beam that had finished before the
+     * step), device, time-major [total_len, B * K] fp32 like output_ids; row `step` is written.  NULL: off, and every other
+     * output is bit for bit what it is with the pointer set. */
+    float* step_log_probs;
 } ftcf_beam_search_args;
 int ftcf_beam_search_step(const ftcf_beam_search_args* args, void* stream);
 /* Per-request LOGIT PROCESSORS: one stage over logits [batch_size, vocab_size] fp32 (device, modified in place), to run between
@@ -591,6 +596,16 @@ int ftcf_gptneox_forward(ftcf_gptneox_t h, const ftcf_forward_args* args);
 int ftcf_gptneox_begin(ftcf_gptneox_t h, const ftcf_forward_args* args);
 int ftcf_gptneox_step(ftcf_gptneox_t h, int max_steps, int* steps_done);
 int ftcf_gptneox_finish(ftcf_gptneox_t h);
+/* Per-token log-probabilities of the hypotheses of the LAST request, which must have run with beam_width > 1 (the reference's
+ * output_log_probs [batch, beam, output_len], GptNeoX.cc:418; ftcf_forward_args.output_log_probs stays refused for beams).
+ * Every beam step records new cum_log_probs - the parent's old cum_log_probs (online_softmax_beamsearch_kernels.cu:241-243);
+ * log_probs[b, k, i] is the recorded value of the cell the gather tree (decoding_kernels.cu:452-583) read the i-th generated
+ * token of hypothesis (b, k) from -- output_ids[b, k, input_lengths[b] + i] -- and 0 where the tree takes no token from a cell:
+ * the end_id fill past the longest beam and everything behind the hypothesis' first end token.  log_probs: device,
+ * capacity >= batch * beam_width * output_len floats.  Valid after forward / finish until the next begin; runs on the engine's
+ * stream and synchronises; changes nothing a later call would see.  FTCF_ERR_INVALID_ARG: no request has run, the last one
+ * was not a beam request or has not finished, capacity too small, NULL. */
+int ftcf_gptneox_beam_log_probs(ftcf_gptneox_t h, float* log_probs, size_t capacity);
 int ftcf_gptneox_get_stats(ftcf_gptneox_t h, ftcf_forward_stats* stats);
 /* enable HIP-event timing around every weight-streaming launch of the decode loop (bench.py roofline leg) */
 int ftcf_gptneox_set_profiling(ftcf_gptneox_t h, int enabled);
@@ -740,6 +755,27 @@ int ftcf_batcher_submit_beam_ex(ftcf_batcher_t b, const int* prompt_ids, int pro
                                 int min_length, const int* stop_words, int stop_len, long* request_id);
 int ftcf_batcher_beam_result(ftcf_batcher_t b, long request_id, int* output_ids, int* sequence_lengths, float* cum_log_probs,
                              int capacity, int* beam_width, int* total_len);
+/* The general form of a beam request.  struct_size must be sizeof(ftcf_beam_options) (anything else is FTCF_ERR_INVALID_ARG
+ * and nothing is queued); beam_width .. stop_len as in ftcf_batcher_submit_beam_ex.  token_log_probs != 0: the request also
+ * returns the log-probability of every generated token of every hypothesis (ftcf_gptneox_beam_log_probs: the step's new
+ * cumulative score minus the parent's old one, online_softmax_beamsearch_kernels.cu:241-243, carried along the gather tree's
+ * parent chain), fetched with ftcf_batcher_beam_result_ex.  With token_log_probs == 0 it is exactly ftcf_batcher_submit_beam_ex. */
+typedef struct {
+    int        struct_size;
+    int        beam_width;
+    float      beam_search_diversity_rate, len_penalty, temperature, repetition_penalty;
+    int        min_length;
+    const int* stop_words;
+    int        stop_len;
+    int        token_log_probs;
+} ftcf_beam_options;
+int ftcf_batcher_submit_beam_opts(ftcf_batcher_t b, const int* prompt_ids, int prompt_len, int max_new_tokens,
+                                  const ftcf_beam_options* options, long* request_id);
+/* ftcf_batcher_beam_result plus token_log_probs [beam_width][max_new_tokens] (entry i: the i-th generated token, 0 behind the
+ * hypothesis' first end token and in the end_id padding).  NULL is allowed (then it is ftcf_batcher_beam_result); non-NULL for
+ * a request that was not submitted with token_log_probs is FTCF_ERR_INVALID_ARG and the result stays parked. */
+int ftcf_batcher_beam_result_ex(ftcf_batcher_t b, long request_id, int* output_ids, int* sequence_lengths, float* cum_log_probs,
+                                float* token_log_probs, int capacity, int* beam_width, int* total_len);
 /* One scheduler iteration: one decode step for the running sequences, then admissions (prefill + first token).  Returns one
  * event per token produced: request id, token, finished (end_id emitted or max_new_tokens reached).  capacity >= 2 * max_batch.
  * With sequences running, a prompt longer than FTCF_BATCHER_PREFILL_CHUNK tokens (default 512; 0 = never) is admitted alone and
