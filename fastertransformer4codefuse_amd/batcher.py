@@ -128,26 +128,15 @@ class ContinuousBatcher:
         opts, keep = pack_logit_options(logit_bias, bad_words, presence_penalty, frequency_penalty, min_new_tokens)
         ids = np.ascontiguousarray(prompt_ids, dtype=np.int32).reshape(-1)
         rid = C.c_long(0)
-        sw, sw_len = None, 0
-        if stop_words:
-            flat = [t for w in stop_words for t in w]
-            sw_len = len(flat)
-            arr = np.zeros((2, sw_len), dtype=np.int32)  # to_word_list_format (codefuse_example.py:26-53)
-            arr[0] = flat
-            arr[1] = -1
-            arr[1, :len(stop_words)] = np.cumsum([len(w) for w in stop_words])
-            sw = np.ascontiguousarray(arr)
+        sw = _word_list(stop_words) if stop_words else None
+        sw_len = int(sw.shape[1]) if sw is not None else 0
+        request = (self._h, capi.vp(ids), int(ids.size), int(max_new_tokens), int(top_k), top_p, temperature, repetition_penalty,
+                   int(seed), capi.vp(sw), sw_len)
         if opts is not None:
-            capi.check(capi.lib().ftcf_batcher_submit_opts(
-                self._h, ids.ctypes.data_as(C.POINTER(C.c_int)), int(ids.size), int(max_new_tokens), int(top_k), C.c_float(top_p),
-                C.c_float(temperature), C.c_float(repetition_penalty), C.c_ulonglong(int(seed)),
-                sw.ctypes.data_as(C.POINTER(C.c_int)) if sw is not None else None, int(sw_len), C.byref(opts), C.byref(rid)))
+            capi.check(capi.lib().ftcf_batcher_submit_opts(*request, C.byref(opts), C.byref(rid)))
             del keep  # (the call copies the arrays)
             return int(rid.value)
-        capi.check(capi.lib().ftcf_batcher_submit_ex(
-            self._h, ids.ctypes.data_as(C.POINTER(C.c_int)), int(ids.size), int(max_new_tokens), int(top_k), C.c_float(top_p),
-            C.c_float(temperature), C.c_float(repetition_penalty), C.c_ulonglong(int(seed)),
-            sw.ctypes.data_as(C.POINTER(C.c_int)) if sw is not None else None, int(sw_len), C.byref(rid)))
+        capi.check(capi.lib().ftcf_batcher_submit_ex(*request, C.byref(rid)))
         return int(rid.value)
 
     def submit_n(self, prompt_ids, max_new_tokens, n, top_k=0, top_p=0.0, temperature=1.0, seed=0, repetition_penalty=1.0,
@@ -163,9 +152,8 @@ class ContinuousBatcher:
         rids = (C.c_long * max(n, 1))()
         sw = _word_list(stop_words) if stop_words else None
         capi.check(capi.lib().ftcf_batcher_submit_n(
-            self._h, ids.ctypes.data_as(C.POINTER(C.c_int)), int(ids.size), int(max_new_tokens), int(top_k), C.c_float(top_p),
-            C.c_float(temperature), C.c_float(repetition_penalty), C.c_ulonglong(int(seed) % (1 << 64)),
-            sw.ctypes.data_as(C.POINTER(C.c_int)) if sw is not None else None, int(sw.shape[1]) if sw is not None else 0,
+            self._h, capi.vp(ids), int(ids.size), int(max_new_tokens), int(top_k), top_p, temperature, repetition_penalty,
+            int(seed) % (1 << 64), capi.vp(sw), int(sw.shape[1]) if sw is not None else 0,
             C.byref(opts) if opts is not None else None, n, rids))
         del keep  # (the call copies the arrays)
         return [int(rids[i]) for i in range(n)]
@@ -183,7 +171,7 @@ class ContinuousBatcher:
         replaced; None clears it.  May be called from inside the token callback (grammar-constrained decoding: advance the
         grammar on the event, hand the next step's mask back).  A request whose mask and options leave no token ends with end_id."""
         if allowed is None:
-            capi.check(capi.lib().ftcf_batcher_set_token_mask(self._h, C.c_long(int(request_id)), None, 0))
+            capi.check(capi.lib().ftcf_batcher_set_token_mask(self._h, int(request_id), None, 0))
             return
         V = int(self._op.vocab_size_)
         a = np.asarray(allowed if isinstance(allowed, np.ndarray) else list(allowed))
@@ -198,8 +186,7 @@ class ContinuousBatcher:
             bits = np.zeros(V, dtype=np.bool_)
             bits[a] = True
         words = np.ascontiguousarray(np.packbits(np.pad(bits, (0, -V % 32)), bitorder="little").view(np.uint32))
-        capi.check(capi.lib().ftcf_batcher_set_token_mask(self._h, C.c_long(int(request_id)), words.ctypes.data_as(C.POINTER(C.c_uint)),
-                                                          int(words.size)))
+        capi.check(capi.lib().ftcf_batcher_set_token_mask(self._h, int(request_id), capi.vp(words), int(words.size)))
 
     def submit_beam(self, prompt_ids, max_new_tokens, beam_width, beam_search_diversity_rate=0.0, len_penalty=0.0, temperature=1.0,
                     repetition_penalty=1.0, min_length=0, stop_words=None, token_log_probs=False):
@@ -209,27 +196,19 @@ class ContinuousBatcher:
         (GptNeoXOp.beam_log_probs)."""
         ids = np.ascontiguousarray(prompt_ids, dtype=np.int32).reshape(-1)
         rid = C.c_long(0)
-        sw, sw_len = None, 0
-        if stop_words:
-            flat = [t for w in stop_words for t in w]
-            sw_len = len(flat)
-            arr = np.zeros((2, sw_len), dtype=np.int32)  # to_word_list_format (codefuse_example.py:26-53)
-            arr[0] = flat
-            arr[1] = -1
-            arr[1, :len(stop_words)] = np.cumsum([len(w) for w in stop_words])
-            sw = np.ascontiguousarray(arr)
+        sw = _word_list(stop_words) if stop_words else None
+        sw_len = int(sw.shape[1]) if sw is not None else 0
         if token_log_probs:
             o = capi.BeamOptions(C.sizeof(capi.BeamOptions), int(beam_width), beam_search_diversity_rate, len_penalty, temperature,
                                  repetition_penalty, int(min_length),
-                                 sw.ctypes.data_as(C.POINTER(C.c_int)) if sw is not None else None, int(sw_len), 1)
-            capi.check(capi.lib().ftcf_batcher_submit_beam_opts(self._h, ids.ctypes.data, int(ids.size), int(max_new_tokens),
+                                 sw.ctypes.data_as(C.POINTER(C.c_int)) if sw is not None else None, sw_len, 1)
+            capi.check(capi.lib().ftcf_batcher_submit_beam_opts(self._h, capi.vp(ids), int(ids.size), int(max_new_tokens),
                                                                 C.byref(o), C.byref(rid)))
             self._beam_log_probs[int(rid.value)] = int(max_new_tokens)
             return int(rid.value)
         capi.check(capi.lib().ftcf_batcher_submit_beam_ex(
-            self._h, ids.ctypes.data_as(C.POINTER(C.c_int)), int(ids.size), int(max_new_tokens), int(beam_width),
-            C.c_float(beam_search_diversity_rate), C.c_float(len_penalty), C.c_float(temperature), C.c_float(repetition_penalty),
-            int(min_length), sw.ctypes.data_as(C.POINTER(C.c_int)) if sw is not None else None, int(sw_len), C.byref(rid)))
+            self._h, capi.vp(ids), int(ids.size), int(max_new_tokens), int(beam_width), beam_search_diversity_rate, len_penalty,
+            temperature, repetition_penalty, int(min_length), capi.vp(sw), sw_len, C.byref(rid)))
         return int(rid.value)
 
     def beam_result(self, request_id):
@@ -238,7 +217,7 @@ class ContinuousBatcher:
         token_log_probs=True returns a fourth array, token_log_probs [beam_width, max_new_tokens] float32: entry i belongs to
         output_ids[:, prompt_len + i]; 0 behind a hypothesis' first end token and in the end_id padding."""
         k, t = C.c_int(0), C.c_int(0)
-        capi.check(capi.lib().ftcf_batcher_beam_result(self._h, C.c_long(int(request_id)), None, None, None, 0, C.byref(k), C.byref(t)))
+        capi.check(capi.lib().ftcf_batcher_beam_result(self._h, int(request_id), None, None, None, 0, C.byref(k), C.byref(t)))
         if k.value == 0:
             return None
         ids = np.zeros((k.value, t.value), dtype=np.int32)
@@ -247,13 +226,11 @@ class ContinuousBatcher:
         if int(request_id) in self._beam_log_probs:
             lp = np.zeros((k.value, self._beam_log_probs[int(request_id)]), dtype=np.float32)
             capi.check(capi.lib().ftcf_batcher_beam_result_ex(
-                self._h, int(request_id), ids.ctypes.data, lens.ctypes.data, cum.ctypes.data, lp.ctypes.data, int(ids.size),
-                C.byref(k), C.byref(t)))
+                self._h, int(request_id), capi.vp(ids), capi.vp(lens), capi.vp(cum), capi.vp(lp), int(ids.size), C.byref(k), C.byref(t)))
             del self._beam_log_probs[int(request_id)]
             return ids, lens, cum, lp
         capi.check(capi.lib().ftcf_batcher_beam_result(
-            self._h, C.c_long(int(request_id)), ids.ctypes.data_as(C.POINTER(C.c_int)), lens.ctypes.data_as(C.POINTER(C.c_int)),
-            cum.ctypes.data_as(C.POINTER(C.c_float)), int(ids.size), C.byref(k), C.byref(t)))
+            self._h, int(request_id), capi.vp(ids), capi.vp(lens), capi.vp(cum), int(ids.size), C.byref(k), C.byref(t)))
         return ids, lens, cum
 
     def set_token_callback(self, fn):
@@ -326,7 +303,7 @@ class ContinuousBatcher:
     def cancel(self, request_id):
         """Drops a waiting or running request; returns False when the id is unknown or already finished."""
         found = C.c_int(0)
-        capi.check(capi.lib().ftcf_batcher_cancel(self._h, C.c_long(int(request_id)), C.byref(found)))
+        capi.check(capi.lib().ftcf_batcher_cancel(self._h, int(request_id), C.byref(found)))
         self._beam_log_probs.pop(int(request_id), None)  # (a cancelled beam request has no result to fetch)
         return bool(found.value)
 

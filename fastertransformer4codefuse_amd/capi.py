@@ -135,34 +135,109 @@ class ForwardStats(C.Structure):
                 ("spec_active", C.c_int), ("spec_steps", C.c_int), ("spec_drafted", C.c_int), ("spec_accepted", C.c_int)]
 
 
-# every symbol include/ftcf.h declares (tests/test_capi_host.py checks the list against the header and the library)
-EXPORTED = [
-    "ftcf_last_error", "ftcf_version", "ftcf_device_count", "ftcf_symmetric_quantize_int8",
-    "ftcf_symmetric_quantize_int8_device", "ftcf_symmetric_quantize_int8_device_workspace",
-    "ftcf_int8_rowmajor_to_tiled", "ftcf_int8_tiled_to_rowmajor", "ftcf_int8_cuda_sm80_to_rowmajor",
-    "ftcf_int8_rowmajor_to_cuda_sm80", "ftcf_fp16_rowmajor_to_tiled",
-    "ftcf_fpA_intB_gemm", "ftcf_fp16_gemm", "ftcf_lm_head", "ftcf_lm_head_layernorm", "ftcf_lm_head_log_probs",
-    "ftcf_gemm_smallm_group", "ftcf_gemm_smallm_workspace_bytes", "ftcf_gemm_smallm_ticket_bytes",
-    "ftcf_residual_dual_layernorm", "ftcf_add_bias_residual", "ftcf_ln_gemv", "ftcf_residual_gemv", "ftcf_residual_gemv_workspace_bytes", "ftcf_layernorm", "ftcf_add_bias_attn_ffn_residual",
-    "ftcf_masked_multihead_attention", "ftcf_masked_multihead_attention_workspace", "ftcf_masked_multihead_attention_beams",
-    "ftcf_context_attention", "ftcf_context_attention_range",
-    "ftcf_verify_attention", "ftcf_verify_attention_workspace", "ftcf_ngram_draft",
-    "ftcf_paged_attention", "ftcf_scatter_kv_to_pages", "ftcf_gather_pages_to_kv", "ftcf_pages_pack", "ftcf_pages_unpack",
-    "ftcf_dynamic_decode_step", "ftcf_beam_search_step", "ftcf_logit_process",
-    "ftcf_comm_get_unique_id", "ftcf_comm_init", "ftcf_comm_destroy", "ftcf_comm_local_unique_id",
-    "ftcf_comm_init_local", "ftcf_comm_init_host_exchange", "ftcf_comm_allreduce_sum",
-    "ftcf_comm_allgather", "ftcf_gptneox_create", "ftcf_gptneox_forward", "ftcf_gptneox_begin", "ftcf_gptneox_step", "ftcf_gptneox_finish",
-    "ftcf_gptneox_beam_log_probs", "ftcf_gptneox_get_stats",
-    "ftcf_gptneox_set_profiling", "ftcf_gptneox_destroy",
-    "ftcf_batcher_create", "ftcf_batcher_create_ex", "ftcf_batcher_create_opts", "ftcf_batcher_preempt_stats", "ftcf_batcher_prefix_stats", "ftcf_batcher_clear_prefix_cache", "ftcf_batcher_submit", "ftcf_batcher_submit_ex", "ftcf_batcher_submit_opts", "ftcf_batcher_submit_n", "ftcf_batcher_fork_stats", "ftcf_batcher_set_token_mask", "ftcf_batcher_submit_beam", "ftcf_batcher_submit_beam_ex", "ftcf_batcher_beam_result", "ftcf_batcher_submit_beam_opts", "ftcf_batcher_beam_result_ex", "ftcf_batcher_step", "ftcf_batcher_step_ex", "ftcf_batcher_step_top", "ftcf_batcher_set_token_callback", "ftcf_batcher_status", "ftcf_batcher_cancel", "ftcf_batcher_destroy"]
+# the header's name of every mirrored struct (tests/test_capi_abi.py compiles the header and compares size, offsets and field sizes)
+STRUCTS = {
+    "ftcf_smallm_problem": SmallmProblem, "ftcf_ln_gemv_args": LnGemvArgs, "ftcf_residual_gemv_args": ResidualGemvArgs,
+    "ftcf_dynamic_decode_args": DynamicDecodeArgs, "ftcf_beam_search_args": BeamSearchArgs,
+    "ftcf_logit_process_args": LogitProcessArgs, "ftcf_gptneox_config": GptNeoXConfig, "ftcf_gptneox_weights": GptNeoXWeights,
+    "ftcf_forward_args": ForwardArgs, "ftcf_forward_stats": ForwardStats, "ftcf_batcher_options": BatcherOptions,
+    "ftcf_logit_options": LogitOptions, "ftcf_beam_options": BeamOptions}
 
-# the entry points of the beam hypotheses' per-token log-probabilities
-BEAM_LOG_PROB_ARGTYPES = {
-    "ftcf_gptneox_beam_log_probs": [C.c_void_p, C.c_void_p, C.c_size_t],
-    "ftcf_batcher_submit_beam_opts": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(BeamOptions), C.POINTER(C.c_long)],
-    "ftcf_batcher_beam_result_ex": [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                    C.POINTER(C.c_int), C.POINTER(C.c_int)],
+# The prototype of every entry point: name -> (restype, argtypes), written out by hand in the header's order and held to the
+# header by tests/test_capi_abi.py.  int / ftcf_dtype / ftcf_act -> I, float -> F, size_t -> Z, long -> L, unsigned long long -> U;
+# every pointer, array parameter and handle -> P (c_void_p takes None, an address as int, byref(), ctypes arrays and pointers).
+I, F, Z, L, U, P = C.c_int, C.c_float, C.c_size_t, C.c_long, C.c_ulonglong, C.c_void_p
+_LAYOUT = [P, Z, Z, P]                       # (src, K, N, dst)
+_SUBMIT = [P, P, I, I, I, F, F, F, U, P, I]  # (b, prompt_ids, prompt_len, max_new_tokens, top_k, top_p, temperature,
+                                             #  repetition_penalty, seed, stop_words, stop_len)
+_SUBMIT_BEAM = [P, P, I, I, I, F, F, F, F]   # (b, prompt_ids, prompt_len, max_new_tokens, beam_width, beam_search_diversity_rate,
+                                             #  len_penalty, temperature, repetition_penalty)
+PROTOTYPES = {
+    "ftcf_last_error": (C.c_char_p, []),
+    "ftcf_version": (I, []),
+    "ftcf_device_count": (I, []),
+    "ftcf_symmetric_quantize_int8": (I, [P, I, Z, Z, Z, P, P]),
+    "ftcf_symmetric_quantize_int8_device": (I, [P, I, Z, Z, Z, P, P, P, Z, P]),
+    "ftcf_symmetric_quantize_int8_device_workspace": (Z, [Z, Z]),
+    "ftcf_int8_rowmajor_to_tiled": (I, _LAYOUT),
+    "ftcf_int8_tiled_to_rowmajor": (I, _LAYOUT),
+    "ftcf_int8_cuda_sm80_to_rowmajor": (I, _LAYOUT),
+    "ftcf_int8_rowmajor_to_cuda_sm80": (I, _LAYOUT),
+    "ftcf_fp16_rowmajor_to_tiled": (I, [P, Z, Z, P, P]),
+    "ftcf_fpA_intB_gemm": (I, [P, P, P, P, I, P, I, I, I, P]),
+    "ftcf_fp16_gemm": (I, [P, P, P, I, P, I, I, I, P]),
+    "ftcf_lm_head": (I, [P, P, P, I, I, I, I, P]),
+    "ftcf_lm_head_layernorm": (I, [P, P, P, P, F, P, P, I, I, I, I, P]),
+    "ftcf_lm_head_log_probs": (I, [P, P, P, P, P, I, I, I, P]),
+    "ftcf_gemm_smallm_group": (I, [C.POINTER(SmallmProblem), I, I, I, P, Z, Z, P, P, P]),
+    "ftcf_gemm_smallm_workspace_bytes": (Z, [I, I, I, I]),
+    "ftcf_gemm_smallm_ticket_bytes": (Z, []),
+    "ftcf_residual_dual_layernorm": (I, [P, P, P, P, I, I, P, P, P, P, P, P, I, I, F, I, I, P]),
+    "ftcf_add_bias_residual": (I, [P, P, P, P, I, I, P]),
+    "ftcf_ln_gemv": (I, [P, I, I, I, P]),
+    "ftcf_residual_gemv": (I, [P, I, I, I, P, Z, P, I, I, P]),
+    "ftcf_residual_gemv_workspace_bytes": (Z, [I, I, I]),
+    "ftcf_layernorm": (I, [P, P, P, P, I, I, F, I, P]),
+    "ftcf_add_bias_attn_ffn_residual": (I, [P, P, P, P, P, I, I, I, I, I, P]),
+    "ftcf_masked_multihead_attention": (I, [P] * 8 + [I] * 6 + [P, P, Z, P]),
+    "ftcf_masked_multihead_attention_workspace": (Z, [I, I, I, I]),
+    "ftcf_masked_multihead_attention_beams": (I, [I] + [P] * 9 + [I] * 9 + [P, P, Z, P]),
+    "ftcf_context_attention": (I, [P] * 5 + [I] * 6 + [P, P]),
+    "ftcf_context_attention_range": (I, [I] + [P] * 5 + [I] * 9 + [P, P]),
+    "ftcf_verify_attention": (I, [P] * 4 + [I] * 7 + [P, P, Z, P]),
+    "ftcf_verify_attention_workspace": (Z, [I, I, I, I]),
+    "ftcf_ngram_draft": (I, [P, I, I, I, P, P, P]),
+    "ftcf_paged_attention": (I, [P] * 7 + [I] * 7 + [P, P]),
+    "ftcf_scatter_kv_to_pages": (I, [P] * 5 + [I] * 6 + [Z, Z, P]),
+    "ftcf_gather_pages_to_kv": (I, [P] * 5 + [I] * 6 + [Z, Z, P]),
+    "ftcf_pages_pack": (I, [P] * 4 + [I] * 5 + [Z, P]),
+    "ftcf_pages_unpack": (I, [P] * 4 + [I] * 5 + [Z, P]),
+    "ftcf_dynamic_decode_step": (I, [P, P]),
+    "ftcf_beam_search_step": (I, [P, P]),
+    "ftcf_logit_process": (I, [P, P]),
+    "ftcf_comm_get_unique_id": (I, [P]),
+    "ftcf_comm_init": (I, [P, I, I, I, P]),
+    "ftcf_comm_destroy": (I, [P]),
+    "ftcf_comm_local_unique_id": (I, [P]),
+    "ftcf_comm_init_local": (I, [P, I, I, I, P]),
+    "ftcf_comm_init_host_exchange": (I, [I, I, I, HOST_ALLGATHER, P, P]),
+    "ftcf_comm_allreduce_sum": (I, [P, P, Z, I, P]),
+    "ftcf_comm_allgather": (I, [P, P, Z, I, P]),
+    "ftcf_gptneox_create": (I, [P, P, P]),
+    "ftcf_gptneox_forward": (I, [P, P]),
+    "ftcf_gptneox_begin": (I, [P, P]),
+    "ftcf_gptneox_step": (I, [P, I, P]),
+    "ftcf_gptneox_finish": (I, [P]),
+    "ftcf_gptneox_beam_log_probs": (I, [P, P, Z]),
+    "ftcf_gptneox_get_stats": (I, [P, P]),
+    "ftcf_gptneox_set_profiling": (I, [P, I]),
+    "ftcf_gptneox_destroy": (I, [P]),
+    "ftcf_batcher_create": (I, [P, I, I, I, I, P]),
+    "ftcf_batcher_create_ex": (I, [P, I, I, I, I, I, P]),
+    "ftcf_batcher_create_opts": (I, [P, P, P]),
+    "ftcf_batcher_preempt_stats": (I, [P] * 9),
+    "ftcf_batcher_prefix_stats": (I, [P] * 9),
+    "ftcf_batcher_clear_prefix_cache": (I, [P]),
+    "ftcf_batcher_submit": (I, [P, P, I, I, I, F, F, U, P]),
+    "ftcf_batcher_submit_ex": (I, _SUBMIT + [P]),
+    "ftcf_batcher_submit_opts": (I, _SUBMIT + [P, P]),
+    "ftcf_batcher_submit_n": (I, _SUBMIT + [P, I, P]),
+    "ftcf_batcher_fork_stats": (I, [P] * 5),
+    "ftcf_batcher_set_token_mask": (I, [P, L, P, I]),
+    "ftcf_batcher_submit_beam": (I, _SUBMIT_BEAM + [P]),
+    "ftcf_batcher_submit_beam_ex": (I, _SUBMIT_BEAM + [I, P, I, P]),
+    "ftcf_batcher_beam_result": (I, [P, L, P, P, P, I, P, P]),
+    "ftcf_batcher_submit_beam_opts": (I, [P, P, I, I, C.POINTER(BeamOptions), C.POINTER(C.c_long)]),
+    "ftcf_batcher_beam_result_ex": (I, [P, L, P, P, P, P, I, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "ftcf_batcher_step": (I, [P, P, P, P, I, P]),
+    "ftcf_batcher_step_ex": (I, [P, P, P, P, P, I, P]),
+    "ftcf_batcher_step_top": (I, [P, P, P, P, P, I, P, P, I, P]),
+    "ftcf_batcher_set_token_callback": (I, [P, BATCHER_TOKEN_CALLBACK, P]),
+    "ftcf_batcher_status": (I, [P] * 4),
+    "ftcf_batcher_cancel": (I, [P, L, P]),
+    "ftcf_batcher_destroy": (I, [P]),
 }
+EXPORTED = list(PROTOTYPES)  # every symbol include/ftcf.h declares
 
 _lib = None
 
@@ -175,18 +250,10 @@ def lib():
             raise FtcfError(-5, f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                                 "(hipcc, gfx950). There is no CPU fallback.")
         _lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-        _lib.ftcf_last_error.restype = C.c_char_p
-        _lib.ftcf_masked_multihead_attention_workspace.restype = C.c_size_t
-        if hasattr(_lib, "ftcf_verify_attention_workspace"):  # (FTCF_LIB_NAME may name an older build: the call itself then fails)
-            _lib.ftcf_verify_attention_workspace.restype = C.c_size_t
-        for name in ("ftcf_gemm_smallm_workspace_bytes", "ftcf_gemm_smallm_ticket_bytes", "ftcf_residual_gemv_workspace_bytes",
-                     "ftcf_symmetric_quantize_int8_device_workspace"):
-            if hasattr(_lib, name):
-                getattr(_lib, name).restype = C.c_size_t
-        for name, argtypes in BEAM_LOG_PROB_ARGTYPES.items():
-            if hasattr(_lib, name):
-                getattr(_lib, name).argtypes = argtypes
-                getattr(_lib, name).restype = C.c_int
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            if hasattr(_lib, name):  # (FTCF_LIB_NAME may name an older build: the call itself then fails)
+                fn = getattr(_lib, name)
+                fn.restype, fn.argtypes = restype, argtypes
     return _lib
 
 

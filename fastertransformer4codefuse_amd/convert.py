@@ -143,7 +143,6 @@ def import_cuda_qbin(in_dir, out_dir, tensor_para_size):
     cutlass_preprocessors.cc:500-539) into this engine's tile layout; scales and every other file are copied unchanged.
     The int8 values themselves are not touched: the result is what `quant` would have produced from the same weights."""
     from . import capi
-    import ctypes as C
     if os.path.exists(out_dir):
         shutil.rmtree(out_dir)
     shutil.copytree(in_dir, out_dir)
@@ -157,7 +156,6 @@ def import_cuda_qbin(in_dir, out_dir, tensor_para_size):
     shapes = {"attention.query_key_value.weight": (H, 3 * hl), "attention.dense.weight": (hl, H),
               "mlp.dense_h_to_4h.weight": (H, il), "mlp.dense_4h_to_h.weight": (il, H)}
     lib = capi.lib()
-    i8p = C.POINTER(C.c_int8)
     for rk in range(tensor_para_size):
         for fn, (K, N) in shapes.items():
             for li in range(L):
@@ -166,8 +164,8 @@ def import_cuda_qbin(in_dir, out_dir, tensor_para_size):
                 if q.size != K * N:
                     raise ValueError(f"{base}.q.bin holds {q.size} bytes, expected {K}x{N}")
                 rm, tiled = np.empty(K * N, np.int8), np.empty(K * N, np.int8)
-                capi.check(lib.ftcf_int8_cuda_sm80_to_rowmajor(q.ctypes.data_as(i8p), K, N, rm.ctypes.data_as(i8p)))
-                capi.check(lib.ftcf_int8_rowmajor_to_tiled(rm.ctypes.data_as(i8p), K, N, tiled.ctypes.data_as(i8p)))
+                capi.check(lib.ftcf_int8_cuda_sm80_to_rowmajor(capi.vp(q), K, N, capi.vp(rm)))
+                capi.check(lib.ftcf_int8_rowmajor_to_tiled(capi.vp(rm), K, N, capi.vp(tiled)))
                 tiled.tofile(base + ".q.bin")
 
 

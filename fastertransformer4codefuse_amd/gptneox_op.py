@@ -50,7 +50,7 @@ class LocalTensorParallelGroup:
 
     def __init__(self):
         ids = np.zeros(capi.UNIQUE_ID_BYTES, dtype=np.uint8)
-        capi.check(capi.lib().ftcf_comm_local_unique_id(ids.ctypes.data_as(C.POINTER(C.c_uint8))))
+        capi.check(capi.lib().ftcf_comm_local_unique_id(capi.vp(ids)))
         self.id = ids
 
 
@@ -62,8 +62,7 @@ def init_tensor_parallel_comm(group, rank, world_size, device):
     caller's process group (any backend)."""
     if isinstance(group, LocalTensorParallelGroup):
         comm = C.c_void_p()
-        capi.check(capi.lib().ftcf_comm_init_local(group.id.ctypes.data_as(C.POINTER(C.c_uint8)), world_size, rank, device,
-                                                   C.byref(comm)))
+        capi.check(capi.lib().ftcf_comm_init_local(capi.vp(group.id), world_size, rank, device, C.byref(comm)))
         return comm
     import torch.distributed as dist
     ids = np.zeros(capi.UNIQUE_ID_BYTES, dtype=np.uint8)
@@ -78,12 +77,12 @@ def init_tensor_parallel_comm(group, rank, world_size, device):
         # fake peers (bench.py --fake-tp N): ONE process runs one rank's shard of a TP=N model over a 1-rank communicator --
         # the kernels of a rank are all launched and the rank plays its own peers: outputs are those of a TP = N job whose
         # every rank holds shard `rank` (an all-reduce is TP x the rank's partial, the gathered logits TP copies of its slice)
-        capi.check(capi.lib().ftcf_comm_get_unique_id(ids.ctypes.data_as(C.POINTER(C.c_uint8))))
+        capi.check(capi.lib().ftcf_comm_get_unique_id(capi.vp(ids)))
         comm = C.c_void_p()
-        capi.check(capi.lib().ftcf_comm_init(ids.ctypes.data_as(C.POINTER(C.c_uint8)), 1, 0, device, C.byref(comm)))
+        capi.check(capi.lib().ftcf_comm_init(capi.vp(ids), 1, 0, device, C.byref(comm)))
         return comm
     if rank == 0:
-        capi.check(capi.lib().ftcf_comm_get_unique_id(ids.ctypes.data_as(C.POINTER(C.c_uint8))))
+        capi.check(capi.lib().ftcf_comm_get_unique_id(capi.vp(ids)))
     backend = dist.get_backend(group)
     t = torch.from_numpy(ids)
     if backend == "nccl":
@@ -92,8 +91,7 @@ def init_tensor_parallel_comm(group, rank, world_size, device):
     dist.broadcast(t, src=src, group=group)
     ids = t.cpu().numpy().copy()
     comm = C.c_void_p()
-    capi.check(capi.lib().ftcf_comm_init(ids.ctypes.data_as(C.POINTER(C.c_uint8)), world_size, rank, device,
-                                         C.byref(comm)))
+    capi.check(capi.lib().ftcf_comm_init(capi.vp(ids), world_size, rank, device, C.byref(comm)))
     return comm
 
 
@@ -334,9 +332,8 @@ def symmetric_quantize_last_axis_of_batched_matrix_int8(weight):
     q = torch.empty(weight.shape, dtype=torch.int8)
     scales = torch.empty((N,) if weight.dim() == 2 else (E, N), dtype=weight.dtype)
     capi.check(capi.lib().ftcf_symmetric_quantize_int8(
-        C.c_void_p(weight.data_ptr()),
-        {torch.float16: capi.FP16, torch.bfloat16: capi.BF16, torch.float32: capi.FP32}[weight.dtype], C.c_size_t(E),
-        C.c_size_t(K), C.c_size_t(N), C.c_void_p(q.data_ptr()), C.c_void_p(scales.data_ptr())))
+        capi.vp(weight), {torch.float16: capi.FP16, torch.bfloat16: capi.BF16, torch.float32: capi.FP32}[weight.dtype], E, K, N,
+        capi.vp(q), capi.vp(scales)))
     return [q, scales]
 
 
@@ -365,12 +362,10 @@ def symmetric_quantize_last_axis_of_batched_matrix_int8_device(weight):
     with torch.cuda.device(weight.device):
         q = torch.empty(weight.shape, dtype=torch.int8, device=weight.device)
         scales = torch.empty((N,) if weight.dim() == 2 else (E, N), dtype=weight.dtype, device=weight.device)
-        ws_bytes = int(capi.lib().ftcf_symmetric_quantize_int8_device_workspace(C.c_size_t(E), C.c_size_t(N)))
+        ws_bytes = int(capi.lib().ftcf_symmetric_quantize_int8_device_workspace(E, N))
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=weight.device)
         # (ws is freed to torch's caching allocator on return: a later allocation on the same stream is ordered after the kernels)
         capi.check(capi.lib().ftcf_symmetric_quantize_int8_device(
-            C.c_void_p(weight.data_ptr()),
-            {torch.float16: capi.FP16, torch.bfloat16: capi.BF16, torch.float32: capi.FP32}[weight.dtype], C.c_size_t(E),
-            C.c_size_t(K), C.c_size_t(N), C.c_void_p(q.data_ptr()), C.c_void_p(scales.data_ptr()), C.c_void_p(ws.data_ptr()),
-            C.c_size_t(ws_bytes), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            capi.vp(weight), {torch.float16: capi.FP16, torch.bfloat16: capi.BF16, torch.float32: capi.FP32}[weight.dtype], E, K, N,
+            capi.vp(q), capi.vp(scales), capi.vp(ws), ws_bytes, torch.cuda.current_stream().cuda_stream))
     return [q, scales]

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from fastertransformer4codefuse_amd import capi
+from tests.test_capi_abi import header_fields
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "fastertransformer4codefuse_amd", "csrc")
@@ -69,8 +70,7 @@ def test_the_new_entry_points_are_declared_and_exported():
     fields = [n for n, _ in capi.BatcherOptions._fields_]
     assert fields == ["struct_size", "max_batch", "page_tokens", "num_pages", "max_seq_len", "prefix_cache", "overcommit", "swap_pages",
                       "swap_stage_bytes"]
-    for f in fields:
-        assert re.search(r"\b" + f + r"\b", hdr.split("} ftcf_batcher_options;")[0].rsplit("typedef struct {", 1)[1]), f
+    assert fields == header_fields("ftcf_batcher_options")
     assert capi.lib().ftcf_version() == 100
 
 

@@ -4,8 +4,6 @@ ftcf_beam_options, the three new entry points."""
 import ctypes as C
 import inspect
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,9 +12,9 @@ import torch  # noqa: F401  (before the engine library: one HIP runtime in the p
 from fastertransformer4codefuse_amd import capi
 from oracle import oracle as orc
 from tests.beam_log_probs_reference import gather_tree_with_payload, step_differences
+from tests.test_capi_abi import CC, check_mirror
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CC = shutil.which("gcc") or shutil.which("cc")
 NEW = ("ftcf_gptneox_beam_log_probs", "ftcf_batcher_submit_beam_opts", "ftcf_batcher_beam_result_ex")
 
 
@@ -97,21 +95,11 @@ def test_step_differences_are_one_fp32_subtraction_against_the_parents_old_score
 
 
 @pytest.mark.skipif(CC is None, reason="no C compiler")
-def test_the_appended_field_and_the_options_struct_sit_where_the_header_puts_them(tmp_path):
-    src = tmp_path / "off.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "ftcf.h"\nint main(void) {\n'
-                   '  printf("%zu %zu %zu\\n", offsetof(ftcf_beam_search_args, step_log_probs), offsetof(ftcf_beam_search_args, end_id),'
-                   ' sizeof(ftcf_beam_search_args));\n'
-                   '  printf("%zu %zu %zu %zu\\n", sizeof(ftcf_beam_options), offsetof(ftcf_beam_options, struct_size),'
-                   ' offsetof(ftcf_beam_options, stop_words), offsetof(ftcf_beam_options, token_log_probs));\n  return 0;\n}\n')
-    exe = str(tmp_path / "off")
-    out = subprocess.run([CC, "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stderr
-    v = [int(x) for x in subprocess.run([exe], capture_output=True, text=True, timeout=60).stdout.split()]
+def test_the_appended_field_and_the_options_struct_sit_where_the_header_puts_them():
+    check_mirror("ftcf_beam_search_args")  # (every field's offset and size and the struct's size: tests/test_capi_abi.py)
+    check_mirror("ftcf_beam_options")
     A, O = capi.BeamSearchArgs, capi.BeamOptions
-    assert [A.step_log_probs.offset, A.end_id.offset, C.sizeof(A)] == v[:3]
     assert A._fields_[-1][0] == "step_log_probs" and A._fields_[-2][0] == "end_id", "appended: the old fields keep their places"
-    assert [C.sizeof(O), O.struct_size.offset, O.stop_words.offset, O.token_log_probs.offset] == v[3:]
     assert O._fields_[0][0] == "struct_size" and O.struct_size.offset == 0
 
 
@@ -123,7 +111,8 @@ def test_the_entry_points_are_declared_exported_and_bound():
     L = capi.lib()
     for name in NEW:
         assert name in capi.EXPORTED and hasattr(L, name), name
-        assert getattr(L, name).argtypes, name
+        restype, argtypes = capi.PROTOTYPES[name]
+        assert argtypes and list(getattr(L, name).argtypes) == argtypes and getattr(L, name).restype is restype is C.c_int, name
     from fastertransformer4codefuse_amd.batcher import ContinuousBatcher
     from fastertransformer4codefuse_amd.gptneox_op import GptNeoXOp
     p = list(inspect.signature(ContinuousBatcher.submit_beam).parameters.values())

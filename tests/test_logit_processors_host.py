@@ -6,38 +6,24 @@ import ctypes as C
 import inspect
 import math
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from fastertransformer4codefuse_amd import capi
 from tests import logit_processors_reference as lref
+from tests.test_capi_abi import CC, check_mirror
 from tests.test_kernel_resources import HIPCC, ROOT, _resource_usage
 
-CC = shutil.which("gcc") or shutil.which("cc")
 INF = float("inf")
 
 
 @pytest.mark.skipif(CC is None, reason="no C compiler")
-def test_struct_layouts_match_the_header(tmp_path):
+def test_struct_layouts_match_the_header():
     structs = {"ftcf_logit_options": capi.LogitOptions, "ftcf_logit_process_args": capi.LogitProcessArgs}
-    body = ""
     for struct, cls in structs.items():
-        for n, _ in cls._fields_:
-            body += f'  printf("%zu\\n", offsetof({struct}, {n}));\n'
-        body += f'  printf("%zu\\n", sizeof({struct}));\n'
-    src = tmp_path / "off.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "ftcf.h"\nint main(void) {\n' + body + "  return 0;\n}\n")
-    exe = str(tmp_path / "off")
-    out = subprocess.run([CC, "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stderr
-    vals = iter(int(v) for v in subprocess.run([exe], capture_output=True, text=True, timeout=60).stdout.split())
-    for struct, cls in structs.items():
-        offs = [next(vals) for _ in cls._fields_]
-        assert [getattr(cls, n).offset for n, _ in cls._fields_] == offs, struct
-        assert C.sizeof(cls) == next(vals), struct
+        check_mirror(struct)  # (every field's offset and size and the struct's size: tests/test_capi_abi.py)
+        offs = [getattr(cls, n).offset for n, _ in cls._fields_]
         assert offs == sorted(offs) and len(set(offs)) == len(offs), "every field of the header, in its order"
     assert capi.LogitOptions._fields_[0][0] == "struct_size" and capi.LogitProcessArgs._fields_[0][0] == "struct_size"
     assert [n for n, _ in capi.LogitOptions._fields_] == ["struct_size", "presence_penalty", "frequency_penalty", "min_new_tokens",

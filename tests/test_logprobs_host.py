@@ -2,13 +2,10 @@
 stores output_log_probs and the beam-search translation unit split off from it cross-compile for gfx950 without spills or
 scratch (the method of tests/test_kernel_resources.py), the fused greedy LM head keeps its register budget, and the ctypes
 ForwardArgs lays the two new fields out as the C header does."""
-import os
-import shutil
-import subprocess
-
 import pytest
 
-from tests.test_kernel_resources import HIPCC, ROOT, _resource_usage
+from tests.test_capi_abi import CC, check_mirror
+from tests.test_kernel_resources import HIPCC, _resource_usage
 
 
 @pytest.mark.skipif(HIPCC is None, reason="no hipcc")
@@ -43,22 +40,10 @@ def test_sampling_kernels_compile_without_new_spills_and_lm_head_greedy_keeps_it
             assert r.get("VGPRs Spill", 0) <= before[rows], (k, r)
 
 
-CC = shutil.which("gcc") or shutil.which("cc")
-
-
 @pytest.mark.skipif(CC is None, reason="no C compiler")
-def test_forward_args_offsets_match_the_header(tmp_path):
+def test_forward_args_offsets_match_the_header():
     from fastertransformer4codefuse_amd import capi
-    src = tmp_path / "off.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "ftcf.h"\nint main(void) {\n'
-                   '  printf("%zu %zu %zu %zu\\n", offsetof(ftcf_forward_args, debug_logits), '
-                   'offsetof(ftcf_forward_args, output_log_probs), offsetof(ftcf_forward_args, context_log_probs), '
-                   'sizeof(ftcf_forward_args));\n  return 0;\n}\n')
-    exe = str(tmp_path / "off")
-    out = subprocess.run([CC, "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stderr
-    dbg, olp, clp, size = (int(v) for v in subprocess.run([exe], capture_output=True, text=True, timeout=60).stdout.split())
+    check_mirror("ftcf_forward_args")  # (every field's offset and size and the struct's size: tests/test_capi_abi.py)
     F = capi.ForwardArgs
-    assert (F.debug_logits.offset, F.output_log_probs.offset, F.context_log_probs.offset) == (dbg, olp, clp)
-    assert capi.C.sizeof(F) == size
+    dbg, olp, clp = F.debug_logits.offset, F.output_log_probs.offset, F.context_log_probs.offset
     assert olp > dbg and clp > olp  # appended after the last existing field

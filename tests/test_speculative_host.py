@@ -2,35 +2,21 @@
 ftcf_forward_stats against a struct compiled from include/ftcf.h, the new entry points on a box without a GPU, and the
 Python-side argument validation."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CC = shutil.which("gcc") or shutil.which("cc")
+from tests.test_capi_abi import CC, check_mirror
 
 ARGS = ("context_log_probs", "speculative_tokens", "speculative_ngram", "draft_ids")
 STATS = ("persist_layout", "spec_active", "spec_steps", "spec_drafted", "spec_accepted")
 
 
 @pytest.mark.skipif(CC is None, reason="no C compiler")
-def test_ctypes_mirror_matches_the_header(tmp_path):
+def test_ctypes_mirror_matches_the_header():
     from fastertransformer4codefuse_amd import capi
-    offs = ", ".join([f"offsetof(ftcf_forward_args, {f})" for f in ARGS] + ["sizeof(ftcf_forward_args)"]
-                     + [f"offsetof(ftcf_forward_stats, {f})" for f in STATS] + ["sizeof(ftcf_forward_stats)"])
-    n = len(ARGS) + len(STATS) + 2
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "ftcf.h"\nint main(void) {\n  size_t v[] = {' + offs + '};\n'
-                   f'  for (int i = 0; i < {n}; i++) printf("%zu ", v[i]);\n  return 0;\n}}\n')
-    exe = tmp_path / "layout"
-    subprocess.check_call([CC, "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)], text=True).split()]
-    want = ([getattr(capi.ForwardArgs, f).offset for f in ARGS] + [C.sizeof(capi.ForwardArgs)]
-            + [getattr(capi.ForwardStats, f).offset for f in STATS] + [C.sizeof(capi.ForwardStats)])
-    assert got == want
+    check_mirror("ftcf_forward_args")  # (every field's offset and size and the struct's size: tests/test_capi_abi.py)
+    check_mirror("ftcf_forward_stats")
     # appended in the header's order, behind everything that was there
     names = [f for f, _ in capi.ForwardArgs._fields_]
     assert names[-4:] == list(ARGS)

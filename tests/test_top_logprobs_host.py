@@ -4,15 +4,12 @@ ftcf_dynamic_decode_args sit in the ctypes structs where the C header puts them,
 and bound, the Python entry points take the argument, and the two new kernels are in the sampling translation unit without scratch."""
 import inspect
 import os
-import shutil
-import subprocess
 
 import pytest
 
 from fastertransformer4codefuse_amd import capi
+from tests.test_capi_abi import CC, check_mirror
 from tests.test_kernel_resources import HIPCC, ROOT, _resource_usage
-
-CC = shutil.which("gcc") or shutil.which("cc")
 
 FIELDS = {
     "ftcf_forward_args": (capi.ForwardArgs, ("output_log_probs", "top_logprobs", "top_logprob_ids", "top_logprob_values",
@@ -22,22 +19,10 @@ FIELDS = {
 
 
 @pytest.mark.skipif(CC is None, reason="no C compiler")
-def test_struct_offsets_match_the_header(tmp_path):
-    body = ""
-    for struct, (_, names) in FIELDS.items():
-        for n in names:
-            body += f'  printf("%zu\\n", offsetof({struct}, {n}));\n'
-        body += f'  printf("%zu\\n", sizeof({struct}));\n'
-    src = tmp_path / "off.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "ftcf.h"\nint main(void) {\n' + body + "  return 0;\n}\n")
-    exe = str(tmp_path / "off")
-    out = subprocess.run([CC, "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stderr
-    vals = iter(int(v) for v in subprocess.run([exe], capture_output=True, text=True, timeout=60).stdout.split())
+def test_struct_offsets_match_the_header():
     for struct, (cls, names) in FIELDS.items():
-        offs = [next(vals) for _ in names]
-        assert [getattr(cls, n).offset for n in names] == offs, struct
-        assert capi.C.sizeof(cls) == next(vals), struct
+        check_mirror(struct)  # (every field's offset and size and the struct's size: tests/test_capi_abi.py)
+        offs = [getattr(cls, n).offset for n in names]
         assert offs == sorted(offs) and len(set(offs)) == len(offs), "in the header's order"
         fields = [f[0] for f in cls._fields_]
         assert fields[-(len(names) - 1):] == list(names[1:]) and fields[-len(names)] == names[0], "the struct's tail, in order"
