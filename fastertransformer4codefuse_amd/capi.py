@@ -64,6 +64,14 @@ class SmallmProblem(C.Structure):  # ftcf_smallm_problem
                 ("C", C.c_void_p), ("n", C.c_int), ("k", C.c_int)]
 
 
+class GemmPlan(C.Structure):  # ftcf_gemm_plan
+    _fields_ = [(n, C.c_int) for n in ("family", "tile_rows", "gx", "gy", "slices", "steps_per_slice", "ring", "prefetch",
+                                       "two_per_cu", "lone", "grid")]
+
+
+GEMM_SPLITK, GEMM_ROWS32, GEMM_ONE_WG, GEMM_FOUR_WAVE = 0, 1, 2, 3  # ftcf_gemm_plan.family
+
+
 class LnGemvArgs(C.Structure):  # ftcf_ln_gemv_args
     _fields_ = [(n, C.c_void_p) for n in ("x", "gamma0", "beta0", "gamma1", "beta1", "W0", "W1", "scale0", "scale1", "bias1",
                                           "out0", "out1")] + [("K", C.c_int), ("N0", C.c_int), ("N1", C.c_int), ("eps", C.c_float)]
@@ -137,7 +145,7 @@ class ForwardStats(C.Structure):
 
 # the header's name of every mirrored struct (tests/test_capi_abi.py compiles the header and compares size, offsets and field sizes)
 STRUCTS = {
-    "ftcf_smallm_problem": SmallmProblem, "ftcf_ln_gemv_args": LnGemvArgs, "ftcf_residual_gemv_args": ResidualGemvArgs,
+    "ftcf_smallm_problem": SmallmProblem, "ftcf_gemm_plan": GemmPlan, "ftcf_ln_gemv_args": LnGemvArgs, "ftcf_residual_gemv_args": ResidualGemvArgs,
     "ftcf_dynamic_decode_args": DynamicDecodeArgs, "ftcf_beam_search_args": BeamSearchArgs,
     "ftcf_logit_process_args": LogitProcessArgs, "ftcf_gptneox_config": GptNeoXConfig, "ftcf_gptneox_weights": GptNeoXWeights,
     "ftcf_forward_args": ForwardArgs, "ftcf_forward_stats": ForwardStats, "ftcf_batcher_options": BatcherOptions,
@@ -166,6 +174,7 @@ PROTOTYPES = {
     "ftcf_fp16_rowmajor_to_tiled": (I, [P, Z, Z, P, P]),
     "ftcf_fpA_intB_gemm": (I, [P, P, P, P, I, P, I, I, I, P]),
     "ftcf_fp16_gemm": (I, [P, P, P, I, P, I, I, I, P]),
+    "ftcf_gemm_tiled_plan": (I, [I, I, I, I, I, C.POINTER(GemmPlan)]),
     "ftcf_lm_head": (I, [P, P, P, I, I, I, I, P]),
     "ftcf_lm_head_layernorm": (I, [P, P, P, P, F, P, P, I, I, I, I, P]),
     "ftcf_lm_head_log_probs": (I, [P, P, P, P, P, I, I, I, P]),

@@ -128,6 +128,15 @@ extern "C" int ftcf_fp16_gemm(const void* A, const void* W, const void* bias, ft
                       (hipStream_t)stream, nullptr, 0, 256, nullptr, nullptr, abi_gemm_workspace(m, (hipStream_t)stream));
     });
 }
+extern "C" int ftcf_gemm_tiled_plan(int m, int n, int k, int int8, int has_workspace, ftcf_gemm_plan* out)
+{
+    return guarded([&] {  // (host only: no require_device)
+        FTCF_CHECK_ARG(out && m >= 1 && n >= 16 && k >= 64 && k % 64 == 0 && n % 16 == 0, "GEMM plan needs k % 64 == 0, n % 16 == 0");
+        const GemmTiledPlan p = gemm_tiled_plan(m, n, k, int8 != 0, has_workspace != 0);
+        *out = ftcf_gemm_plan{p.family, p.tile_rows, p.gx, p.gy, p.slices, p.steps_per_slice, p.ring, p.prefetch, p.two_per_cu, p.lone,
+                              p.grid};
+    });
+}
 extern "C" int ftcf_lm_head(const void* A, const void* W, float* logits, int m, int n, int k, int ldc, void* stream)
 {
     return guarded([&] {

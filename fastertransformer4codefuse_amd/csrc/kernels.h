@@ -74,6 +74,26 @@ size_t gemm_tiled_ticket_bytes();  // the workspace's tail
 int    gemm_tiled_splitk_max_m();  // rows up to which launch_gemm_tiled uses the workspace (FTCF_GEMM_SPLITK_MAX_M)
 void   launch_gemm_tiled(const f16* A, const void* W, const f16* scale, const f16* bias, int act, f16* C, int m, int n,
                          int k, bool int8, hipStream_t s, float* workspace = nullptr);
+// the form launch_gemm_tiled runs (m, n, k) in: its own variables, decided on the host without a device (ftcf_gemm_plan mirrors it)
+enum GemmTiledFamily {
+    GEMM_TILED_SPLITK    = 0,  // tiles cut along K, the slices reduced inside the launch (needs the workspace)
+    GEMM_TILED_ROWS32    = 1,  // 32 x 64 tiles on four waves, 2-D grid (no workspace, m <= 32)
+    GEMM_TILED_ONE_WG    = 2,  // one workgroup of eight waves per 64- or 128-row tile
+    GEMM_TILED_FOUR_WAVE = 3,  // fp16 weights from 2048 rows: 128 x 256 tiles on four waves
+};
+struct GemmTiledPlan {
+    int family;           // GemmTiledFamily
+    int tile_rows;        // 32 / 48 / 64 / 128
+    int gx, gy;           // column blocks, row blocks
+    int slices;           // K slices per tile (1 outside the split-K family)
+    int steps_per_slice;  // k-steps of 64 per slice; the last slice may hold fewer
+    int ring;             // 0 (plain loop), 2 or 4 k-steps
+    int prefetch;         // A fragments of a k-step read from LDS ahead of the dequantisation (PF)
+    int two_per_cu;       // register budget of two workgroups per CU (OCC2)
+    int lone;             // one-workgroup-per-tile family: at most 256 tiles, one workgroup per CU anyway
+    int grid;             // workgroups launched (gx rounded up to 8 where workgroups are placed by XCD)
+};
+GemmTiledPlan gemm_tiled_plan(int m, int n, int k, bool int8, bool has_workspace);
 // batched decode GEMM for m <= 16 rows (HBM bound forms); with a `workspace` (>= gemm_smallm_workspace_bytes of this
 // GEMM) the burst form runs: K slices of 20 tiles, every wave requests its whole slice at once
 // at once; `workspace` = [partial_bytes of split-K partial sums][gemm_smallm_ticket_bytes(), zeroed once before the first

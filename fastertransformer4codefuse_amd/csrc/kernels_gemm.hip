@@ -15,7 +15,8 @@
 // into ~256 workgroups, a ring of four k-steps of weight tiles and A-tile registers, the slices reduced inside the launch
 // (SPLITK, D = 4); more rows -- 64- or 128-row tiles, ring of two k-steps (D = 2) when the k-steps divide, with the A
 // fragments prefetched (PF) where one workgroup per CU runs anyway and held to 128 VGPRs (OCC2) otherwise; the plain loop
-// (D = 0) for odd k-step counts and without a workspace.  5..16 rows: k_gemm_smallm_burst below.
+// (D = 0) for odd k-step counts and without a workspace.  gemm_tiled_plan below decides the form on the host; the tests ask it
+// (ftcf_gemm_tiled_plan) which form a shape runs in.  5..16 rows: k_gemm_smallm_burst below.
 #include "ftcf_common.h"
 #include "kernels.h"
 
@@ -445,20 +446,21 @@ int gemm_tiled_splitk_max_m()
     return v;  // (the larger of the two weight forms' limits: who sizes a workspace by it covers both)
 }
 
-void launch_gemm_tiled(const f16* A, const void* W, const f16* scale, const f16* bias, int act, f16* C, int m, int n,
-                       int k, bool int8, hipStream_t s, float* workspace)
+// The form launch_gemm_tiled runs a GEMM in, from its shape alone (and FTCF_GEMM_SPLITK / FTCF_GEMM_SK128_MIN_M, read per call: the
+// tests switch them inside one process; FTCF_GEMM_SPLITK_MAX_M, read once).  Pure host code: the launcher launches from its
+// result, and ftcf_gemm_tiled_plan (include/ftcf.h) hands it to the tests, which pick their shapes by it.
+GemmTiledPlan gemm_tiled_plan(int m, int n, int k, bool int8, bool has_workspace)
 {
-    if (m == 0) {
-        return;
-    }
-    FTCF_CHECK_ARG(k % GEMM_KSTEP == 0, "GEMM needs k % 64 == 0 (as the reference: fpA_intB_gemm_template.h:159-163)");
-    FTCF_CHECK_ARG(n % 16 == 0, "GEMM needs n % 16 == 0");
-    const int NT = n / 16;
+    GemmTiledPlan p{};
+    const int NT     = n / 16;
+    const int ksteps = k / GEMM_KSTEP;
+    p.slices          = 1;
+    p.steps_per_slice = ksteps;
     const char*      sk_env        = getenv("FTCF_GEMM_SPLITK");  // (read per call: the tests switch it inside one process)
     const int        splitk_target = sk_env ? atoi(sk_env) : 256;
     static const int splitk_max_env = getenv("FTCF_GEMM_SPLITK_MAX_M") ? atoi(getenv("FTCF_GEMM_SPLITK_MAX_M")) : -1;
     const int splitk_max_m = splitk_max_env >= 0 ? splitk_max_env : (int8 ? GEMM_SPLITK_MAX_M_I8 : GEMM_SPLITK_MAX_M_F16);
-    if (workspace && m <= splitk_max_m && splitk_target > 0) {
+    if (has_workspace && m <= splitk_max_m && splitk_target > 0) {
         // 64-row tiles cut along K until ~1 workgroup per CU is in flight (FTCF_GEMM_SPLITK: the target number of workgroups)
         constexpr int deep = 4;  // ring depth of the split-K form (0 / 2: measured slower, profiles/r03_notes.md)
         // 64-row tiles; one row block (m <= 64): the lowest tile that covers it, 32 / 48 / 64 rows -- a 64-row tile on 17..32 rows
@@ -473,7 +475,6 @@ void launch_gemm_tiled(const f16* A, const void* W, const f16* scale, const f16*
         const int     RGs = (rgsel && m <= 64) ? std::max(2, (m + 15) / 16) : (m > sk128_min ? 8 : 4);
         const int BM = RGs * 16;
         const int gx = (NT + 8 * NG - 1) / (8 * NG), gy = (m + BM - 1) / BM, gx8 = 8 * ((gx + 7) / 8);
-        const int ksteps = k / GEMM_KSTEP;
         int       KS     = std::max(1, std::min({8, splitk_target / (gx8 * gy), ksteps / 8}));
         KS               = std::max<long>(1, std::min<long>(KS, (long)(GEMM_SPLITK_WS / (size_t)(BM * 256 * 4)) / ((long)gx * gy)));
         if (gx * gy <= (int)GEMM_SPLITK_TILES) {
@@ -482,9 +483,94 @@ void launch_gemm_tiled(const f16* A, const void* W, const f16* scale, const f16*
             const int  rnd = dd ? DQ : 1;
             const int  per = ((ksteps + KS - 1) / KS + rnd - 1) / rnd * rnd;
             KS             = (ksteps + per - 1) / per;  // no empty slice
-            f32x4*    ws   = reinterpret_cast<f32x4*>(workspace);
-            unsigned* tk   = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(workspace) + GEMM_SPLITK_WS);
-            dim3      grid(gx8 * gy * KS);
+            p.family          = GEMM_TILED_SPLITK;
+            p.tile_rows       = BM;
+            p.gx              = gx;
+            p.gy              = gy;
+            p.slices          = KS;
+            p.steps_per_slice = per;
+            p.ring            = dd ? DQ : 0;
+            p.prefetch        = dd;
+            p.grid            = gx8 * gy * KS;
+            return p;
+        }
+    }
+    if (m <= 32) {
+        p.family    = GEMM_TILED_ROWS32;
+        p.tile_rows = 32;
+        p.gx        = (NT + 3) / 4;
+        p.gy        = (m + 31) / 32;
+        p.grid      = p.gx * p.gy;
+        return p;
+    }
+    // Block tile 128 x 256 (RG, NG, WAVES) = (8, 2, 8).  Measured on the 13B layer at m = 1024 (tools/bench_gemm.py, us per
+    // layer of four GEMMs): 128 x 512 tiles 1006, 64 x 256 tiles 857, this 760; with `nt` weight loads and the plain
+    // 2-D grid 791 (int8) / 932 (fp16 weights).  hipBLASLt on the same fp16 shapes: 651-762 depending on the layout.
+    // Two things matter more than the tile: (1) the weight panel of a column block is read by every row block, so it is
+    // loaded with the default cache policy (the decode kernels' `nt` would drop it from the L2), and (2) the row blocks
+    // of one panel are placed on ONE XCD, next to each other in time (1-D grid, workgroup b runs on XCD b % 8): the panel
+    // crosses the fabric once instead of once per XCD.  Few tiles (m <= 512 with n = 5120: < 160 workgroups for 256
+    // CUs) -> 64-row tiles.
+    constexpr int NG = 2;
+    const int     gx = (NT + 8 * NG - 1) / (8 * NG);
+    constexpr int small_tiles = 160;
+    // (above 1024 rows also when the 128-row tiles would leave a partial round of the 256 CUs: n = 5120 at 1025..1536 rows is
+    // 180..240 tiles -- 13B prompt phase at 1536 tokens 51.2 -> 47.7 ms (int8), 54.0 -> 52.4 (fp16); at exactly 1024 rows, 160
+    // tiles, the 64-row form is SLOWER: 31.1 -> 32.5 / 33.1 -> 38.8)
+    const long    t128  = (long)gx * ((m + 127) / 128);
+    const bool    small = t128 < small_tiles || (m > 1024 && t128 < 256);
+    const int     gy = small ? (m + 63) / 64 : (m + 127) / 128;
+    // The ring form, two k-steps deep (it needs an even number of k-steps; else the plain loop).  At most one workgroup per CU
+    // (n = 5120 at m <= 1024: 160 tiles): with the A fragments prefetched, 163 VGPRs.  More tiles than that: without the
+    // prefetch and held to 128 VGPRs, so that two workgroups share a CU as in the plain form (124 VGPRs).  13B int8 layer,
+    // us, plain loop / ring at one workgroup per CU / ring at two: m = 1024: QKV 163 / 180 / 163, out-proj 91 / 80 / 93,
+    // FFN1 218 / 235 / 216, FFN2 293 / 270 / 295; m = 2048: 348 / 375 / 340, 138 / 147 / 135, 392 / 418 / 380, 506 / 532 / 487.
+    constexpr int big_deep = 2;
+    const int     bd       = ksteps % 2 == 0 ? big_deep : 0;
+    const bool    lone     = (long)gx * gy <= 256;
+    p.tile_rows = small ? 64 : 128;
+    p.gx        = gx;
+    p.gy        = gy;
+    p.grid      = 8 * ((gx + 7) / 8) * gy;
+    p.lone      = lone;
+    // fp16 weights from 2048 rows: the same 128 x 256 tile on FOUR waves of four column groups each -- an A fragment read from LDS
+    // feeds four MFMAs instead of two, two workgroups per CU (252 VGPRs, plain loop: the ring of two k-steps spills 58).  13B prompt
+    // phase, fp16 weights: 2048 tokens 64.4 -> 63.2 ms, 4096: 133.2 -> 129.6; at 1024 tokens it is slower (33.1 -> 34.7), and with
+    // int8 weights at every length (1024: 29.9 -> 33.4, 4096: 120.0 -> 121.0).
+    if (!int8 && !small && m >= 2048) {
+        p.family     = GEMM_TILED_FOUR_WAVE;
+        p.two_per_cu = 1;
+        return p;
+    }
+    p.family = GEMM_TILED_ONE_WG;
+    p.ring   = bd;
+    if (bd == 2 && lone) {
+        p.prefetch = 1;
+    }
+    else if (bd == 2) {
+        p.prefetch   = !int8;
+        p.two_per_cu = int8;
+    }
+    return p;
+}
+
+void launch_gemm_tiled(const f16* A, const void* W, const f16* scale, const f16* bias, int act, f16* C, int m, int n,
+                       int k, bool int8, hipStream_t s, float* workspace)
+{
+    if (m == 0) {
+        return;
+    }
+    FTCF_CHECK_ARG(k % GEMM_KSTEP == 0, "GEMM needs k % 64 == 0 (as the reference: fpA_intB_gemm_template.h:159-163)");
+    FTCF_CHECK_ARG(n % 16 == 0, "GEMM needs n % 16 == 0");
+    const GemmTiledPlan p = gemm_tiled_plan(m, n, k, int8, workspace != nullptr);
+    const int           gx = p.gx, gy = p.gy;
+    const dim3          grid(p.grid);
+    if (p.family == GEMM_TILED_SPLITK) {
+        constexpr int NG = 2, DQ = 4;
+        const int     RGs = p.tile_rows / 16, KS = p.slices, per = p.steps_per_slice;
+        const bool    dd  = p.ring == DQ;
+        f32x4*        ws  = reinterpret_cast<f32x4*>(workspace);
+        unsigned*     tk  = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(workspace) + GEMM_SPLITK_WS);
 #define FTCF_SK(I8, Dv, RGv)                                                                                                     \
     hipLaunchKernelGGL((k_gemm_tiled<I8, RGv, NG, 8, false, true, true, Dv, (Dv > 0)>), grid, dim3(512), 0, s, A, W, scale, bias, act, C, m, \
                        n, k, gx, gy, KS, per, ws, tk)
@@ -501,83 +587,50 @@ void launch_gemm_tiled(const f16* A, const void* W, const f16* scale, const f16*
     else {                                                                                                                       \
         FTCF_SK(I8, Dv, 4);                                                                                                      \
     }
-            if (int8 && dd) {
-                FTCF_SK_RG(true, DQ)
-            }
-            else if (int8) {
-                FTCF_SK_RG(true, 0)
-            }
-            else if (dd) {
-                FTCF_SK_RG(false, DQ)
-            }
-            else {
-                FTCF_SK_RG(false, 0)
-            }
-#undef FTCF_SK_RG
-#undef FTCF_SK
-            FTCF_HIP_CHECK(hipGetLastError());
-            return;
+        if (int8 && dd) {
+            FTCF_SK_RG(true, DQ)
         }
-    }
-    if (m <= 32) {
-        dim3 grid((NT + 3) / 4, (m + 31) / 32);
-        if (int8) {
-            hipLaunchKernelGGL((k_gemm_tiled<true, 2, 1, 4>), grid, dim3(256), 0, s, A, W, scale, bias, act, C, m, n, k);
+        else if (int8) {
+            FTCF_SK_RG(true, 0)
+        }
+        else if (dd) {
+            FTCF_SK_RG(false, DQ)
         }
         else {
-            hipLaunchKernelGGL((k_gemm_tiled<false, 2, 1, 4>), grid, dim3(256), 0, s, A, W, scale, bias, act, C, m, n, k);
+            FTCF_SK_RG(false, 0)
+        }
+#undef FTCF_SK_RG
+#undef FTCF_SK
+    }
+    else if (p.family == GEMM_TILED_ROWS32) {
+        const dim3 grid2(gx, gy);
+        if (int8) {
+            hipLaunchKernelGGL((k_gemm_tiled<true, 2, 1, 4>), grid2, dim3(256), 0, s, A, W, scale, bias, act, C, m, n, k);
+        }
+        else {
+            hipLaunchKernelGGL((k_gemm_tiled<false, 2, 1, 4>), grid2, dim3(256), 0, s, A, W, scale, bias, act, C, m, n, k);
         }
     }
+    else if (p.family == GEMM_TILED_FOUR_WAVE) {
+        hipLaunchKernelGGL((k_gemm_tiled<false, 8, 4, 4, false, true, false, 0, false, true>), grid, dim3(256), 0, s, A, W, scale, bias,
+                           act, C, m, n, k, gx, gy);
+    }
     else {
-        // Block tile 128 x 256 (RG, NG, WAVES) = (8, 2, 8).  Measured on the 13B layer at m = 1024 (tools/bench_gemm.py, us per
-        // layer of four GEMMs): 128 x 512 tiles 1006, 64 x 256 tiles 857, this 760; with `nt` weight loads and the plain
-        // 2-D grid 791 (int8) / 932 (fp16 weights).  hipBLASLt on the same fp16 shapes: 651-762 depending on the layout.
-        // Two things matter more than the tile: (1) the weight panel of a column block is read by every row block, so it is
-        // loaded with the default cache policy (the decode kernels' `nt` would drop it from the L2), and (2) the row blocks
-        // of one panel are placed on ONE XCD, next to each other in time (1-D grid, workgroup b runs on XCD b % 8): the panel
-        // crosses the fabric once instead of once per XCD.  Few tiles (m <= 512 with n = 5120: < 160 workgroups for 256
-        // CUs) -> 64-row tiles.
-        constexpr int NG = 2;
-        const int     gx = (NT + 8 * NG - 1) / (8 * NG);
-        constexpr int small_tiles = 160;
-        // (above 1024 rows also when the 128-row tiles would leave a partial round of the 256 CUs: n = 5120 at 1025..1536 rows is
-        // 180..240 tiles -- 13B prompt phase at 1536 tokens 51.2 -> 47.7 ms (int8), 54.0 -> 52.4 (fp16); at exactly 1024 rows, 160
-        // tiles, the 64-row form is SLOWER: 31.1 -> 32.5 / 33.1 -> 38.8)
-        const long    t128  = (long)gx * ((m + 127) / 128);
-        const bool    small = t128 < small_tiles || (m > 1024 && t128 < 256);
-        const int     gy = small ? (m + 63) / 64 : (m + 127) / 128;
-        dim3          grid(8 * ((gx + 7) / 8) * gy);
-        // The ring form, two k-steps deep (it needs an even number of k-steps; else the plain loop).  At most one workgroup per CU
-        // (n = 5120 at m <= 1024: 160 tiles): with the A fragments prefetched, 163 VGPRs.  More tiles than that: without the
-        // prefetch and held to 128 VGPRs, so that two workgroups share a CU as in the plain form (124 VGPRs).  13B int8 layer,
-        // us, plain loop / ring at one workgroup per CU / ring at two: m = 1024: QKV 163 / 180 / 163, out-proj 91 / 80 / 93,
-        // FFN1 218 / 235 / 216, FFN2 293 / 270 / 295; m = 2048: 348 / 375 / 340, 138 / 147 / 135, 392 / 418 / 380, 506 / 532 / 487.
-        constexpr int big_deep = 2;
-        const int        bd       = (k / GEMM_KSTEP) % 2 == 0 ? big_deep : 0;
-        const bool       lone     = (long)gx * gy <= 256;
+        constexpr int NG    = 2;
+        const bool    small = p.tile_rows == 64;
 #define FTCF_BIG(I8, RGv, Dv, PFv, O2v)                                                                                          \
     hipLaunchKernelGGL((k_gemm_tiled<I8, RGv, NG, 8, false, true, false, Dv, PFv, O2v>), grid, dim3(512), 0, s, A, W, scale, bias, act, \
                        C, m, n, k, gx, gy)
 #define FTCF_BIG_D(I8, RGv)                                                                                                      \
-    if (bd == 2 && lone) {                                                                                                       \
+    if (p.ring == 2 && p.lone) {                                                                                                 \
         FTCF_BIG(I8, RGv, 2, true, false);                                                                                       \
     }                                                                                                                            \
-    else if (bd == 2) {                                                                                                          \
+    else if (p.ring == 2) {                                                                                                      \
         FTCF_BIG(I8, RGv, 2, !I8, I8);                                                                                           \
     }                                                                                                                            \
     else {                                                                                                                       \
         FTCF_BIG(I8, RGv, 0, false, false);                                                                                      \
     }
-        // fp16 weights from 2048 rows: the same 128 x 256 tile on FOUR waves of four column groups each -- an A fragment read from LDS
-        // feeds four MFMAs instead of two, two workgroups per CU (252 VGPRs, plain loop: the ring of two k-steps spills 58).  13B prompt
-        // phase, fp16 weights: 2048 tokens 64.4 -> 63.2 ms, 4096: 133.2 -> 129.6; at 1024 tokens it is slower (33.1 -> 34.7), and with
-        // int8 weights at every length (1024: 29.9 -> 33.4, 4096: 120.0 -> 121.0).
-        if (!int8 && !small && m >= 2048) {
-            hipLaunchKernelGGL((k_gemm_tiled<false, 8, 4, 4, false, true, false, 0, false, true>), grid, dim3(256), 0, s, A, W, scale, bias,
-                               act, C, m, n, k, gx, gy);
-            FTCF_HIP_CHECK(hipGetLastError());
-            return;
-        }
         if (small && int8) {
             FTCF_BIG_D(true, 4)
         }

@@ -88,6 +88,24 @@ int ftcf_fpA_intB_gemm(const void* A, const int8_t* B_tiled, const void* scales,
  * optional fused bias+gelu reproduces invokeAddBiasGeluV2 (kernels/activation_kernels.cu:401-426). */
 int ftcf_fp16_gemm(const void* A, const void* W_tiled, const void* bias, ftcf_act act, void* C, int m, int n, int k,
                    void* stream);
+/* The form the two GEMMs above run (m, n, k) in above 16 rows (the tiled MFMA GEMM; the engine and the batcher launch it through
+ * the same decision).  Host only: no device is needed or touched.  has_workspace: whether the caller holds the split-K workspace;
+ * the two entry points above hold one for 17 <= m <= the largest split-K row count of either weight type (768).  The decision
+ * reads FTCF_GEMM_SPLITK and FTCF_GEMM_SK128_MIN_M at every call and FTCF_GEMM_SPLITK_MAX_M once per process, as the launch does.
+ * m >= 1, n % 16 == 0, k % 64 == 0, else FTCF_ERR_INVALID_ARG. */
+typedef struct {
+    int family;          /* 0 split-K, 1 32-row form, 2 one workgroup per tile, 3 four-wave form (fp16 weights) */
+    int tile_rows;       /* 32 / 48 / 64 / 128 */
+    int gx, gy;          /* column blocks (256 columns; 64 in the 32-row form), row blocks */
+    int slices;          /* K slices per tile; 1 outside the split-K family */
+    int steps_per_slice; /* k-steps (64 k) per slice; the last slice holds the remainder */
+    int ring;            /* ring depth in k-steps: 0 (plain loop), 2 or 4 */
+    int prefetch;        /* A fragments prefetched */
+    int two_per_cu;      /* register budget of two workgroups per CU */
+    int lone;            /* one workgroup per tile: at most 256 tiles */
+    int grid;            /* workgroups launched */
+} ftcf_gemm_plan;
+int ftcf_gemm_tiled_plan(int m, int n, int k, int int8, int has_workspace, ftcf_gemm_plan* out);
 /* LM head (models/gptneox/GptNeoX.cc:866-912): logits_f32[m, n] = A[m,k] (fp16) x W[n,k]^T (fp16, row major [V,H]) */
 int ftcf_lm_head(const void* A, const void* W_nk, float* logits, int m, int n, int k, int ldc, void* stream);
 /* The same LM head with the final LayerNorm (GptNeoX.cc:854-863) fused in front, as the engine's token loop runs it for <= 4

@@ -1,5 +1,5 @@
 """Inputs and error measures shared by the kernel-level tests of the forms the engine launches (test_gpu_burst_gemm.py,
-test_gpu_fused_ln.py, test_gpu_stage_gemv.py).  Plain numpy, but for dev16 and Weights, which put their data on the GPU.
+test_gpu_fused_ln.py, test_gpu_stage_gemv.py, test_gpu_tiled_gemm.py).  Plain numpy, but for dev16 and Weights, which put their data on the GPU.
 
 EXACT inputs: activations in {-1, 0, 1} (dense), weights small integers q in {-3..3} times a power of two that varies by column
 (the int8 scale, or folded into the fp16 weight), biases and residual inputs integer multiples of the column's unit.  Every
@@ -137,3 +137,72 @@ class Weights:
         if self.int8:
             return orc.gemm(A, q=self.q, scale=self.s32, bias=bias, act=act, fp16=True)
         return orc.gemm(A, W=self.w32, bias=bias, act=act, fp16=True)
+
+
+class GemmProblem:
+    """one GEMM C[m, n] = epilogue(A[m, k] x W) on new activations: device operands, an output of `rows` >= m rows filled with a
+    sentinel, and its reference.  epi 0: none, 1: bias, 2: bias + gelu."""
+
+    def __init__(self, rng, W, m, epi, rows):
+        self.W, self.m, self.epi = W, m, epi
+        k, n = W.k, W.n
+        self.expect = None
+        bias = None
+        if W.exact:
+            a = exact_acts(rng, m, k)
+            acc = np.rint(a.astype(np.float32) @ W.qf).astype(np.int64)  # exact: every partial sum is an integer < 2^24
+            assert_units(acc, "GEMM result")
+            self.A = a.astype(np.float32)
+            if epi:
+                b = rng.randint(-64, 65, size=n).astype(np.int64)
+                assert_units(acc + b, "GEMM result + bias")
+                bias = (b * W.unit).astype(np.float32)
+                acc = acc + b
+            if epi < 2:
+                self.expect = bits(half(acc * W.unit))
+        else:
+            self.A = half(rng.randn(m, k)).astype(np.float32)
+            if epi:
+                bias = half(rng.randn(n)).astype(np.float32)
+        self.bias = bias
+        self.dA = dev16(bits(half(self.A)))
+        self.dB = None if bias is None else dev16(bits(half(bias)))
+        self.sent = sentinel(rng, rows * n).reshape(rows, n)
+        self.dC = dev16(self.sent)
+
+    def tag(self):
+        return ("int8" if self.W.int8 else "fp16", self.m, self.W.n, self.W.k, self.epi)
+
+    def got(self):
+        import torch
+        torch.cuda.synchronize()
+        out = self.dC.cpu().numpy().view(np.uint16)
+        assert np.array_equal(out[self.m:], self.sent[self.m:]), ("rows >= m written", self.m, self.W.n, self.W.k)
+        return out[:self.m]
+
+    def check(self, oracle_ulps, kernel_ulps, worst=None, tag=None):
+        """-> the output bits.  exact: bit for bit; Gaussian without epilogue: ulps against float64 (and the oracle against it);
+        bias / gelu epilogues: the oracle at the tolerances test_gpu_kernels.py uses for it."""
+        import torch
+        out = self.got()
+        W, tag = self.W, tag or self.tag()
+        if self.expect is not None:
+            bad = np.argwhere(out != self.expect)
+            assert bad.size == 0, (tag, "not bit exact at (row, col)", bad[:8].tolist(),
+                                   out.view(np.float16)[tuple(bad[0])], self.expect.view(np.float16)[tuple(bad[0])])
+        elif self.epi:
+            ref = W.oracle(self.A, self.bias, 1 if self.epi == 2 else 0)
+            torch.testing.assert_close(torch.from_numpy(out.view(np.float16).astype(np.float32)), torch.from_numpy(ref), rtol=1e-3,
+                                       atol=2e-3, msg=lambda t: f"{tag}: {t}")
+        else:
+            A64 = self.A.astype(np.float64)
+            ref = half(A64 @ W.w64())
+            mag = (np.abs(A64) @ np.abs(W.w64())) / 128
+            e_o = float(ulps(W.oracle(self.A, None, 0), ref, mag).max())
+            e_k = float(ulps(out.view(np.float16), ref, mag).max())
+            print(f"[{tag}: oracle {e_o:.2f} ulp, kernel {e_k:.2f} ulp] ", end="")
+            if worst is not None:
+                worst[0], worst[1] = max(worst[0], e_o), max(worst[1], e_k)
+            assert e_o <= oracle_ulps, (tag, "oracle vs float64", e_o)
+            assert e_k <= kernel_ulps, (tag, "kernel vs float64", e_k)
+        return out

@@ -116,7 +116,7 @@ def check_mirror(struct):
     assert want == compiled_layouts()[struct], struct
 
 
-STRUCT_NAMES = ["ftcf_smallm_problem", "ftcf_ln_gemv_args", "ftcf_residual_gemv_args", "ftcf_dynamic_decode_args",
+STRUCT_NAMES = ["ftcf_smallm_problem", "ftcf_gemm_plan", "ftcf_ln_gemv_args", "ftcf_residual_gemv_args", "ftcf_dynamic_decode_args",
                 "ftcf_beam_search_args", "ftcf_logit_process_args", "ftcf_gptneox_config", "ftcf_gptneox_weights", "ftcf_forward_args",
                 "ftcf_forward_stats", "ftcf_batcher_options", "ftcf_logit_options", "ftcf_beam_options"]
 

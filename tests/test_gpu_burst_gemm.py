@@ -73,73 +73,19 @@ class Workspace:
 ROWS = 17  # rows of every output buffer: rows >= m must keep the sentinel
 
 
-class Problem:
-    """one GEMM on new activations: device operands, a sentinel-filled output and its reference.  epi 0: none, 1: bias, 2: bias +
-    gelu."""
+class Problem(ki.GemmProblem):
+    """one GEMM on new activations (kernel_inputs.GemmProblem) as a descriptor of the group launch; ROWS output rows"""
 
     def __init__(self, rng, W, m, epi):
-        self.W, self.m, self.epi = W, m, epi
-        k, n = W.k, W.n
-        self.expect = None
-        bias = None
-        if W.exact:
-            a = ki.exact_acts(rng, m, k)
-            acc = np.rint(a.astype(np.float32) @ W.qf).astype(np.int64)  # exact: every partial sum is an integer < 2^24
-            ki.assert_units(acc, "GEMM result")
-            self.A = a.astype(np.float32)
-            if epi:
-                b = rng.randint(-64, 65, size=n).astype(np.int64)
-                ki.assert_units(acc + b, "GEMM result + bias")
-                bias = (b * W.unit).astype(np.float32)
-                acc = acc + b
-            if epi < 2:
-                self.expect = ki.bits(ki.half(acc * W.unit))
-        else:
-            self.A = ki.half(rng.randn(m, k)).astype(np.float32)
-            if epi:
-                bias = ki.half(rng.randn(n)).astype(np.float32)
-        self.bias = bias
-        self.dA = dev16(ki.bits(ki.half(self.A)))
-        self.dB = None if bias is None else dev16(ki.bits(ki.half(bias)))
-        self.sent = ki.sentinel(rng, ROWS * n).reshape(ROWS, n)
-        self.dC = dev16(self.sent)
+        super().__init__(rng, W, m, epi, ROWS)
 
     def desc(self):
         return capi.SmallmProblem(A=self.dA.data_ptr(), W=self.W.W.data_ptr(), scale=0 if self.W.scale is None else self.W.scale.data_ptr(),
                                   bias=0 if self.dB is None else self.dB.data_ptr(), act=1 if self.epi == 2 else 0, C=self.dC.data_ptr(),
                                   n=self.W.n, k=self.W.k)
 
-    def got(self):
-        torch.cuda.synchronize()
-        out = self.dC.cpu().numpy().view(np.uint16)
-        assert np.array_equal(out[self.m:], self.sent[self.m:]), ("rows >= m written", self.m, self.W.n, self.W.k)
-        return out[:self.m]
-
     def check(self, worst=None):
-        """-> the output bits.  exact: bit for bit; Gaussian without epilogue: ulps against float64 (and the oracle against it);
-        bias / gelu epilogues: the oracle at the tolerances test_gpu_kernels.py uses for it."""
-        out = self.got()
-        W, tag = self.W, ("int8" if self.W.int8 else "fp16", self.m, self.W.n, self.W.k, self.epi)
-        if self.expect is not None:
-            bad = np.argwhere(out != self.expect)
-            assert bad.size == 0, (tag, "not bit exact at (row, col)", bad[:8].tolist(),
-                                   out.view(np.float16)[tuple(bad[0])], self.expect.view(np.float16)[tuple(bad[0])])
-        elif self.epi:
-            ref = W.oracle(self.A, self.bias, 1 if self.epi == 2 else 0)
-            torch.testing.assert_close(torch.from_numpy(out.view(np.float16).astype(np.float32)), torch.from_numpy(ref), rtol=1e-3,
-                                       atol=2e-3, msg=lambda t: f"{tag}: {t}")
-        else:
-            A64 = self.A.astype(np.float64)
-            ref = ki.half(A64 @ W.w64())
-            mag = (np.abs(A64) @ np.abs(W.w64())) / 128
-            e_o = float(ki.ulps(W.oracle(self.A, None, 0), ref, mag).max())
-            e_k = float(ki.ulps(out.view(np.float16), ref, mag).max())
-            print(f"[{tag}: oracle {e_o:.2f} ulp, kernel {e_k:.2f} ulp] ", end="")
-            if worst is not None:
-                worst[0], worst[1] = max(worst[0], e_o), max(worst[1], e_k)
-            assert e_o <= ORACLE_ULPS, (tag, "oracle vs float64", e_o)
-            assert e_k <= KERNEL_ULPS, (tag, "kernel vs float64", e_k)
-        return out
+        return super().check(ORACLE_ULPS, KERNEL_ULPS, worst)
 
 
 def launch(ws, probs, m, int8, d_step=None, offset=0, stream=None):
