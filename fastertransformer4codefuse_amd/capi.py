@@ -104,6 +104,17 @@ class LogitProcessArgs(C.Structure):  # ftcf_logit_process_args
                 ("slice", C.c_int), ("mask", C.c_void_p), ("mask_on", C.c_void_p)]
 
 
+class VerifyAcceptArgs(C.Structure):  # ftcf_verify_accept_args
+    _fields_ = [(n, C.c_int) for n in ("struct_size", "R", "V", "step", "end_id", "max_input_len", "total_len")] + [
+        ("logits", C.c_void_p), ("draft", C.c_void_p), ("output_ids", C.c_void_p), ("stop_words", C.c_void_p),
+        ("stop_len", C.c_int), ("finished", C.c_void_p), ("seq_len", C.c_void_p), ("cum_log_probs", C.c_void_p),
+        ("output_log_probs", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+        ("emitted", C.c_void_p), ("accepted", C.c_void_p), ("tokens", C.c_void_p)]
+
+
+VERIFY_ACCEPT_WORKSPACE_BYTES = 8192  # FTCF_VERIFY_ACCEPT_WORKSPACE_BYTES
+
+
 class LogitOptions(C.Structure):  # ftcf_logit_options
     _fields_ = [("struct_size", C.c_int), ("presence_penalty", C.c_float), ("frequency_penalty", C.c_float),
                 ("min_new_tokens", C.c_int), ("bias_ids", C.POINTER(C.c_int)), ("bias_values", C.POINTER(C.c_float)),
@@ -151,6 +162,10 @@ STRUCTS = {
     "ftcf_forward_args": ForwardArgs, "ftcf_forward_stats": ForwardStats, "ftcf_batcher_options": BatcherOptions,
     "ftcf_logit_options": LogitOptions, "ftcf_beam_options": BeamOptions}
 
+# ... and of the structs the header declares with a tag (`typedef struct NAME { ... } NAME;`): tests/test_speculative_scope_host.py
+# compares their layouts the same way
+TAGGED_STRUCTS = {"ftcf_verify_accept_args": VerifyAcceptArgs}
+
 # The prototype of every entry point: name -> (restype, argtypes), written out by hand in the header's order and held to the
 # header by tests/test_capi_abi.py.  int / ftcf_dtype / ftcf_act -> I, float -> F, size_t -> Z, long -> L, unsigned long long -> U;
 # every pointer, array parameter and handle -> P (c_void_p takes None, an address as int, byref(), ctypes arrays and pointers).
@@ -196,6 +211,7 @@ PROTOTYPES = {
     "ftcf_verify_attention": (I, [P] * 4 + [I] * 7 + [P, P, Z, P]),
     "ftcf_verify_attention_workspace": (Z, [I, I, I, I]),
     "ftcf_ngram_draft": (I, [P, I, I, I, P, P, P]),
+    "ftcf_verify_accept": (I, [P, P]),
     "ftcf_paged_attention": (I, [P] * 7 + [I] * 7 + [P, P]),
     "ftcf_scatter_kv_to_pages": (I, [P] * 5 + [I] * 6 + [Z, Z, P]),
     "ftcf_gather_pages_to_kv": (I, [P] * 5 + [I] * 6 + [Z, Z, P]),
@@ -220,6 +236,7 @@ PROTOTYPES = {
     "ftcf_gptneox_beam_log_probs": (I, [P, P, Z]),
     "ftcf_gptneox_get_stats": (I, [P, P]),
     "ftcf_gptneox_set_profiling": (I, [P, I]),
+    "ftcf_gptneox_set_speculative_scope": (I, [P, I]),
     "ftcf_gptneox_destroy": (I, [P]),
     "ftcf_batcher_create": (I, [P, I, I, I, I, P]),
     "ftcf_batcher_create_ex": (I, [P, I, I, I, I, I, P]),

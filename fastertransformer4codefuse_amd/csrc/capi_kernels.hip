@@ -495,6 +495,41 @@ extern "C" int ftcf_ngram_draft(const int* tokens, int n, int K, int N, int* dra
         launch_ngram_draft(tokens, n, nullptr, K, N, nullptr, 0, 0, draft, n_draft, nullptr, nullptr, (hipStream_t)stream);
     });
 }
+extern "C" int ftcf_verify_accept(const ftcf_verify_accept_args* a, void* stream)
+{
+    return guarded([&] {
+        require_device();
+        FTCF_CHECK_ARG(a != nullptr, "NULL argument");
+        FTCF_CHECK_ARG(a->struct_size == (int)sizeof(ftcf_verify_accept_args), "verify accept: struct_size is not sizeof(ftcf_verify_accept_args)");
+        FTCF_CHECK_ARG(a->R >= 1 && a->R <= VERIFY_MAX_ROWS && a->V >= 1, "verify accept: 1 <= R <= 16, V >= 1");
+        FTCF_CHECK_ARG(a->logits && a->output_ids && a->finished && a->seq_len && (a->R == 1 || a->draft), "verify accept: NULL tensor");
+        FTCF_CHECK_ARG(a->emitted && a->accepted && a->tokens, "verify accept: NULL output");
+        FTCF_CHECK_ARG(a->workspace && a->workspace_bytes >= verify_close_workspace_bytes(), "verify accept: workspace too small");
+        FTCF_CHECK_ARG(a->end_id >= 0 && a->end_id < a->V, "verify accept: end_id outside the vocabulary");
+        FTCF_CHECK_ARG(!a->stop_words || (a->stop_len >= 1 && a->stop_len <= 4096), "verify accept: stop_len must be in [1, 4096]");
+        VerifyCloseParams p{};
+        p.logits           = a->logits;
+        p.R                = a->R;
+        p.V                = a->V;
+        p.step             = a->step;
+        p.end_id           = a->end_id;
+        p.max_input_len    = a->max_input_len;
+        p.total_len        = a->total_len;
+        p.draft            = a->draft;
+        p.output_ids       = a->output_ids;
+        p.stop_words       = a->stop_words;
+        p.stop_len         = a->stop_len;
+        p.finished         = a->finished;
+        p.seq_len          = a->seq_len;
+        p.cum_log_probs    = a->cum_log_probs;
+        p.output_log_probs = a->output_log_probs;
+        p.emitted          = a->emitted;
+        p.accepted         = a->accepted;
+        p.tokens           = a->tokens;
+        p.ws               = (float*)a->workspace;
+        launch_verify_close(p, (hipStream_t)stream);
+    });
+}
 extern "C" int ftcf_context_attention(const void* qkv, const void* qkv_bias, const int* input_lengths, void* k_cache,
                                       void* v_cache, int B, int S, int nh, int dh, int rot, int s_max, void* ctx,
                                       void* stream)

@@ -186,11 +186,22 @@ void ftcf_gptneox::clear_exchange_window()
 // it always has, and the stats say so.  No side effect but ONE host synchronisation, issued only when everything else holds.
 bool ftcf_gptneox::speculation_wanted(const ftcf_forward_args& a, int total)
 {
+    // what the engine's scope decides (ftcf_gptneox_set_speculative_scope): at scope 0 a request with any of these runs
+    // unspeculated; at scope 1 the pass's tail (k_verify_close) serves them.  optional_last_tokens masks the first generated step
+    // only, which never drafts.  A temperature leaves the arg max alone but not the soft-max: with a log-probability output it
+    // still excludes the request.
+    const bool log_probs = a.return_cum_log_probs || a.output_log_probs;
+    bool       scoped    = !a.callback && !log_probs && !a.stop_words_list && !a.optional_last_tokens;
+    if (spec_scope == 1) {
+        scoped = true;
+        for (int i = 0; log_probs && i < a.n_temperature; i++) {
+            scoped &= a.temperature && a.temperature[i] == 1.f;
+        }
+    }
     const bool eligible =
         a.speculative_tokens > 0 && a.batch_size == 1 && a.beam_width == 1 && !fp32 && cfg.tensor_para_size == 1 && cfg.use_gptj_residual
-        && prefill_begin == 0 && verify_attention_supported(nhl, dh, total) && H % 64 == 0 && hl % 64 == 0 && il % 64 == 0 && !a.callback
-        && !a.return_cum_log_probs && !a.output_log_probs && a.top_logprobs == 0 && !a.debug_logits && !a.stop_words_list
-        && !a.optional_last_tokens && a.n_min_length == 0 && (a.n_top_k == 0 || (a.top_k && a.top_k[0] <= 1))
+        && prefill_begin == 0 && verify_attention_supported(nhl, dh, total) && H % 64 == 0 && hl % 64 == 0 && il % 64 == 0 && scoped
+        && a.top_logprobs == 0 && !a.debug_logits && a.n_min_length == 0 && (a.n_top_k == 0 || (a.top_k && a.top_k[0] <= 1))
         && (a.n_top_p == 0 || (a.top_p && a.top_p[0] == 0.f))
         && (a.n_repetition_penalty == 0 || (a.repetition_penalty && a.repetition_penalty[0] == 1.f)) && !logits_hook;
     if (!eligible) {
@@ -474,6 +485,7 @@ void ftcf_gptneox::begin(const ftcf_forward_args& a)
     FTCF_HIP_CHECK(hipEventRecord(e1, stream));
 
     ses.open(a, session_sampling_params(a, route, in_len), session_beam_params(a, route, in_len), e0, e1, spec_plan);
+    ses.spec_scope = spec_scope;
     stats.decode_ms = 0.f;
 }
 
@@ -744,20 +756,44 @@ void ftcf_gptneox::verify_pass(int st, int drafts)
         [](f16*, size_t, hipStream_t, bool) {}, [&](double bytes, auto&& launch, hipStream_t s) { timed(KIND_SMALLM, bytes, launch, s); });
     launch_layernorm(vx, final_g, final_b, vnrm, R, H, 1e-5f, true, stream);
     timed(KIND_LM_HEAD, 2.0 * V * H, [&] { lm_head_dispatch(vnrm, lm_head, vlogits, R, V, H, V, stream); });
-    VerifyAcceptParams vp{};
-    vp.logits     = vlogits;
-    vp.R          = R;
-    vp.V          = V;
-    vp.step       = st;
-    vp.end_id     = cfg.end_id;
-    vp.draft      = spec_draft;
-    vp.output_ids = step_ids;
-    vp.finished   = finished;
-    vp.seq_len    = seq_len;
-    vp.state      = state;
-    vp.h_flags    = h_flags;
-    vp.argmax_ws  = spec_argmax;
-    launch_verify_accept(vp, stream);
+    if (ses.spec_scope == 1) {  // stop words, log-probabilities and the callback's tokens are the tail's business
+        VerifyCloseParams cp{};
+        cp.logits           = vlogits;
+        cp.R                = R;
+        cp.V                = V;
+        cp.step             = st;
+        cp.end_id           = cfg.end_id;
+        cp.max_input_len    = ses.S;
+        cp.total_len        = ses.total;
+        cp.draft            = spec_draft;
+        cp.output_ids       = step_ids;
+        cp.stop_words       = ses.sp.stop_words;
+        cp.stop_len         = ses.sp.stop_len;
+        cp.finished         = finished;
+        cp.seq_len          = seq_len;
+        cp.cum_log_probs    = ses.sp.return_cum_log_probs ? cum : nullptr;
+        cp.output_log_probs = ses.sp.return_cum_log_probs ? ses.sp.output_log_probs : nullptr;
+        cp.state            = state;
+        cp.h_flags          = h_flags;
+        cp.ws               = spec_close_ws;
+        launch_verify_close(cp, stream);
+    }
+    else {
+        VerifyAcceptParams vp{};
+        vp.logits     = vlogits;
+        vp.R          = R;
+        vp.V          = V;
+        vp.step       = st;
+        vp.end_id     = cfg.end_id;
+        vp.draft      = spec_draft;
+        vp.output_ids = step_ids;
+        vp.finished   = finished;
+        vp.seq_len    = seq_len;
+        vp.state      = state;
+        vp.h_flags    = h_flags;
+        vp.argmax_ws  = spec_argmax;
+        launch_verify_accept(vp, stream);
+    }
     // what the next plain step expects of the step before it (k_greedy_decode's tail): the embedding row of the last token emitted
     // and the rotary table of its position
     launch_step_prologue(x, wte, step_ids, &state->step, rot_table, pad_count, 1, H, rot, stream, &state->all_finished);
@@ -772,6 +808,26 @@ int ftcf_gptneox::step_speculative(int max_steps)
     const ftcf_forward_args& a = ses.a;
     const int       S = ses.S, total = ses.total;
     DecodeStopwatch watch(*this);
+    // The streaming callback of a request that speculates (scope 1), once per emitted token in order, with what the plain loop's
+    // report_tokens(step) passes for that step: the token and the sequence length behind it (a row that did not advance reports
+    // end_id), not for the request's last position.  A pass left both in the pinned flags; a plain step's are copied as there.
+    auto report_tokens = [&](int st, int emitted, bool pass) {
+        for (int i = 0; i < emitted && st + i + 1 < total; i++) {
+            int tok = 0, idx = 0;
+            if (pass) {
+                tok = h_flags[FLAG_SPEC_TOKENS + i];
+                idx = h_flags[FLAG_SPEC_SEQ_LEN + i];
+            }
+            else {
+                FTCF_HIP_CHECK(hipMemcpy(&tok, step_ids + st, sizeof(int), hipMemcpyDeviceToHost));
+                FTCF_HIP_CHECK(hipMemcpy(&idx, seq_len, sizeof(int), hipMemcpyDeviceToHost));
+            }
+            if (idx != st + i) {
+                tok = cfg.end_id;
+            }
+            a.callback(&tok, &idx, ses.batch, ses.K, a.callback_user);
+        }
+    };
     int done = 0;
     while (done < max_steps && ses.next_step < total && !ses.all_finished) {
         const int  st           = ses.next_step;
@@ -805,6 +861,9 @@ int ftcf_gptneox::step_speculative(int max_steps)
         done += emitted;
         ses.all_finished = h_flags[FLAG_ALL_FINISHED] != 0;
         ses.spec_nd      = h_flags[FLAG_SPEC_NEXT_DRAFTS];
+        if (a.callback && cfg.tensor_para_rank == 0) {
+            report_tokens(st, emitted, nd > 0);
+        }
     }
     watch.stop("the token loop");
     watch.add_to_stats();
@@ -1182,7 +1241,7 @@ extern "C" int ftcf_gptneox_create(const ftcf_gptneox_config* cfg, const ftcf_gp
             FTCF_HIP_CHECK(hipMalloc((void**)&e->tp_scratch, 256));
             FTCF_HIP_CHECK(hipMemsetAsync(e->tp_scratch, 0, 256, e->stream));
         }
-        FTCF_HIP_CHECK(hipHostMalloc((void**)&e->h_flags, 64, hipHostMallocDefault));
+        FTCF_HIP_CHECK(hipHostMalloc((void**)&e->h_flags, FLAG_WORDS * sizeof(int), hipHostMallocDefault));
         e->h_flags[FLAG_ALL_FINISHED] = e->h_flags[FLAG_LAST_STEP] = e->h_flags[FLAG_LM_GREEDY_GAVE_UP] = 0;
         FTCF_HIP_CHECK(hipStreamSynchronize(e->stream));
         if (e->bounce) {
@@ -1264,6 +1323,15 @@ extern "C" int ftcf_gptneox_set_profiling(ftcf_gptneox_t h, int enabled)
             h->kind_ms[k] = h->kind_bytes[k] = 0;
             h->kind_n[k]                     = 0;
         }
+    });
+}
+
+extern "C" int ftcf_gptneox_set_speculative_scope(ftcf_gptneox_t h, int scope)
+{
+    return guarded([&] {
+        FTCF_CHECK_ARG(h, "NULL argument");
+        FTCF_CHECK_ARG(scope == 0 || scope == 1, "speculative scope must be 0 or 1");
+        h->spec_scope = scope;
     });
 }
 

@@ -225,6 +225,10 @@ struct ftcf_gptneox {
     float *vlogits = nullptr, *vrot = nullptr, *spec_aws = nullptr, *spec_gws = nullptr;
     size_t spec_partial = 0;  // split-K partials of the pass's burst GEMMs (a workspace of their own: [partials][tickets])
     int *  spec_draft = nullptr, *spec_ndraft = nullptr, *spec_argmax = nullptr;
+    float* spec_close_ws = nullptr;  // the slice partials of k_verify_close (scope 1)
+    // which requests may speculate (ftcf_gptneox_set_speculative_scope): 0 the bare greedy request, 1 also one with stop words,
+    // log-probabilities, a streaming callback or optional_last_tokens.  Read by begin(): a request keeps the scope it began under.
+    int    spec_scope = 0;
 
     // profiling
     bool               profiling = false;
@@ -471,6 +475,7 @@ struct ftcf_gptneox {
         spec_draft   = c.take<int>(R);
         spec_ndraft  = c.take<int>(4);
         spec_argmax  = c.take<int>(2 * R);
+        spec_close_ws = c.take<float>(verify_close_workspace_bytes() / 4);
     }
     // B = rows of the request (batch * beam_width)
     void plan(int B, int S, int total, int K)
@@ -1381,6 +1386,7 @@ struct ftcf_gptneox {
         // speculative decoding: on for this request; K, N; the draft count the last step's draft kernel left for the next one;
         // verify passes, drafts proposed / accepted so far
         bool              spec = false;
+        int               spec_scope = 0;  // the engine's scope when the request began: 1 closes a pass with k_verify_close
         int               spec_K = 0, spec_N = 0, spec_nd = 0;
         int               spec_steps = 0, spec_drafted = 0, spec_accepted = 0;
         // the state a request starts its token loop from: everything above as declared (no step taken; no graph captured: the

@@ -414,7 +414,11 @@ enum HostFlag {
     FLAG_SPEC_EMITTED      = 3,  // tokens emitted by a verify pass
     FLAG_SPEC_NEXT_DRAFTS  = 4,  // the draft kernel's count for the next step
     FLAG_SPEC_ACCEPTED     = 5,  // drafts of the verify pass that became output tokens
-    FLAG_COUNT             = 6
+    FLAG_COUNT             = 6,
+    // a verify pass closed by k_verify_close (speculative scope 1): the tokens it emitted and the sequence length behind each
+    FLAG_SPEC_TOKENS       = 16,  // [VERIFY_MAX_ROWS]
+    FLAG_SPEC_SEQ_LEN      = 32,  // [VERIFY_MAX_ROWS]
+    FLAG_WORDS             = 48   // words of the engine's mailbox
 };
 struct DecodeState {  // device resident, one per engine
     int step;         // current step (max_input_len .. total-1)
@@ -577,6 +581,35 @@ struct VerifyAcceptParams {
     int*         argmax_ws;
 };
 void launch_verify_accept(const VerifyAcceptParams& p, hipStream_t s);
+// The same acceptance for a request with stop words, log-probabilities or a streaming callback (speculative scope 1; the
+// stand-alone ftcf_verify_accept of include/ftcf.h is the contract), in two launches: k_verify_slices reduces every row in
+// VERIFY_ACCEPT_SLICES vocabulary slices to {best, index, max, sum of exponentials}, k_verify_close merges them in slice order
+// and closes the step: for i = 0 .. m in order the token a[i] goes to output_ids[step + i], its log-probability
+// logf(exp(v - max) / (sum + 1e-6f)) is added to cum_log_probs[0] (sequential fp32 adds) and stored at
+// output_log_probs[step + i - max_input_len], then end_id, the stop words (decode_finish_body's rule at step + i, over the history
+// and the tokens just written) and the length criterion are tested; nothing is written behind the first token that finishes the
+// row.  One row of one sequence: output_ids is [total_len].  step >= max(1, max_input_len), step + R <= total_len.
+// state / h_flags (the engine's; the flags of launch_verify_accept plus FLAG_SPEC_TOKENS / FLAG_SPEC_SEQ_LEN) and emitted /
+// accepted / tokens [16] (device) may each be NULL.  ws: verify_close_workspace_bytes().
+constexpr int VERIFY_ACCEPT_SLICES = 32;
+struct VerifyCloseParams {
+    const float* logits;  // [R, V]
+    int          R, V, step, end_id, max_input_len, total_len;
+    const int*   draft;  // [R - 1]
+    int*         output_ids;
+    const int*   stop_words;  // [2, stop_len] or NULL
+    int          stop_len;
+    uint8_t*     finished;
+    int*         seq_len;
+    float*       cum_log_probs;     // [1] or NULL
+    float*       output_log_probs;  // [total_len - max_input_len] or NULL
+    DecodeState* state;
+    int*         h_flags;
+    int *        emitted, *accepted, *tokens;
+    float*       ws;
+};
+size_t verify_close_workspace_bytes();
+void   launch_verify_close(const VerifyCloseParams& p, hipStream_t s);
 
 // ---- per-request logit processors over logits [B, V] fp32, in place, BEFORE the dynamic decode : kernels_logits.hip ----
 // (include/ftcf.h ftcf_logit_process_args is the contract; the fields are its fields.)  A row is processed when it is enabled

@@ -11,10 +11,12 @@
 //      the reference's + 1e-6, the context rounded once.
 //  * k_ngram_draft      : prompt-lookup drafting, one workgroup.
 //  * k_verify_embed / k_verify_argmax / k_verify_accept : the pass's input rows and the greedy acceptance rule.
+//  * k_verify_slices / k_verify_close : the acceptance rule of a request with stop words, log-probabilities or a callback.
 //
 // Roofline: HBM (4 * len * dh * nh bytes per layer, once for all rows); the VALU work grows with R (R * dh fused
 // multiply-adds per key and head, twice).
 #include "attn_device.hip.h"
+#include "sampling_device.hip.h"
 
 namespace ftcf {
 
@@ -561,6 +563,248 @@ void launch_verify_accept(const VerifyAcceptParams& p, hipStream_t s)
     FTCF_CHECK_ARG(p.R >= 1 && p.R <= VERIFY_MAX_ROWS && p.V >= 1, "verify accept: bad arguments");
     hipLaunchKernelGGL(k_verify_argmax, dim3(p.R), dim3(256), 0, s, p.logits, p.V, p.argmax_ws);
     hipLaunchKernelGGL(k_verify_accept, dim3(1), dim3(64), 0, s, p);
+    FTCF_HIP_CHECK(hipGetLastError());
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The decode tail of a verify pass whose request has stop words, log-probabilities or a streaming callback (speculative scope 1,
+// DESIGN.md section 4g), in two launches:
+//  * k_verify_slices : grid (VS_SLICES, R).  A workgroup reduces its contiguous slice of its row to {best value, best index,
+//      slice max, sum of exp(v - slice max)} -- the partial of k_greedy_decode -- with VS_MAXE loads per thread in flight, chunk by
+//      chunk for a slice longer than 256 * VS_MAXE logits (any V).  Against k_verify_argmax (one workgroup per row: V / 256
+//      DEPENDENT loads per thread, 394 at V = 100864) a row is read by 32 workgroups at 13 independent loads per thread.
+//  * k_verify_close  : one workgroup.  Every row's partials are merged in slice order by one thread (a fixed order: two launches
+//      give identical bits), then the step is closed in one place: the accepted prefix, the tokens, their log-probabilities, the
+//      end token, the stop words (decode_finish_body's rule, kernels_sampling.hip), the length criterion, the state words and
+//      the pinned flags -- with the emitted tokens and the sequence length behind each, so that the host's callback copies nothing.
+// No workgroup waits for another: the launch boundary orders the partials.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int VS_SLICES = VERIFY_ACCEPT_SLICES;
+constexpr int VS_MAXE   = 16;  // logits per thread and chunk
+
+__global__ __launch_bounds__(256) void k_verify_slices(const float* __restrict__ logits, const int V, float* part)
+{
+    __shared__ float redv[4], redm[4], reds[4];
+    __shared__ int   redi[4];
+    const int    r = blockIdx.y, blk = blockIdx.x, lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int    slice = (V + VS_SLICES - 1) / VS_SLICES;
+    const int    i0 = blk * slice;
+    const int    n  = max(0, min(slice, V - i0));
+    const float* l  = logits + (size_t)r * V + i0;
+    VI    best{-INFINITY, 0x7fffffff};
+    float m = -FLT_MAX, se = 0.f;
+    for (int c0 = 0; c0 < n; c0 += 256 * VS_MAXE) {
+        float vals[VS_MAXE];
+#pragma unroll
+        for (int j = 0; j < VS_MAXE; j++) {  // (clamped, never conditional: all loads of the chunk are in flight together)
+            const int i = c0 + (int)threadIdx.x + 256 * j;
+            vals[j]     = l[i < n ? i : n - 1];
+        }
+        float cm = m;
+#pragma unroll
+        for (int j = 0; j < VS_MAXE; j++) {
+            const int i = c0 + (int)threadIdx.x + 256 * j;
+            if (i < n) {
+                cm = fmaxf(cm, vals[j]);
+                if (best.i == 0x7fffffff || better(vals[j], i0 + i, best.v, best.i)) {
+                    best.v = vals[j];
+                    best.i = i0 + i;
+                }
+            }
+        }
+        se *= __expf(m - cm);
+#pragma unroll
+        for (int j = 0; j < VS_MAXE; j++) {
+            if (c0 + (int)threadIdx.x + 256 * j < n) {
+                se += __expf(vals[j] - cm);
+            }
+        }
+        m = cm;
+    }
+    // the wave's, then the four waves' in wave order
+    const VI    wb = wave_best(best);
+    const float wm = wave_max(m);
+    const float ws = wave_sum(se * __expf(m - wm));  // (a thread without an element adds 0 * exp(.) = 0)
+    if (lane == 0) {
+        redv[wid] = wb.v;
+        redi[wid] = wb.i;
+        redm[wid] = wm;
+        reds[wid] = ws;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        VI    b{redv[0], redi[0]};
+        float bm = redm[0];
+        for (int w = 1; w < 4; w++) {
+            if (better(redv[w], redi[w], b.v, b.i)) {
+                b.v = redv[w];
+                b.i = redi[w];
+            }
+            bm = fmaxf(bm, redm[w]);
+        }
+        float tot = 0.f;
+        for (int w = 0; w < 4; w++) {
+            tot += reds[w] * __expf(redm[w] - bm);
+        }
+        // write-through stores (agent scope: the closing workgroup may sit on another XCD)
+        va_gu32* o = (va_gu32*)(part + ((size_t)r * VS_SLICES + blk) * 4);
+        __hip_atomic_store(o + 0, __float_as_uint(n > 0 ? b.v : -INFINITY), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(o + 1, (unsigned)(n > 0 ? b.i : 0x7fffffff), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(o + 2, __float_as_uint(n > 0 ? bm : -FLT_MAX), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(o + 3, __float_as_uint(n > 0 ? tot : 0.f), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_verify_close(const VerifyCloseParams p, const float* part)
+{
+    constexpr int RM = VERIFY_MAX_ROWS;
+    __shared__ unsigned s_part[RM * VS_SLICES * 4];
+    __shared__ int   s_a[RM], s_draft[RM], s_stop[RM];
+    __shared__ float s_lp[RM];
+    __shared__ int   s_m;
+    const int  R = p.R, st = p.step;
+    const bool lp_on = p.cum_log_probs || p.output_log_probs;
+    {  // every row's partials, requested together
+        const va_gu32* q = (const va_gu32*)part;
+        for (int i = threadIdx.x; i < R * VS_SLICES * 4; i += 256) {
+            s_part[i] = __hip_atomic_load(q + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if ((int)threadIdx.x < RM) {
+            s_draft[threadIdx.x] = (int)threadIdx.x < R - 1 ? p.draft[threadIdx.x] : -1;
+            s_stop[threadIdx.x]  = 0;
+        }
+    }
+    __syncthreads();
+    // ---- a[r] and its log-probability: row r's partials in slice order, by one thread ----
+    if ((int)threadIdx.x < R) {
+        const unsigned* q = s_part + threadIdx.x * VS_SLICES * 4;
+        VI    b{__uint_as_float(q[0]), (int)q[1]};
+        float M = __uint_as_float(q[2]);
+        for (int sl = 1; sl < VS_SLICES; sl++) {
+            const float v = __uint_as_float(q[sl * 4]);
+            const int   i = (int)q[sl * 4 + 1];
+            if (better(v, i, b.v, b.i)) {
+                b.v = v;
+                b.i = i;
+            }
+            M = fmaxf(M, __uint_as_float(q[sl * 4 + 2]));
+        }
+        float tot = 0.f;
+        for (int sl = 0; sl < VS_SLICES; sl++) {
+            tot += __uint_as_float(q[sl * 4 + 3]) * __expf(__uint_as_float(q[sl * 4 + 2]) - M);
+        }
+        s_a[threadIdx.x]  = (b.i == 0x7fffffff || b.i < 0) ? 0 : b.i;
+        s_lp[threadIdx.x] = lp_on ? logf(__expf(b.v - M) / (tot + 1e-6f)) : 0.f;
+    }
+    __syncthreads();
+    // ---- stage 1: m, the longest prefix of drafts the model agrees with ----
+    if (threadIdx.x == 0) {
+        int m = 0;
+        while (m < R - 1 && s_draft[m] == s_a[m]) {
+            m++;
+        }
+        s_m = m;
+    }
+    __syncthreads();
+    const int m = s_m;
+    // ---- the stop words at every candidate position st + i, i <= m (stop_criteria_kernels.cu:24-83): a (position, word) pair per
+    // thread; tokens before st are the history, tokens from st on the ones this pass is about to write ----
+    if (p.stop_words) {
+        const int* words = p.stop_words;
+        const int* offs  = words + p.stop_len;
+        for (int w = threadIdx.x; w < (m + 1) * p.stop_len; w += 256) {
+            const int i = w / p.stop_len, id = w % p.stop_len;
+            if (offs[id] < 0) {
+                continue;
+            }
+            const int item_end = offs[id], item_start = id > 0 ? offs[id - 1] : 0;
+            const int item_size = item_end - item_start;
+            const int step      = st + i;
+            bool      stop      = false;
+            if (step + 1 >= item_size) {
+                stop = true;
+                for (int t = item_size - 1; t >= 0; t--) {
+                    const int pos  = step - (item_size - 1) + t;
+                    const int prev = pos >= st ? s_a[pos - st] : p.output_ids[pos];
+                    if (prev != words[item_start + t]) {
+                        stop = false;
+                        break;
+                    }
+                }
+            }
+            if (stop) {
+                atomicOr(&s_stop[i], 1);
+            }
+        }
+    }
+    __syncthreads();
+    // ---- stages 2 - 4: the tokens in order, cut after the first one that finishes the row; the state words and the flags ----
+    if (threadIdx.x == 0) {
+        float     cum = p.cum_log_probs ? p.cum_log_probs[0] : 0.f;
+        const int sl0 = p.seq_len[0];
+        int       e = 0, fin = 0;
+        for (int i = 0; i <= m && !fin; i++) {
+            const int id = s_a[i], step = st + i;
+            p.output_ids[step] = id;
+            if (lp_on) {
+                cum += s_lp[i];  // (sequential fp32 adds in token order: the sum of the stored values is cum_log_probs, bit for bit)
+                if (p.output_log_probs) {
+                    p.output_log_probs[step - p.max_input_len] = s_lp[i];
+                }
+            }
+            fin = id == p.end_id;
+            fin |= s_stop[i];
+            fin |= step >= p.total_len;  // length_criterion (stop_criteria_kernels.cu:106-158), limit = total_len
+            e++;
+            if (p.h_flags) {
+                p.h_flags[FLAG_SPEC_TOKENS + i]  = id;
+                p.h_flags[FLAG_SPEC_SEQ_LEN + i] = sl0 + e;
+            }
+            if (p.tokens) {
+                p.tokens[i] = id;
+            }
+        }
+        const int acc = m < e ? m : e;  // drafts that became output tokens
+        if (p.cum_log_probs && lp_on) {
+            p.cum_log_probs[0] = cum;
+        }
+        p.seq_len[0]  = sl0 + e;
+        p.finished[0] = (uint8_t)fin;
+        if (p.emitted) {
+            *p.emitted = e;
+        }
+        if (p.accepted) {
+            *p.accepted = acc;
+        }
+        if (p.state) {
+            p.state->all_finished = fin;
+            p.state->steps_done += e;
+            p.state->step = st + e;
+        }
+        if (p.h_flags) {  // (the host reads them behind a synchronisation of the stream)
+            p.h_flags[FLAG_LAST_STEP]     = st + e - 1;
+            p.h_flags[FLAG_SPEC_EMITTED]  = e;
+            p.h_flags[FLAG_SPEC_ACCEPTED] = acc;
+            __threadfence_system();
+            p.h_flags[FLAG_ALL_FINISHED] = fin;
+        }
+    }
+}
+
+size_t verify_close_workspace_bytes()
+{
+    return (size_t)VERIFY_MAX_ROWS * VS_SLICES * 4 * sizeof(float);
+}
+
+void launch_verify_close(const VerifyCloseParams& p, hipStream_t s)
+{
+    FTCF_CHECK_ARG(p.R >= 1 && p.R <= VERIFY_MAX_ROWS && p.V >= 1, "verify accept: 1 <= rows <= 16, vocabulary >= 1");
+    FTCF_CHECK_ARG(p.logits && p.output_ids && p.finished && p.seq_len && p.ws && (p.R == 1 || p.draft), "verify accept: NULL tensor");
+    FTCF_CHECK_ARG(p.step >= 1 && p.max_input_len >= 0 && p.step >= p.max_input_len && p.step + p.R <= p.total_len,
+                   "verify accept: the rows' positions step .. step + R - 1 must lie in [max(1, max_input_len), total_len)");
+    FTCF_CHECK_ARG(!p.stop_words || p.stop_len >= 1, "verify accept: stop_words needs stop_len >= 1");
+    hipLaunchKernelGGL(k_verify_slices, dim3(VS_SLICES, p.R), dim3(256), 0, s, p.logits, p.V, p.ws);
+    hipLaunchKernelGGL(k_verify_close, dim3(1), dim3(256), 0, s, p, (const float*)p.ws);
     FTCF_HIP_CHECK(hipGetLastError());
 }
 

@@ -204,7 +204,8 @@ class GptNeoXOp:
         drafted per step -- by prompt lookup over the last speculative_ngram tokens (default 3), or taken from draft_ids (int32
         CUDA [output_len]: the guess for each generated position, negative = no guess) -- and verified in one decoder pass.
         The tokens are those of the same request without it; a request the feature does not cover runs as before and
-        stats()["spec_active"] is 0."""
+        stats()["spec_active"] is 0.  set_speculative_scope(1) widens what it covers to requests with stop words,
+        log-probabilities, a callback or optional_last_tokens."""
         spec_k, spec_n = check_speculative_args(speculative_tokens, speculative_ngram, draft_ids, output_len)
         _check_input(input_ids, "input_ids", torch.int32)
         if input_ids.dim() != 2:
@@ -310,6 +311,12 @@ class GptNeoXOp:
 
     def set_profiling(self, enabled):
         capi.check(capi.lib().ftcf_gptneox_set_profiling(self._h, int(bool(enabled))))
+
+    def set_speculative_scope(self, scope):
+        """Which requests with speculative_tokens may speculate (ftcf_gptneox_set_speculative_scope), for requests begun after the
+        call: 0 (the default) the bare greedy request; 1 also a greedy request with stop words, return_cum_log_probs,
+        return_output_log_probs, a callback or optional_last_tokens -- what harness.generate() sends.  Anything else raises."""
+        capi.check(capi.lib().ftcf_gptneox_set_speculative_scope(self._h, int(scope)))
 
 
 def symmetric_quantize_last_axis_of_batched_matrix_int8(weight):

@@ -380,16 +380,23 @@ class GptNeoX(torch.nn.Module):
     def forward(self, start_ids, start_lengths, output_len, beam_width=1, top_k=None, top_p=None,
                 beam_search_diversity_rate=None, temperature=None, len_penalty=None, repetition_penalty=None,
                 random_seed=None, stop_words_list=None, optional_last_tokens=None, return_output_length=False,
-                return_cum_log_probs=0, callback=None):
+                return_cum_log_probs=0, callback=None, speculative_tokens=None, speculative_ngram=None):
+        """speculative_tokens / speculative_ngram (None: the call is the reference's): speculative greedy decoding of
+        GptNeoXOp.forward, with the engine's speculative scope set to 1 -- the requests generate() sends (cum_log_probs, a
+        callback, stop words, last tokens) are then covered.  An op without the switch gets the reference's call."""
         if not self.build_model:
             self.cuda()
         assert start_ids.size(1) > 0, \
             "input len must be larger than zero. For an unconditional case, use start_id as the first token."
         to_dev = lambda t: None if t is None else t.cuda(self.device)
+        speculative = {}
+        if (speculative_tokens is not None or speculative_ngram is not None) and hasattr(self.model, "set_speculative_scope"):
+            self.model.set_speculative_scope(1)
+            speculative = dict(speculative_tokens=speculative_tokens, speculative_ngram=speculative_ngram)
         outputs = self.model.forward(to_dev(start_ids), to_dev(start_lengths), output_len, beam_width, top_k, top_p,
                                      beam_search_diversity_rate, temperature, len_penalty, repetition_penalty,
                                      random_seed, to_dev(stop_words_list), to_dev(optional_last_tokens),
-                                     return_cum_log_probs, callback)
+                                     return_cum_log_probs, callback, **speculative)
         if not return_output_length:
             return outputs[0]
         return tuple(outputs) if return_cum_log_probs > 0 else (outputs[0], outputs[1])
@@ -458,9 +465,11 @@ def _trim_and_decode(ids, prompt_len, end_id, tokenizer):
 
 def generate(gpt, tokenizer, texts, output_len, beam_width, top_k=None, top_p=None, beam_search_diversity_rate=None,
              temperature=None, len_penalty=None, repetition_penalty=None, random_seed=None, input_ids_list=None,
-             callback=None, stop_words_list=None, last_token_list=None, trie=None):
+             callback=None, stop_words_list=None, last_token_list=None, trie=None, speculative_tokens=None,
+             speculative_ngram=None):
     """Prompts (texts, or token id lists) -> ([B][beam] texts, [B][beam] generated lengths, cum_log_probs, seconds).
-    Counterpart of codefuse_example.py:666-770; the request / response shapes are what CodeFuseHandler.predict serves."""
+    Counterpart of codefuse_example.py:666-770; the request / response shapes are what CodeFuseHandler.predict serves.
+    speculative_tokens / speculative_ngram: passed on to GptNeoX.forward when given."""
     assert texts is not None or input_ids_list is not None
     prompts = [list(tokenizer.encode(t)) for t in texts] if texts is not None else [list(r) for r in input_ids_list]
     start_ids, prompt_lens = _pad_rows(prompts, gpt.end_id)
@@ -479,11 +488,14 @@ def generate(gpt, tokenizer, texts, output_len, beam_width, top_k=None, top_p=No
             trie.printAutoSuggestions(prefix, hits)
             candidates.append([tid for _, tid in hits] or [gpt.end_id])
         last_tokens, _ = _pad_rows(candidates, -1)
+    speculative = {}
+    if speculative_tokens is not None or speculative_ngram is not None:
+        speculative = dict(speculative_tokens=speculative_tokens, speculative_ngram=speculative_ngram)
     t0 = time.time()
     with torch.no_grad():
         out = gpt(start_ids=start_ids, start_lengths=torch.IntTensor(prompt_lens), output_len=output_len,
                   beam_width=beam_width, stop_words_list=stop_words, optional_last_tokens=last_tokens,
-                  return_output_length=True, return_cum_log_probs=1, callback=callback, **sampling)
+                  return_output_length=True, return_cum_log_probs=1, callback=callback, **sampling, **speculative)
     latency = time.time() - t0
     token_rows, cum_log_probs = out[0].detach().cpu().tolist(), out[2].detach().cpu().tolist()
     outputs, output_lengths = [], []
@@ -520,6 +532,9 @@ def get_data_package(request_dict, default_random_seed):
     pkg["random_seed"] = gather("random_seed", default_random_seed)
     pkg["stop_words_list"] = gather("stop_words")
     pkg["last_token_list"] = gather("last_token")
+    for key in ("speculative_tokens", "speculative_ngram"):  # (per request, optional: absent keys leave the package as it was)
+        if key in request_dict:
+            pkg[key] = request_dict[key]
     return pkg
 
 

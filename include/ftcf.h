@@ -237,6 +237,48 @@ size_t ftcf_verify_attention_workspace(int R, int nh, int dh, int s_max);
  * draft is t[s + g, min(s + g + K, n)).  No match: zero drafts.  draft [K] and n_draft [1] are device int32.  1 <= K <= 15,
  * 1 <= N <= 8. */
 int ftcf_ngram_draft(const int* tokens, int n, int K, int N, int* draft, int* n_draft, void* stream);
+/* The decode tail of a verify pass for a request with stop words, log-probabilities or a streaming callback (the engine runs it
+ * for every pass of a request that began under ftcf_gptneox_set_speculative_scope(h, 1)): two launches and nothing else.
+ * logits [R, V] fp32 (device, not modified) are the pass's rows: row i is the model's distribution behind the token of position
+ * step + i - 1, i.e. behind draft[i - 1] for i >= 1.  a[i] = the arg max of row i (value descending, index ascending on ties);
+ * m = the longest prefix with draft[i] == a[i] (draft [R - 1] device int32; NULL with R = 1).  For i = 0 .. m in order:
+ *   - a[i] is written to output_ids[step + i] (output_ids [total_len] device int32: ONE sequence, positions [0, step) are its
+ *     history) and to tokens[i];
+ *   - with cum_log_probs and / or output_log_probs given (device fp32 [1] / [total_len - max_input_len], either may be NULL):
+ *     lp = logf(exp(v - row max) / (sum of exp(. - row max) + 1e-6f)) is added to cum_log_probs[0] and stored at
+ *     output_log_probs[step + i - max_input_len] -- the value the plain greedy step commits.  The adds are sequential fp32 adds
+ *     in i order: a sequential fp32 sum of the stored values reproduces cum_log_probs bit for bit;
+ *   - the row finishes when a[i] == end_id, when a stop word ends at position step + i (stop_words [2, stop_len] device int32 or
+ *     NULL: the ids back to back, then cumulative end offsets, -1 padded, as stop_words_list of ftcf_forward_args for one row;
+ *     a word may straddle the history and the tokens just written; drafts behind position m are never looked at), or when
+ *     step + i >= total_len.
+ * Nothing is written behind the first token that finishes the row.  *emitted = the tokens written (1 .. m + 1), *accepted = the
+ * drafts among them (min(m, emitted)); seq_len[0] += emitted; finished[0] = whether the last token finished the row (device int32
+ * [1] / int32 [1] / int32 [1] / uint8 [1]); tokens is device int32 [16].  Every other cell of every buffer keeps its bits.
+ * 1 <= R <= 16, max(1, max_input_len) <= step, step + R <= total_len, 0 <= end_id < V; any V.  Deterministic: two calls give identical
+ * bits.  workspace: FTCF_VERIFY_ACCEPT_WORKSPACE_BYTES device bytes.  Enqueues on `stream` and does not synchronise.
+ * struct_size != sizeof(ftcf_verify_accept_args), R outside 1..16, a NULL tensor other than the optional ones, positions outside
+ * the sequence: FTCF_ERR_INVALID_ARG. */
+#define FTCF_VERIFY_ACCEPT_WORKSPACE_BYTES 8192
+typedef struct ftcf_verify_accept_args {
+    int          struct_size;
+    int          R, V, step, end_id, max_input_len, total_len;
+    const float* logits;
+    const int*   draft;
+    int*         output_ids;
+    const int*   stop_words;
+    int          stop_len;
+    uint8_t*     finished;
+    int*         seq_len;
+    float*       cum_log_probs;
+    float*       output_log_probs;
+    void*        workspace;
+    size_t       workspace_bytes;
+    int*         emitted;
+    int*         accepted;
+    int*         tokens;
+} ftcf_verify_accept_args;
+int ftcf_verify_accept(const ftcf_verify_accept_args* args, void* stream);
 /* GptContextAttentionLayer<T>::forward minus the two projections (layers/attention_layers/
  * GptContextAttentionLayer.cc:142-345): bias + NeoX rotary + cache fill + causal masked softmax(QK^T)V.
  * qkv [B*S, 3*Hl] fp16 (row = b*S+s), ctx [B*S, Hl] fp16. */
@@ -565,9 +607,15 @@ typedef struct {
      * exactly the tokens plain greedy decoding produces one at a time.  A step with no draft is the plain step; the first step
      * of a request never drafts.  Eligible:
      * batch 1 with input_lengths[0] == max_input_len, beam_width 1, greedy (top_k <= 1 and top_p 0), repetition_penalty 1, no
-     * min_length / optional_last_tokens / stop words / callback / return_cum_log_probs / output_log_probs / debug_logits, fp16
-     * engine (int8_mode 0 / 1), parallel residual, tensor_para_size 1, size_per_head 64 / 128, hidden and inter sizes multiples
-     * of 64, at most ~32000 positions.  An ineligible request is not an error: it runs as without the fields and ftcf_forward_stats.spec_active says so.
+     * min_length / top_logprobs / debug_logits, fp16 engine (int8_mode 0 / 1), parallel residual, tensor_para_size 1,
+     * size_per_head 64 / 128, hidden and inter sizes multiples of 64, at most ~32000 positions -- and, at the engine's default
+     * speculative scope 0, no optional_last_tokens / stop words / callback / return_cum_log_probs / output_log_probs.  Under
+     * ftcf_gptneox_set_speculative_scope(h, 1) those five no longer exclude a request (a temperature other than 1 together with
+     * return_cum_log_probs or output_log_probs still does: it changes the soft-max, not the arg max): tokens and sequence
+     * lengths are those of the request without the fields, the callback is invoked once per emitted token with the arguments of
+     * the unspeculated request, in its order, cum_log_probs is the sequential fp32 sum of output_log_probs, and both agree with
+     * the unspeculated request's as two GEMM forms do (a pass runs the burst GEMMs).
+     * An ineligible request is not an error: it runs as without the fields and ftcf_forward_stats.spec_active says so.
      * speculative_tokens outside 0..15 or speculative_ngram outside 0..8: FTCF_ERR_INVALID_ARG. */
     int        speculative_tokens;
     int        speculative_ngram;
@@ -627,6 +675,12 @@ int ftcf_gptneox_beam_log_probs(ftcf_gptneox_t h, float* log_probs, size_t capac
 int ftcf_gptneox_get_stats(ftcf_gptneox_t h, ftcf_forward_stats* stats);
 /* enable HIP-event timing around every weight-streaming launch of the decode loop (bench.py roofline leg) */
 int ftcf_gptneox_set_profiling(ftcf_gptneox_t h, int enabled);
+/* Which requests with speculative_tokens > 0 may speculate (a switch of the engine, not a request field: ftcf_forward_args keeps
+ * its layout).  0, the default: the bare greedy request, as before the switch existed -- the same launches, bits and spec_active.
+ * 1: also a request with stop words, return_cum_log_probs, output_log_probs, a streaming callback or optional_last_tokens (see
+ * speculative_tokens of ftcf_forward_args); every verify pass of such an engine closes with the two launches of
+ * ftcf_verify_accept.  Holds for requests begun after the call.  Any other value: FTCF_ERR_INVALID_ARG. */
+int ftcf_gptneox_set_speculative_scope(ftcf_gptneox_t h, int scope);
 int ftcf_gptneox_destroy(ftcf_gptneox_t h);
 
 

@@ -8,6 +8,12 @@ rate, over its passes), tokens per pass, tokens/s, next to the plain run's; brea
 plain step time.  Plain and speculative runs alternate inside the one process, after a warm-up of each shape.
 
     python tools/bench_speculative.py [--prompt-len 1024] [--out-len 512] [--rounds 3] [--ks 2,4,8] [--every 0,4,2,1]
+
+--scope adds the leg of the wider speculative scope (GptNeoXOp.set_speculative_scope(1)): the same workload as the harness sends
+it -- return_cum_log_probs, a stop-word list that never matches and a no-op callback -- whose passes close with k_verify_slices +
+k_verify_close instead of k_verify_argmax + k_verify_accept.  Per round the plain run, the scope 0 run and the scope 1 run follow
+each other in the one process; a row reports both legs' milliseconds per verify pass (best, and the spread over the rounds) and
+tokens/s (profiles/speculative_scope_bench.txt).
 """
 import argparse
 import json
@@ -30,6 +36,7 @@ def main():
     p.add_argument("--rounds", type=int, default=3)
     p.add_argument("--ks", default="2,4,8")
     p.add_argument("--every", default="0,4,2,1", help="corrupt every p-th draft (0: none, 1: all)")
+    p.add_argument("--scope", action="store_true", help="add the scope 1 leg (cum_log_probs + stop words + callback) next to scope 0")
     a = p.parse_args()
     capi.require_gpu()
     import bench
@@ -61,6 +68,8 @@ def main():
 
     ks = [int(x) for x in a.ks.split(",") if x]
     every = [int(x) for x in a.every.split(",") if x]
+    if a.scope:
+        return scope_legs(a, op, run, drafts, gen, n_gen, ks, every, dev)
     for K in ks:  # warm-up of each shape (arena, graph capture of the plain step, every kernel's code object)
         run(32)
         run(32, speculative_tokens=K, draft_ids=drafts(0)[:32].contiguous())
@@ -86,6 +95,49 @@ def main():
                     best = r
             rows.append(best)
             print(json.dumps(best), flush=True)
+    return rows
+
+
+def scope_legs(a, op, run, drafts, gen, n_gen, ks, every, dev):
+    """scope 0 (the bare request) next to scope 1 (the request the harness sends), alternating"""
+    never = torch.tensor([[[2, 2], [2, -1]]], dtype=torch.int32, device=dev)  # one word, the end token twice: never completes
+    wide = dict(return_cum_log_probs=1, stop_words_list=never, callback=lambda d: None)
+
+    def leg(scope, plain_ms, **kw):
+        op.set_speculative_scope(scope)
+        toks, n_s, ss = run(**kw)
+        n_plain = ss["decode_steps"] - ss["spec_accepted"] - ss["spec_steps"]
+        pass_ms = (ss["decode_ms"] - n_plain * plain_ms) / max(1, ss["spec_steps"])
+        return dict(spec_active=ss["spec_active"], passes=ss["spec_steps"], accepted=ss["spec_accepted"], ms_per_pass=pass_ms,
+                    tok_s=ss["decode_steps"] / ss["decode_ms"] * 1e3,
+                    tokens_differ=sum(1 for x, y in zip(toks[:n_s], gen) if x != y) + abs(n_s - n_gen))
+
+    for K in ks:
+        op.set_speculative_scope(1)
+        run(32, speculative_tokens=K, draft_ids=drafts(0)[:32].contiguous(), **wide)
+    rows = []
+    for K in ks:
+        for ev in every:
+            d = drafts(ev)
+            legs = {0: [], 1: []}
+            plain = []
+            for _ in range(a.rounds):
+                op.set_speculative_scope(0)
+                _, _, sp = run()
+                plain_ms = sp["decode_ms"] / sp["decode_steps"]
+                plain.append(plain_ms)
+                legs[0].append(leg(0, plain_ms, speculative_tokens=K, draft_ids=d))
+                legs[1].append(leg(1, plain_ms, speculative_tokens=K, draft_ids=d, **wide))
+            row = dict(K=K, corrupt_every=ev, plain_ms_per_token=[round(min(plain), 4), round(max(plain), 4)])
+            for sc in (0, 1):
+                ms = [r["ms_per_pass"] for r in legs[sc]]
+                row[f"scope{sc}"] = dict(spec_active=legs[sc][0]["spec_active"], passes=legs[sc][0]["passes"], accepted=legs[sc][0]["accepted"],
+                                         ms_per_pass_min=round(min(ms), 4), ms_per_pass_max=round(max(ms), 4),
+                                         tok_s_best=round(max(r["tok_s"] for r in legs[sc]), 1),
+                                         tokens_differ=max(r["tokens_differ"] for r in legs[sc]))
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    op.set_speculative_scope(0)
     return rows
 
 
