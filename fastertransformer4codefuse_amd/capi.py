@@ -115,6 +115,15 @@ class VerifyAcceptArgs(C.Structure):  # ftcf_verify_accept_args
 VERIFY_ACCEPT_WORKSPACE_BYTES = 8192  # FTCF_VERIFY_ACCEPT_WORKSPACE_BYTES
 
 
+class VerifySampleArgs(C.Structure):  # ftcf_verify_sample_args: ftcf_verify_accept_args, then what the top-k layer draws with
+    _fields_ = list(VerifyAcceptArgs._fields_) + [
+        ("top_k", C.c_int), ("top_p_topk", C.c_float), ("temperature", C.c_float), ("random_seed", C.c_ulonglong),
+        ("draw_counter", C.c_void_p)]
+
+
+VERIFY_SAMPLE_WORKSPACE_BYTES = 266368  # FTCF_VERIFY_SAMPLE_WORKSPACE_BYTES
+
+
 class LogitOptions(C.Structure):  # ftcf_logit_options
     _fields_ = [("struct_size", C.c_int), ("presence_penalty", C.c_float), ("frequency_penalty", C.c_float),
                 ("min_new_tokens", C.c_int), ("bias_ids", C.POINTER(C.c_int)), ("bias_values", C.POINTER(C.c_float)),
@@ -164,7 +173,7 @@ STRUCTS = {
 
 # ... and of the structs the header declares with a tag (`typedef struct NAME { ... } NAME;`): tests/test_speculative_scope_host.py
 # compares their layouts the same way
-TAGGED_STRUCTS = {"ftcf_verify_accept_args": VerifyAcceptArgs}
+TAGGED_STRUCTS = {"ftcf_verify_accept_args": VerifyAcceptArgs, "ftcf_verify_sample_args": VerifySampleArgs}
 
 # The prototype of every entry point: name -> (restype, argtypes), written out by hand in the header's order and held to the
 # header by tests/test_capi_abi.py.  int / ftcf_dtype / ftcf_act -> I, float -> F, size_t -> Z, long -> L, unsigned long long -> U;
@@ -212,6 +221,7 @@ PROTOTYPES = {
     "ftcf_verify_attention_workspace": (Z, [I, I, I, I]),
     "ftcf_ngram_draft": (I, [P, I, I, I, P, P, P]),
     "ftcf_verify_accept": (I, [P, P]),
+    "ftcf_verify_sample": (I, [P, P]),
     "ftcf_paged_attention": (I, [P] * 7 + [I] * 7 + [P, P]),
     "ftcf_scatter_kv_to_pages": (I, [P] * 5 + [I] * 6 + [Z, Z, P]),
     "ftcf_gather_pages_to_kv": (I, [P] * 5 + [I] * 6 + [Z, Z, P]),
@@ -237,6 +247,7 @@ PROTOTYPES = {
     "ftcf_gptneox_get_stats": (I, [P, P]),
     "ftcf_gptneox_set_profiling": (I, [P, I]),
     "ftcf_gptneox_set_speculative_scope": (I, [P, I]),
+    "ftcf_gptneox_set_speculative_sampling": (I, [P, I]),
     "ftcf_gptneox_destroy": (I, [P]),
     "ftcf_batcher_create": (I, [P, I, I, I, I, P]),
     "ftcf_batcher_create_ex": (I, [P, I, I, I, I, I, P]),

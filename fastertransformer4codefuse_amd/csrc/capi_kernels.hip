@@ -530,6 +530,57 @@ extern "C" int ftcf_verify_accept(const ftcf_verify_accept_args* a, void* stream
         launch_verify_close(p, (hipStream_t)stream);
     });
 }
+static_assert(FTCF_VERIFY_SAMPLE_WORKSPACE_BYTES
+                  == (2 * VERIFY_MAX_ROWS * VERIFY_ACCEPT_SLICES * VERIFY_SAMPLE_MAX_K + VERIFY_MAX_ROWS * VERIFY_ACCEPT_SLICES * 2
+                      + VERIFY_MAX_ROWS * 2)
+                         * sizeof(float),
+              "FTCF_VERIFY_SAMPLE_WORKSPACE_BYTES is verify_sample_workspace_bytes()");
+extern "C" int ftcf_verify_sample(const ftcf_verify_sample_args* a, void* stream)
+{
+    return guarded([&] {
+        require_device();
+        FTCF_CHECK_ARG(a != nullptr, "NULL argument");
+        FTCF_CHECK_ARG(a->struct_size == (int)sizeof(ftcf_verify_sample_args), "verify sample: struct_size is not sizeof(ftcf_verify_sample_args)");
+        FTCF_CHECK_ARG(a->R >= 1 && a->R <= VERIFY_MAX_ROWS && a->V >= 1, "verify sample: 1 <= R <= 16, V >= 1");
+        FTCF_CHECK_ARG(a->top_k >= 1 && a->top_k <= VERIFY_SAMPLE_MAX_K && a->V <= VERIFY_SAMPLE_MAX_V,
+                       "verify sample: 1 <= top_k <= 64, V <= 131072");
+        FTCF_CHECK_ARG(a->logits && a->output_ids && a->finished && a->seq_len && a->draw_counter && (a->R == 1 || a->draft),
+                       "verify sample: NULL tensor");
+        FTCF_CHECK_ARG(a->emitted && a->accepted && a->tokens, "verify sample: NULL output");
+        FTCF_CHECK_ARG(a->workspace && a->workspace_bytes >= verify_sample_workspace_bytes(), "verify sample: workspace too small");
+        FTCF_CHECK_ARG(a->end_id >= 0 && a->end_id < a->V, "verify sample: end_id outside the vocabulary");
+        FTCF_CHECK_ARG(!a->stop_words || (a->stop_len >= 1 && a->stop_len <= 4096), "verify sample: stop_len must be in [1, 4096]");
+        FTCF_CHECK_ARG(a->top_p_topk > 0.f && a->top_p_topk <= 1.f && a->temperature >= 0.f, "verify sample: top_p_topk in (0, 1], temperature >= 0");
+        VerifySampleParams q{};
+        VerifyCloseParams& p = q.c;
+        p.logits           = a->logits;
+        p.R                = a->R;
+        p.V                = a->V;
+        p.step             = a->step;
+        p.end_id           = a->end_id;
+        p.max_input_len    = a->max_input_len;
+        p.total_len        = a->total_len;
+        p.draft            = a->draft;
+        p.output_ids       = a->output_ids;
+        p.stop_words       = a->stop_words;
+        p.stop_len         = a->stop_len;
+        p.finished         = a->finished;
+        p.seq_len          = a->seq_len;
+        p.cum_log_probs    = a->cum_log_probs;
+        p.output_log_probs = a->output_log_probs;
+        p.emitted          = a->emitted;
+        p.accepted         = a->accepted;
+        p.tokens           = a->tokens;
+        q.top_k             = a->top_k;
+        q.top_p_topk        = a->top_p_topk;
+        q.apply_temperature = (a->temperature != 0.f && a->temperature != 1.f) ? 1 : 0;
+        q.temperature       = a->temperature;
+        q.random_seed       = (uint64_t)a->random_seed;
+        q.draw_counter      = reinterpret_cast<uint64_t*>(a->draw_counter);
+        q.ws                = (float*)a->workspace;
+        launch_verify_sample(q, (hipStream_t)stream);
+    });
+}
 extern "C" int ftcf_context_attention(const void* qkv, const void* qkv_bias, const int* input_lengths, void* k_cache,
                                       void* v_cache, int B, int S, int nh, int dh, int rot, int s_max, void* ctx,
                                       void* stream)

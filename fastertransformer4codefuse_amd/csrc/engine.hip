@@ -190,19 +190,24 @@ bool ftcf_gptneox::speculation_wanted(const ftcf_forward_args& a, int total)
     // unspeculated; at scope 1 the pass's tail (k_verify_close) serves them.  optional_last_tokens masks the first generated step
     // only, which never drafts.  A temperature leaves the arg max alone but not the soft-max: with a log-probability output it
     // still excludes the request.
+    // A top-k sampled request (ftcf_gptneox_set_speculative_sampling): top_k in 2..64, a top_p next to it being the p of the top-k
+    // layer, over a vocabulary the sampled tail holds in registers.  Its tail applies the temperature itself, so a temperature
+    // excludes nothing there.
+    const bool sampled = spec_sampling == 1 && a.n_top_k > 0 && a.top_k && a.top_k[0] >= 2 && a.top_k[0] <= VERIFY_SAMPLE_MAX_K
+                         && V <= VERIFY_SAMPLE_MAX_V;
     const bool log_probs = a.return_cum_log_probs || a.output_log_probs;
     bool       scoped    = !a.callback && !log_probs && !a.stop_words_list && !a.optional_last_tokens;
     if (spec_scope == 1) {
         scoped = true;
-        for (int i = 0; log_probs && i < a.n_temperature; i++) {
+        for (int i = 0; log_probs && !sampled && i < a.n_temperature; i++) {
             scoped &= a.temperature && a.temperature[i] == 1.f;
         }
     }
     const bool eligible =
         a.speculative_tokens > 0 && a.batch_size == 1 && a.beam_width == 1 && !fp32 && cfg.tensor_para_size == 1 && cfg.use_gptj_residual
         && prefill_begin == 0 && verify_attention_supported(nhl, dh, total) && H % 64 == 0 && hl % 64 == 0 && il % 64 == 0 && scoped
-        && a.top_logprobs == 0 && !a.debug_logits && a.n_min_length == 0 && (a.n_top_k == 0 || (a.top_k && a.top_k[0] <= 1))
-        && (a.n_top_p == 0 || (a.top_p && a.top_p[0] == 0.f))
+        && a.top_logprobs == 0 && !a.debug_logits && a.n_min_length == 0 && (a.n_top_k == 0 || (a.top_k && a.top_k[0] <= 1) || sampled)
+        && (a.n_top_p == 0 || (a.top_p && (a.top_p[0] == 0.f || sampled)))
         && (a.n_repetition_penalty == 0 || (a.repetition_penalty && a.repetition_penalty[0] == 1.f)) && !logits_hook;
     if (!eligible) {
         return false;
@@ -486,6 +491,14 @@ void ftcf_gptneox::begin(const ftcf_forward_args& a)
 
     ses.open(a, session_sampling_params(a, route, in_len), session_beam_params(a, route, in_len), e0, e1, spec_plan);
     ses.spec_scope = spec_scope;
+    if (spec_plan && route.k_eff[0] >= 2) {  // (speculation_wanted admitted it: the switch is on, 2 <= top_k <= 64)
+        ses.spec_sampled    = true;
+        ses.spec_top_k      = route.k_eff[0];
+        ses.spec_p_topk     = route.p_topk[0];
+        ses.spec_apply_temp = route.apply_temperature;
+        ses.spec_temp       = a.n_temperature > 0 ? a.temperature[0] : 1.f;
+        ses.spec_seed       = a.n_random_seed > 0 ? a.random_seed[0] : 0;
+    }
     stats.decode_ms = 0.f;
 }
 
@@ -756,8 +769,9 @@ void ftcf_gptneox::verify_pass(int st, int drafts)
         [](f16*, size_t, hipStream_t, bool) {}, [&](double bytes, auto&& launch, hipStream_t s) { timed(KIND_SMALLM, bytes, launch, s); });
     launch_layernorm(vx, final_g, final_b, vnrm, R, H, 1e-5f, true, stream);
     timed(KIND_LM_HEAD, 2.0 * V * H, [&] { lm_head_dispatch(vnrm, lm_head, vlogits, R, V, H, V, stream); });
-    if (ses.spec_scope == 1) {  // stop words, log-probabilities and the callback's tokens are the tail's business
-        VerifyCloseParams cp{};
+    if (ses.spec_sampled || ses.spec_scope == 1) {  // stop words, log-probabilities and the callback's tokens are the tail's business
+        VerifySampleParams q{};
+        VerifyCloseParams& cp = q.c;
         cp.logits           = vlogits;
         cp.R                = R;
         cp.V                = V;
@@ -776,7 +790,19 @@ void ftcf_gptneox::verify_pass(int st, int drafts)
         cp.state            = state;
         cp.h_flags          = h_flags;
         cp.ws               = spec_close_ws;
-        launch_verify_close(cp, stream);
+        if (ses.spec_sampled) {  // every row sampled with the draw the plain step of its position would take (either scope)
+            q.top_k             = ses.spec_top_k;
+            q.top_p_topk        = ses.spec_p_topk;
+            q.apply_temperature = ses.spec_apply_temp;
+            q.temperature       = ses.spec_temp;
+            q.random_seed       = ses.spec_seed;
+            q.draw_counter      = draws;
+            q.ws                = spec_sample_ws;
+            launch_verify_sample(q, stream);
+        }
+        else {
+            launch_verify_close(cp, stream);
+        }
     }
     else {
         VerifyAcceptParams vp{};
@@ -1332,6 +1358,15 @@ extern "C" int ftcf_gptneox_set_speculative_scope(ftcf_gptneox_t h, int scope)
         FTCF_CHECK_ARG(h, "NULL argument");
         FTCF_CHECK_ARG(scope == 0 || scope == 1, "speculative scope must be 0 or 1");
         h->spec_scope = scope;
+    });
+}
+
+extern "C" int ftcf_gptneox_set_speculative_sampling(ftcf_gptneox_t h, int enabled)
+{
+    return guarded([&] {
+        FTCF_CHECK_ARG(h, "NULL argument");
+        FTCF_CHECK_ARG(enabled == 0 || enabled == 1, "speculative sampling must be 0 or 1");
+        h->spec_sampling = enabled;
     });
 }
 

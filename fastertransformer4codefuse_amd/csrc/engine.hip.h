@@ -229,6 +229,10 @@ struct ftcf_gptneox {
     // which requests may speculate (ftcf_gptneox_set_speculative_scope): 0 the bare greedy request, 1 also one with stop words,
     // log-probabilities, a streaming callback or optional_last_tokens.  Read by begin(): a request keeps the scope it began under.
     int    spec_scope = 0;
+    // may a top-k sampled request speculate (ftcf_gptneox_set_speculative_sampling)?  Its passes close with the sampled tail
+    // (launch_verify_sample) on the request's own draw counter and seed.  Read by begin(), like the scope.
+    int    spec_sampling = 0;
+    float* spec_sample_ws = nullptr;  // candidates, slice statistics and picks of the sampled tail
 
     // profiling
     bool               profiling = false;
@@ -476,6 +480,7 @@ struct ftcf_gptneox {
         spec_ndraft  = c.take<int>(4);
         spec_argmax  = c.take<int>(2 * R);
         spec_close_ws = c.take<float>(verify_close_workspace_bytes() / 4);
+        spec_sample_ws = c.take<float>(verify_sample_workspace_bytes() / 4);
     }
     // B = rows of the request (batch * beam_width)
     void plan(int B, int S, int total, int K)
@@ -1389,6 +1394,11 @@ struct ftcf_gptneox {
         int               spec_scope = 0;  // the engine's scope when the request began: 1 closes a pass with k_verify_close
         int               spec_K = 0, spec_N = 0, spec_nd = 0;
         int               spec_steps = 0, spec_drafted = 0, spec_accepted = 0;
+        // a top-k sampled request that speculates: its passes close with the sampled tail on what the plain steps sample with
+        bool              spec_sampled = false;
+        int               spec_top_k = 0, spec_apply_temp = 0;
+        float             spec_p_topk = 1.f, spec_temp = 1.f;
+        uint64_t          spec_seed = 0;
         // the state a request starts its token loop from: everything above as declared (no step taken; no graph captured: the
         // previous request's were destroyed by abandon_session() / finish()) but what the request itself says.  [e0, e1] time
         // the prompt phase.

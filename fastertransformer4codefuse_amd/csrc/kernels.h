@@ -610,6 +610,27 @@ struct VerifyCloseParams {
 };
 size_t verify_close_workspace_bytes();
 void   launch_verify_close(const VerifyCloseParams& p, hipStream_t s);
+// The tail of a verify pass of a TOP-K SAMPLED request (the stand-alone ftcf_verify_sample of include/ftcf.h is the contract), in
+// three launches: k_verify_topk_slices (the first half of k_topk_decode per row: VERIFY_ACCEPT_SLICES slices in registers, scaled by
+// the temperature on load, their k best and {max, sum of exponentials}), k_verify_pick (a workgroup per row merges the slices'
+// candidate sets as k_topk_decode's finishing workgroup does and draws with uniform number draw_counter[0] + row: topk_draw_at)
+// and k_verify_sample_close (the stages of k_verify_close on the sampled tokens, then draw_counter[0] += emitted).  Row i is
+// reached only behind i accepted rows, i.e. behind exactly i draws: the tokens are the plain sampled run's for the same seed.
+// c: as for launch_verify_close (c.ws is not used); 1 <= top_k <= 64, V <= 131072.  ws: verify_sample_workspace_bytes().
+struct VerifySampleParams {
+    VerifyCloseParams c;
+    int               top_k;
+    float             top_p_topk;         // the p of the top-k layer (1: all of the k)
+    int               apply_temperature;  // logits are read as logit * (1.0f / (temperature + 1e-6f)), k_decode_prep's expression
+    float             temperature;
+    uint64_t          random_seed;
+    uint64_t*         draw_counter;  // device [1]
+    float*            ws;
+};
+constexpr int VERIFY_SAMPLE_MAX_K = 64;
+constexpr int VERIFY_SAMPLE_MAX_V = VERIFY_ACCEPT_SLICES * 256 * 16;
+size_t verify_sample_workspace_bytes();
+void   launch_verify_sample(const VerifySampleParams& p, hipStream_t s);
 
 // ---- per-request logit processors over logits [B, V] fp32, in place, BEFORE the dynamic decode : kernels_logits.hip ----
 // (include/ftcf.h ftcf_logit_process_args is the contract; the fields are its fields.)  A row is processed when it is enabled

@@ -12,6 +12,7 @@
 //  * k_ngram_draft      : prompt-lookup drafting, one workgroup.
 //  * k_verify_embed / k_verify_argmax / k_verify_accept : the pass's input rows and the greedy acceptance rule.
 //  * k_verify_slices / k_verify_close : the acceptance rule of a request with stop words, log-probabilities or a callback.
+//  * k_verify_topk_slices / k_verify_pick / k_verify_sample_close : the same for a top-k sampled request, token for token.
 //
 // Roofline: HBM (4 * len * dh * nh bytes per layer, once for all rows); the VALU work grows with R (R * dh fused
 // multiply-adds per key and head, twice).
@@ -655,58 +656,24 @@ __global__ __launch_bounds__(256) void k_verify_slices(const float* __restrict__
     }
 }
 
-__global__ __launch_bounds__(256) void k_verify_close(const VerifyCloseParams p, const float* part)
+// Stages 1 - 4 of a pass's close, shared by k_verify_close and k_verify_sample_close: s_a[r] / s_lp[r] are row r's token and its
+// log-probability, s_draft[r] the drafts (-1 behind the last), s_stop[] zero, all in LDS behind a barrier.  Returns the tokens
+// emitted (in thread 0; 0 in every other thread).
+__device__ __forceinline__ int verify_close_stages(const VerifyCloseParams& p, const bool lp_on, const int* s_a, const float* s_lp,
+                                                   const int* s_draft, int* s_stop, int* s_m_slot)
 {
-    constexpr int RM = VERIFY_MAX_ROWS;
-    __shared__ unsigned s_part[RM * VS_SLICES * 4];
-    __shared__ int   s_a[RM], s_draft[RM], s_stop[RM];
-    __shared__ float s_lp[RM];
-    __shared__ int   s_m;
-    const int  R = p.R, st = p.step;
-    const bool lp_on = p.cum_log_probs || p.output_log_probs;
-    {  // every row's partials, requested together
-        const va_gu32* q = (const va_gu32*)part;
-        for (int i = threadIdx.x; i < R * VS_SLICES * 4; i += 256) {
-            s_part[i] = __hip_atomic_load(q + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        if ((int)threadIdx.x < RM) {
-            s_draft[threadIdx.x] = (int)threadIdx.x < R - 1 ? p.draft[threadIdx.x] : -1;
-            s_stop[threadIdx.x]  = 0;
-        }
-    }
-    __syncthreads();
-    // ---- a[r] and its log-probability: row r's partials in slice order, by one thread ----
-    if ((int)threadIdx.x < R) {
-        const unsigned* q = s_part + threadIdx.x * VS_SLICES * 4;
-        VI    b{__uint_as_float(q[0]), (int)q[1]};
-        float M = __uint_as_float(q[2]);
-        for (int sl = 1; sl < VS_SLICES; sl++) {
-            const float v = __uint_as_float(q[sl * 4]);
-            const int   i = (int)q[sl * 4 + 1];
-            if (better(v, i, b.v, b.i)) {
-                b.v = v;
-                b.i = i;
-            }
-            M = fmaxf(M, __uint_as_float(q[sl * 4 + 2]));
-        }
-        float tot = 0.f;
-        for (int sl = 0; sl < VS_SLICES; sl++) {
-            tot += __uint_as_float(q[sl * 4 + 3]) * __expf(__uint_as_float(q[sl * 4 + 2]) - M);
-        }
-        s_a[threadIdx.x]  = (b.i == 0x7fffffff || b.i < 0) ? 0 : b.i;
-        s_lp[threadIdx.x] = lp_on ? logf(__expf(b.v - M) / (tot + 1e-6f)) : 0.f;
-    }
-    __syncthreads();
+    const int R = p.R, st = p.step;
+    int       emitted = 0;
     // ---- stage 1: m, the longest prefix of drafts the model agrees with ----
     if (threadIdx.x == 0) {
         int m = 0;
         while (m < R - 1 && s_draft[m] == s_a[m]) {
             m++;
         }
-        s_m = m;
+        *s_m_slot = m;
     }
     __syncthreads();
-    const int m = s_m;
+    const int m = *s_m_slot;
     // ---- the stop words at every candidate position st + i, i <= m (stop_criteria_kernels.cu:24-83): a (position, word) pair per
     // thread; tokens before st are the history, tokens from st on the ones this pass is about to write ----
     if (p.stop_words) {
@@ -788,7 +755,54 @@ __global__ __launch_bounds__(256) void k_verify_close(const VerifyCloseParams p,
             __threadfence_system();
             p.h_flags[FLAG_ALL_FINISHED] = fin;
         }
+        emitted = e;
     }
+    return emitted;
+}
+
+__global__ __launch_bounds__(256) void k_verify_close(const VerifyCloseParams p, const float* part)
+{
+    constexpr int RM = VERIFY_MAX_ROWS;
+    __shared__ unsigned s_part[RM * VS_SLICES * 4];
+    __shared__ int   s_a[RM], s_draft[RM], s_stop[RM];
+    __shared__ float s_lp[RM];
+    __shared__ int   s_m;
+    const int  R = p.R;
+    const bool lp_on = p.cum_log_probs || p.output_log_probs;
+    {  // every row's partials, requested together
+        const va_gu32* q = (const va_gu32*)part;
+        for (int i = threadIdx.x; i < R * VS_SLICES * 4; i += 256) {
+            s_part[i] = __hip_atomic_load(q + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if ((int)threadIdx.x < RM) {
+            s_draft[threadIdx.x] = (int)threadIdx.x < R - 1 ? p.draft[threadIdx.x] : -1;
+            s_stop[threadIdx.x]  = 0;
+        }
+    }
+    __syncthreads();
+    // ---- a[r] and its log-probability: row r's partials in slice order, by one thread ----
+    if ((int)threadIdx.x < R) {
+        const unsigned* q = s_part + threadIdx.x * VS_SLICES * 4;
+        VI    b{__uint_as_float(q[0]), (int)q[1]};
+        float M = __uint_as_float(q[2]);
+        for (int sl = 1; sl < VS_SLICES; sl++) {
+            const float v = __uint_as_float(q[sl * 4]);
+            const int   i = (int)q[sl * 4 + 1];
+            if (better(v, i, b.v, b.i)) {
+                b.v = v;
+                b.i = i;
+            }
+            M = fmaxf(M, __uint_as_float(q[sl * 4 + 2]));
+        }
+        float tot = 0.f;
+        for (int sl = 0; sl < VS_SLICES; sl++) {
+            tot += __uint_as_float(q[sl * 4 + 3]) * __expf(__uint_as_float(q[sl * 4 + 2]) - M);
+        }
+        s_a[threadIdx.x]  = (b.i == 0x7fffffff || b.i < 0) ? 0 : b.i;
+        s_lp[threadIdx.x] = lp_on ? logf(__expf(b.v - M) / (tot + 1e-6f)) : 0.f;
+    }
+    __syncthreads();
+    (void)verify_close_stages(p, lp_on, s_a, s_lp, s_draft, s_stop, &s_m);
 }
 
 size_t verify_close_workspace_bytes()
@@ -805,6 +819,192 @@ void launch_verify_close(const VerifyCloseParams& p, hipStream_t s)
     FTCF_CHECK_ARG(!p.stop_words || p.stop_len >= 1, "verify accept: stop_words needs stop_len >= 1");
     hipLaunchKernelGGL(k_verify_slices, dim3(VS_SLICES, p.R), dim3(256), 0, s, p.logits, p.V, p.ws);
     hipLaunchKernelGGL(k_verify_close, dim3(1), dim3(256), 0, s, p, (const float*)p.ws);
+    FTCF_HIP_CHECK(hipGetLastError());
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The tail of a verify pass of a TOP-K SAMPLED request, in three launches.  The engine's random numbers are
+// counter based (ftcf_uniform(seed, 0, draw)): the n-th generated token of a request consumes draw n whatever happened before, and
+// row i of a pass is reached only behind i accepted rows, i.e. behind exactly i draws.  So row i is SAMPLED with draw
+// draw_counter + i, draft i is accepted only when it is the sampled token, and the counter advances by the tokens emitted: the
+// output is the plain sampled run's token sequence for the same seed.
+//  * k_verify_topk_slices  : grid (VS_SLICES, R), the first half of k_topk_decode for row blockIdx.y: the slice's logits in registers
+//      (multiplied by k_decode_prep's temperature factor on load; the buffer is left alone), its {max, sum of exponentials} when
+//      log-probabilities are wanted, its k best as a set (slice_select; block_best for one), written through (agent scope).
+//  * k_verify_pick         : grid (R).  Row r's workgroup merges the 32 candidate sets as k_topk_decode's finishing workgroup does
+//      (the same functions under the same conditions), one thread draws with draw_counter[0] + r (topk_draw_at) and leaves the token
+//      and logf(probability), commit_pick's value.
+//  * k_verify_sample_close : one workgroup, verify_close_stages on the sampled tokens, then draw_counter[0] += emitted.
+// No workgroup waits for another: the launch boundaries order candidates, picks and the counter.  Every merge order is fixed: two
+// launches give identical bits.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int VT_MAXE = 16;  // logits per thread: V <= 32 * 256 * 16 = 131072 (VERIFY_SAMPLE_MAX_V)
+constexpr int VT_MAXK = VERIFY_SAMPLE_MAX_K;
+constexpr size_t VT_CAND  = (size_t)VERIFY_MAX_ROWS * VS_SLICES * VT_MAXK;  // candidate values, then as many ids ...
+constexpr size_t VT_STATS = (size_t)VERIFY_MAX_ROWS * VS_SLICES * 2;        // ... {max, sum of exponentials} per slice ...
+constexpr size_t VT_PICKS = (size_t)VERIFY_MAX_ROWS * 2;                    // ... every row's token, then its log-probability
+
+__global__ __launch_bounds__(256) void k_verify_topk_slices(const float* __restrict__ logits, const int V, const int k, const int lp_on,
+                                                            const int apply_temperature, const float temperature, float* ws)
+{
+    __shared__ float redv[4];
+    __shared__ int   redi[4];
+    __shared__ int   hist[256];
+    __shared__ int   hist8[8][257];
+    __shared__ int   s_sel[4];
+    const int    r = blockIdx.y, blk = blockIdx.x;
+    const int    slice = (V + VS_SLICES - 1) / VS_SLICES;
+    const int    i0 = blk * slice;
+    const int    n  = max(0, min(slice, V - i0));
+    const float* l  = logits + (size_t)r * V + i0;
+    float*       ov = ws + ((size_t)r * VS_SLICES + blk) * VT_MAXK;
+    int*         oi = reinterpret_cast<int*>(ws + VT_CAND) + ((size_t)r * VS_SLICES + blk) * VT_MAXK;
+    const float  scale = apply_temperature ? 1.0f / (temperature + 1e-6f) : 1.f;  // sampling_penalty_kernels.cu:117-147
+    float        vals[VT_MAXE], lmax;
+    const int    ne   = n > (int)threadIdx.x ? (n - (int)threadIdx.x + 255) / 256 : 0;
+    const VI     best = slice_load(vals, l, ne, -1, lmax, scale);
+    if (lp_on) {  // {max, sum of exp(v - max)} of the slice for the row's soft-max
+        float       m;
+        const float sum = slice_stats(vals, ne, lmax, redv, m);
+        if (threadIdx.x == 0) {
+            va_gu32* st = (va_gu32*)(ws + 2 * VT_CAND + ((size_t)r * VS_SLICES + blk) * 2);
+            __hip_atomic_store(st + 0, __float_as_uint(n > 0 ? m : -FLT_MAX), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(st + 1, __float_as_uint(n > 0 ? sum : 0.f), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    const int ke = k < n ? k : n;  // candidates this slice can supply
+    for (int i = ke + threadIdx.x; i < k; i += 256) {
+        put_cand<true>(ov, oi, i, -INFINITY, -1);
+    }
+    if (ke == 1) {
+        const VI b = block_best(best, redv, redi);
+        if (threadIdx.x == 0) {
+            put_cand<true>(ov, oi, 0, b.v, i0 + b.i);
+        }
+    }
+    else if (ke > 1) {
+        slice_select<VT_MAXE, true>(vals, ne, n, ke, l, i0, ov, oi, hist8, hist, s_sel, redi, false, -1, scale);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_verify_pick(float* ws, const int k, const int lp_on, const uint64_t seed,
+                                                     const uint64_t* __restrict__ draw_counter, const float p_topk)
+{
+    __shared__ float redv[4];
+    __shared__ int   redi[4];
+    __shared__ int   hist[256];
+    __shared__ int   hist8[8][257];
+    __shared__ int   s_sel[4];
+    __shared__ float sv[VS_SLICES * VT_MAXK];
+    __shared__ int   si[VS_SLICES * VT_MAXK];
+    __shared__ float tv[VT_MAXK];
+    __shared__ int   ti[VT_MAXK];
+    const int row = blockIdx.x;
+    int       n2 = 1;
+    while (n2 < VS_SLICES * k) {
+        n2 <<= 1;
+    }
+    int k2 = 1;
+    while (k2 < k) {
+        k2 <<= 1;
+    }
+    {
+        const va_gu32* cv = (const va_gu32*)(ws + (size_t)row * VS_SLICES * VT_MAXK);
+        const va_gu32* ci = (const va_gu32*)(ws + VT_CAND + (size_t)row * VS_SLICES * VT_MAXK);
+        // (all of a thread's candidates requested together: one round trip, not eight)
+        constexpr int NC = VS_SLICES * VT_MAXK / 256;
+        unsigned      rv[NC], ri[NC];
+#pragma unroll
+        for (int j = 0; j < NC; j++) {
+            const int c  = threadIdx.x + 256 * j;
+            const int cc = c < VS_SLICES * k ? c : 0;
+            const int q = cc / k, e = cc - q * k;
+            ri[j] = __hip_atomic_load(ci + q * VT_MAXK + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            rv[j] = __hip_atomic_load(cv + q * VT_MAXK + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+#pragma unroll
+        for (int j = 0; j < NC; j++) {
+            const int c = threadIdx.x + 256 * j;
+            if (c < n2) {
+                const bool ok = c < VS_SLICES * k && (int)ri[j] >= 0;
+                sv[c]         = ok ? __uint_as_float(rv[j]) : -INFINITY;
+                si[c]         = ok ? (int)ri[j] : 0x7fffffff;
+            }
+        }
+    }
+    if (k > 1 && n2 >= 4 * k2) {
+        union_topk(sv, si, n2, k, k2, tv, ti, hist, s_sel, redi, hist8);
+    }
+    else if (k > 1) {
+        bitonic_sort_best_first(sv, si, n2);
+    }
+    else {
+        best_of_slices(sv, si, VS_SLICES, redv, redi);
+    }
+    // ---- top-k layer: sv / si [0, k) are the row's k best; the draw of the token this row would be ----
+    if (threadIdx.x == 0) {
+        const va_gu32* st   = (const va_gu32*)(ws + 2 * VT_CAND + (size_t)row * VS_SLICES * 2);
+        const int      pick = topk_draw_at<VS_SLICES>(lp_on != 0, seed, draw_counter[0] + (uint64_t)row, p_topk, k, sv, [&](const int i) {
+            return __uint_as_float(__hip_atomic_load(st + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        });
+        int id = si[pick];
+        if (id == 0x7fffffff || id < 0) {  // (commit_pick's rule)
+            id = 0;
+        }
+        va_gu32* out = (va_gu32*)(ws + 2 * VT_CAND + VT_STATS);
+        __hip_atomic_store(out + row, (unsigned)id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(out + VERIFY_MAX_ROWS + row, __float_as_uint(lp_on ? logf(sv[pick]) : 0.f), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_verify_sample_close(const VerifyCloseParams p, const float* ws, uint64_t* draw_counter)
+{
+    constexpr int RM = VERIFY_MAX_ROWS;
+    __shared__ int   s_a[RM], s_draft[RM], s_stop[RM];
+    __shared__ float s_lp[RM];
+    __shared__ int   s_m;
+    const int  R = p.R;
+    const bool lp_on = p.cum_log_probs || p.output_log_probs;
+    if ((int)threadIdx.x < RM) {
+        const int      r = threadIdx.x, rc = r < R ? r : 0;
+        const va_gu32* q = (const va_gu32*)(ws + 2 * VT_CAND + VT_STATS);
+        const unsigned id = __hip_atomic_load(q + rc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned lp = __hip_atomic_load(q + RM + rc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_a[r]     = r < R ? (int)id : 0;
+        s_lp[r]    = r < R ? __uint_as_float(lp) : 0.f;
+        s_draft[r] = r < R - 1 ? p.draft[r] : -1;
+        s_stop[r]  = 0;
+    }
+    __syncthreads();
+    const int e = verify_close_stages(p, lp_on, s_a, s_lp, s_draft, s_stop, &s_m);
+    if (threadIdx.x == 0) {
+        draw_counter[0] += (uint64_t)e;  // one draw per emitted token: the rows behind the accepted run consumed none
+    }
+}
+
+size_t verify_sample_workspace_bytes()
+{
+    return (2 * VT_CAND + VT_STATS + VT_PICKS) * sizeof(float);
+}
+
+void launch_verify_sample(const VerifySampleParams& q, hipStream_t s)
+{
+    const VerifyCloseParams& p = q.c;
+    FTCF_CHECK_ARG(p.R >= 1 && p.R <= VERIFY_MAX_ROWS && p.V >= 1, "verify sample: 1 <= rows <= 16, vocabulary >= 1");
+    FTCF_CHECK_ARG(q.top_k >= 1 && q.top_k <= VERIFY_SAMPLE_MAX_K && p.V <= VERIFY_SAMPLE_MAX_V,
+                   "verify sample: 1 <= top_k <= 64, vocabulary <= 131072");
+    FTCF_CHECK_ARG(p.logits && p.output_ids && p.finished && p.seq_len && q.ws && q.draw_counter && (p.R == 1 || p.draft),
+                   "verify sample: NULL tensor");
+    FTCF_CHECK_ARG(p.step >= 1 && p.max_input_len >= 0 && p.step >= p.max_input_len && p.step + p.R <= p.total_len,
+                   "verify sample: the rows' positions step .. step + R - 1 must lie in [max(1, max_input_len), total_len)");
+    FTCF_CHECK_ARG(!p.stop_words || p.stop_len >= 1, "verify sample: stop_words needs stop_len >= 1");
+    const int lp_on = (p.cum_log_probs || p.output_log_probs) ? 1 : 0;
+    hipLaunchKernelGGL(k_verify_topk_slices, dim3(VS_SLICES, p.R), dim3(256), 0, s, p.logits, p.V, q.top_k, lp_on, q.apply_temperature,
+                       q.temperature, q.ws);
+    hipLaunchKernelGGL(k_verify_pick, dim3(p.R), dim3(256), 0, s, q.ws, q.top_k, lp_on, q.random_seed, (const uint64_t*)q.draw_counter,
+                       q.top_p_topk);
+    hipLaunchKernelGGL(k_verify_sample_close, dim3(1), dim3(256), 0, s, p, (const float*)q.ws, q.draw_counter);
     FTCF_HIP_CHECK(hipGetLastError());
 }
 

@@ -205,7 +205,7 @@ class GptNeoXOp:
         CUDA [output_len]: the guess for each generated position, negative = no guess) -- and verified in one decoder pass.
         The tokens are those of the same request without it; a request the feature does not cover runs as before and
         stats()["spec_active"] is 0.  set_speculative_scope(1) widens what it covers to requests with stop words,
-        log-probabilities, a callback or optional_last_tokens."""
+        log-probabilities, a callback or optional_last_tokens, set_speculative_sampling(1) to top-k sampled requests."""
         spec_k, spec_n = check_speculative_args(speculative_tokens, speculative_ngram, draft_ids, output_len)
         _check_input(input_ids, "input_ids", torch.int32)
         if input_ids.dim() != 2:
@@ -317,6 +317,12 @@ class GptNeoXOp:
         call: 0 (the default) the bare greedy request; 1 also a greedy request with stop words, return_cum_log_probs,
         return_output_log_probs, a callback or optional_last_tokens -- what harness.generate() sends.  Anything else raises."""
         capi.check(capi.lib().ftcf_gptneox_set_speculative_scope(self._h, int(scope)))
+
+    def set_speculative_sampling(self, enabled=1):
+        """Whether a top-k sampled request (top_k in 2..64, any temperature, a top_p next to the top_k) with speculative_tokens
+        may speculate (ftcf_gptneox_set_speculative_sampling), for requests begun after the call: 0 the default, 1 yes -- its
+        tokens are those of the same request without speculation for the same random_seed.  Anything else raises."""
+        capi.check(capi.lib().ftcf_gptneox_set_speculative_sampling(self._h, int(enabled)))
 
 
 def symmetric_quantize_last_axis_of_batched_matrix_int8(weight):

@@ -383,7 +383,8 @@ class GptNeoX(torch.nn.Module):
                 return_cum_log_probs=0, callback=None, speculative_tokens=None, speculative_ngram=None):
         """speculative_tokens / speculative_ngram (None: the call is the reference's): speculative greedy decoding of
         GptNeoXOp.forward, with the engine's speculative scope set to 1 -- the requests generate() sends (cum_log_probs, a
-        callback, stop words, last tokens) are then covered.  An op without the switch gets the reference's call."""
+        callback, stop words, last tokens) are then covered -- and with speculative sampling switched on, so that their top_k = 50
+        is covered too (token for token the unspeculated request's).  An op without the switches gets the reference's call."""
         if not self.build_model:
             self.cuda()
         assert start_ids.size(1) > 0, \
@@ -392,6 +393,8 @@ class GptNeoX(torch.nn.Module):
         speculative = {}
         if (speculative_tokens is not None or speculative_ngram is not None) and hasattr(self.model, "set_speculative_scope"):
             self.model.set_speculative_scope(1)
+            if hasattr(self.model, "set_speculative_sampling"):  # (the top_k = 50 every request of get_data_package carries)
+                self.model.set_speculative_sampling(1)
             speculative = dict(speculative_tokens=speculative_tokens, speculative_ngram=speculative_ngram)
         outputs = self.model.forward(to_dev(start_ids), to_dev(start_lengths), output_len, beam_width, top_k, top_p,
                                      beam_search_diversity_rate, temperature, len_penalty, repetition_penalty,

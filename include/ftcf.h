@@ -279,6 +279,43 @@ typedef struct ftcf_verify_accept_args {
     int*         tokens;
 } ftcf_verify_accept_args;
 int ftcf_verify_accept(const ftcf_verify_accept_args* args, void* stream);
+/* The decode tail of a verify pass of a TOP-K SAMPLED request (the engine runs it for every pass of a sampled request that began
+ * under ftcf_gptneox_set_speculative_sampling(h, 1)): three launches and nothing else.  Everything is ftcf_verify_accept's but
+ * a[i]: row i's logits, each multiplied by 1.0f / (temperature + 1e-6f) as it is read when temperature is neither 0 nor 1 (the
+ * buffer is not modified), go through the top-k layer of ftcf_dynamic_decode_step -- the top_k best (value descending, index
+ * ascending on ties) become exp(v - best) or, with cum_log_probs / output_log_probs given, their soft-max probabilities over the
+ * row, and uniform number u = draw (draw_counter[0] + i) of the stream of random_seed walks them up to u * top_p_topk * their sum
+ * -- and a[i] is the token the walk stops at; lp = logf(its probability).  The tokens are emitted as there, and
+ * draw_counter[0] += emitted (device uint64 [1]).  Row i is reached only behind i accepted rows, i.e. behind exactly i draws: the
+ * emitted tokens are those of `emitted` plain sampled steps from the same state, and a rejected row has consumed no draw.
+ * top_p_topk: the p of the top-k layer in (0, 1], 1 = all of the k.  1 <= top_k <= 64 and V <= 131072 (else
+ * FTCF_ERR_INVALID_ARG, as for every bad argument of ftcf_verify_accept); draw_counter must not be NULL.  Deterministic: two
+ * calls from the same state give identical bits.  workspace: FTCF_VERIFY_SAMPLE_WORKSPACE_BYTES device bytes. */
+#define FTCF_VERIFY_SAMPLE_WORKSPACE_BYTES 266368
+typedef struct ftcf_verify_sample_args {
+    int                 struct_size;
+    int                 R, V, step, end_id, max_input_len, total_len;
+    const float*        logits;
+    const int*          draft;
+    int*                output_ids;
+    const int*          stop_words;
+    int                 stop_len;
+    uint8_t*            finished;
+    int*                seq_len;
+    float*              cum_log_probs;
+    float*              output_log_probs;
+    void*               workspace;
+    size_t              workspace_bytes;
+    int*                emitted;
+    int*                accepted;
+    int*                tokens;
+    int                 top_k;
+    float               top_p_topk;
+    float               temperature;
+    unsigned long long  random_seed;
+    unsigned long long* draw_counter;
+} ftcf_verify_sample_args;
+int ftcf_verify_sample(const ftcf_verify_sample_args* args, void* stream);
 /* GptContextAttentionLayer<T>::forward minus the two projections (layers/attention_layers/
  * GptContextAttentionLayer.cc:142-345): bias + NeoX rotary + cache fill + causal masked softmax(QK^T)V.
  * qkv [B*S, 3*Hl] fp16 (row = b*S+s), ctx [B*S, Hl] fp16. */
@@ -681,6 +718,16 @@ int ftcf_gptneox_set_profiling(ftcf_gptneox_t h, int enabled);
  * speculative_tokens of ftcf_forward_args); every verify pass of such an engine closes with the two launches of
  * ftcf_verify_accept.  Holds for requests begun after the call.  Any other value: FTCF_ERR_INVALID_ARG. */
 int ftcf_gptneox_set_speculative_scope(ftcf_gptneox_t h, int scope);
+/* Whether a TOP-K SAMPLED request with speculative_tokens > 0 may speculate (a switch of the engine like the scope, and
+ * independent of it).  0, the default: as before the switch existed -- the same launches, bits and spec_active.  1: top_k in
+ * 2..64 no longer excludes a request, with any temperature (also together with log-probability outputs: the pass's tail applies
+ * it) and with a top_p next to the top_k (the p of the top-k layer); every verify pass of such a request closes with the three
+ * launches of ftcf_verify_sample on the engine's draw counter, so the tokens, sequence lengths and callback invocations are
+ * those of the unspeculated request for the same random_seed.  What the scope decides (stop words, log-probabilities, callback,
+ * optional_last_tokens) it still decides; pure top-p (top_k 0 with a top_p), top_k > 64, a vocabulary above 131072 and
+ * everything speculative_tokens of ftcf_forward_args excludes besides stay excluded.  Greedy requests are not affected.  Holds for
+ * requests begun after the call.  Any other value: FTCF_ERR_INVALID_ARG. */
+int ftcf_gptneox_set_speculative_sampling(ftcf_gptneox_t h, int enabled);
 int ftcf_gptneox_destroy(ftcf_gptneox_t h);
 
 

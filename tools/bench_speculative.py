@@ -14,6 +14,14 @@ it -- return_cum_log_probs, a stop-word list that never matches and a no-op call
 k_verify_close instead of k_verify_argmax + k_verify_accept.  Per round the plain run, the scope 0 run and the scope 1 run follow
 each other in the one process; a row reports both legs' milliseconds per verify pass (best, and the spread over the rounds) and
 tokens/s (profiles/speculative_scope_bench.txt).
+
+--sampled adds the leg of speculative SAMPLING (GptNeoXOp.set_speculative_sampling(1)): the request as the harness sends it with its
+top_k = 50, whose passes close with k_verify_topk_slices + k_verify_pick + k_verify_sample_close.  The drafts are the plain SAMPLED
+run's tokens (same seed) with every p-th replaced.  Per round the plain greedy run, the greedy scope 1 run, the plain sampled run
+and the speculative sampled run follow each other in the one process; a row reports, for the greedy and the sampled leg, the plain
+milliseconds per token, milliseconds per verify pass (best and the spread) and tokens/s (profiles/speculative_sampled_bench.txt).
+The difference between the two passes is the selection: per row the radix select of 32 slices' k best, a merge and a draw where
+the greedy pass keeps an arg max -- what k_topk_decode costs over k_greedy_decode in the plain step.
 """
 import argparse
 import json
@@ -37,6 +45,8 @@ def main():
     p.add_argument("--ks", default="2,4,8")
     p.add_argument("--every", default="0,4,2,1", help="corrupt every p-th draft (0: none, 1: all)")
     p.add_argument("--scope", action="store_true", help="add the scope 1 leg (cum_log_probs + stop words + callback) next to scope 0")
+    p.add_argument("--sampled", action="store_true", help="the top_k 50 request of the harness under speculative sampling, next to greedy scope 1")
+    p.add_argument("--seed", type=int, default=7, help="random_seed of the sampled legs")
     a = p.parse_args()
     capi.require_gpu()
     import bench
@@ -51,8 +61,8 @@ def main():
     lens = torch.full((1,), S, dtype=torch.int32, device=dev)
     k1 = torch.tensor([1], dtype=torch.int32)
 
-    def run(n_out=out_len, **kw):
-        o = op.forward(ids, lens, n_out, 1, k1, **kw)
+    def run(n_out=out_len, top_k=k1, **kw):
+        o = op.forward(ids, lens, n_out, 1, top_k, **kw)
         torch.cuda.synchronize()
         return o[0][0, 0, S:].cpu().tolist(), int(o[1][0, 0].item()) - S, op.stats()
 
@@ -70,6 +80,8 @@ def main():
     every = [int(x) for x in a.every.split(",") if x]
     if a.scope:
         return scope_legs(a, op, run, drafts, gen, n_gen, ks, every, dev)
+    if a.sampled:
+        return sampled_legs(a, op, run, gen, n_gen, ks, every, dev, m.vocab)
     for K in ks:  # warm-up of each shape (arena, graph capture of the plain step, every kernel's code object)
         run(32)
         run(32, speculative_tokens=K, draft_ids=drafts(0)[:32].contiguous())
@@ -138,6 +150,64 @@ def scope_legs(a, op, run, drafts, gen, n_gen, ks, every, dev):
             rows.append(row)
             print(json.dumps(row), flush=True)
     op.set_speculative_scope(0)
+    return rows
+
+
+def sampled_legs(a, op, run, gen, n_gen, ks, every, dev, V):
+    """the harness's request greedy at scope 1 next to the same request with its top_k = 50 under speculative sampling, alternating"""
+    never = torch.tensor([[[2, 2], [2, -1]]], dtype=torch.int32, device=dev)  # one word, the end token twice: never completes
+    wide = dict(return_cum_log_probs=1, stop_words_list=never, callback=lambda d: None)
+    k50 = dict(top_k=torch.tensor([50], dtype=torch.int32), random_seed=torch.tensor([a.seed], dtype=torch.int64))
+    out_len = a.out_len
+    op.set_speculative_scope(1)
+    op.set_speculative_sampling(1)
+    s_gen, s_n, _ = run(**k50, **wide)
+    s_gen = s_gen[:s_n]
+    print(json.dumps(dict(sampled_plain_tokens=s_n, not_the_greedy_token=sum(1 for x, y in zip(s_gen, gen) if x != y))), flush=True)
+    wrong = lambda t: 3 + (t - 3 + 1) % (V - 3)
+
+    def drafts(tokens, ev):
+        d = [(wrong(t) if ev and i % ev == ev - 1 else t) for i, t in enumerate(tokens)]
+        return torch.tensor(d + [3] * (out_len - len(d)), dtype=torch.int32, device=dev)
+
+    def leg(tokens, n_tokens, plain_ms, **kw):
+        toks, n_s, ss = run(**kw)
+        n_plain = ss["decode_steps"] - ss["spec_accepted"] - ss["spec_steps"]
+        pass_ms = (ss["decode_ms"] - n_plain * plain_ms) / max(1, ss["spec_steps"])
+        return dict(spec_active=ss["spec_active"], passes=ss["spec_steps"], accepted=ss["spec_accepted"], ms_per_pass=pass_ms,
+                    tok_s=ss["decode_steps"] / ss["decode_ms"] * 1e3,
+                    tokens_differ=sum(1 for x, y in zip(toks[:n_s], tokens) if x != y) + abs(n_s - n_tokens))
+
+    for K in ks:  # warm-up of each shape
+        run(32, speculative_tokens=K, draft_ids=drafts(gen, 0)[:32].contiguous(), **wide)
+        run(32, speculative_tokens=K, draft_ids=drafts(s_gen, 0)[:32].contiguous(), **k50, **wide)
+    rows = []
+    for K in ks:
+        for ev in every:
+            dg, ds = drafts(gen, ev), drafts(s_gen, ev)
+            legs = {"greedy": [], "sampled": []}
+            plain = {"greedy": [], "sampled": []}
+            for _ in range(a.rounds):
+                sp = run(**wide)[2]
+                plain["greedy"].append(sp["decode_ms"] / sp["decode_steps"])
+                legs["greedy"].append(leg(gen, n_gen, plain["greedy"][-1], speculative_tokens=K, draft_ids=dg, **wide))
+                sp = run(**k50, **wide)[2]
+                plain["sampled"].append(sp["decode_ms"] / sp["decode_steps"])
+                legs["sampled"].append(leg(s_gen, s_n, plain["sampled"][-1], speculative_tokens=K, draft_ids=ds, **k50, **wide))
+            row = dict(K=K, corrupt_every=ev)
+            for name in ("greedy", "sampled"):
+                ms = [r["ms_per_pass"] for r in legs[name]]
+                row[name] = dict(plain_ms_per_token=[round(min(plain[name]), 4), round(max(plain[name]), 4)],
+                                 plain_tok_s=round(1e3 / min(plain[name]), 1), spec_active=legs[name][0]["spec_active"],
+                                 passes=legs[name][0]["passes"], accepted=legs[name][0]["accepted"], ms_per_pass_min=round(min(ms), 4),
+                                 ms_per_pass_max=round(max(ms), 4), tok_s_best=round(max(r["tok_s"] for r in legs[name]), 1),
+                                 tokens_differ=max(r["tokens_differ"] for r in legs[name]))
+            row["sampled_minus_greedy_ms_per_pass"] = round(row["sampled"]["ms_per_pass_min"] - row["greedy"]["ms_per_pass_min"], 4)
+            row["sampled_minus_greedy_plain_ms"] = round(row["sampled"]["plain_ms_per_token"][0] - row["greedy"]["plain_ms_per_token"][0], 4)
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    op.set_speculative_scope(0)
+    op.set_speculative_sampling(0)
     return rows
 
 
