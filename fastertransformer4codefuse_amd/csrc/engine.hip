@@ -186,10 +186,10 @@ void ftcf_gptneox::clear_exchange_window()
 // it always has, and the stats say so.  No side effect but ONE host synchronisation, issued only when everything else holds.
 bool ftcf_gptneox::speculation_wanted(const ftcf_forward_args& a, int total)
 {
-    // what the engine's scope decides (ftcf_gptneox_set_speculative_scope): at scope 0 a request with any of these runs
-    // unspeculated; at scope 1 the pass's tail (k_verify_close) serves them.  optional_last_tokens masks the first generated step
-    // only, which never drafts.  A temperature leaves the arg max alone but not the soft-max: with a log-probability output it
-    // still excludes the request.
+    // what the engine's scope decides (ftcf_gptneox_set_speculative_scope), here and nowhere else: at scope 0 a request with any
+    // of these runs unspeculated; at scope 1 it speculates and the pass's tail (k_verify_close, which closes every greedy pass at
+    // either scope) serves them.  optional_last_tokens masks the first generated step only, which never drafts.  A temperature
+    // leaves the arg max alone but not the soft-max: with a log-probability output it still excludes the request.
     // A top-k sampled request (ftcf_gptneox_set_speculative_sampling): top_k in 2..64, a top_p next to it being the p of the top-k
     // layer, over a vocabulary the sampled tail holds in registers.  Its tail applies the temperature itself, so a temperature
     // excludes nothing there.
@@ -490,7 +490,6 @@ void ftcf_gptneox::begin(const ftcf_forward_args& a)
     FTCF_HIP_CHECK(hipEventRecord(e1, stream));
 
     ses.open(a, session_sampling_params(a, route, in_len), session_beam_params(a, route, in_len), e0, e1, spec_plan);
-    ses.spec_scope = spec_scope;
     if (spec_plan && route.k_eff[0] >= 2) {  // (speculation_wanted admitted it: the switch is on, 2 <= top_k <= 64)
         ses.spec_sampled    = true;
         ses.spec_top_k      = route.k_eff[0];
@@ -734,7 +733,7 @@ int ftcf_gptneox::step(int max_steps)
 // One verify pass: the token of position step - 1 and `drafts` drafted tokens as R = drafts + 1 rows of the
 // one sequence through the batched decode layers in their grouped form (ParallelResidualDecoder, layers.hip.h: the burst GEMM pairs
 // [QKV, FFN1] -> attention -> [out-proj, FFN2], residual + both LayerNorms in one pass) with the verify attention, then the final
-// LayerNorm, the LM head on R rows and the acceptance kernel, which closes the step as the greedy kernels do.  The K / V rows of
+// LayerNorm, the LM head on R rows and the acceptance kernels, which close the step as the greedy kernels do.  The K / V rows of
 // rejected drafts stay in the cache beyond the sequence's length; the next step overwrites them.
 void ftcf_gptneox::verify_pass(int st, int drafts)
 {
@@ -769,56 +768,41 @@ void ftcf_gptneox::verify_pass(int st, int drafts)
         [](f16*, size_t, hipStream_t, bool) {}, [&](double bytes, auto&& launch, hipStream_t s) { timed(KIND_SMALLM, bytes, launch, s); });
     launch_layernorm(vx, final_g, final_b, vnrm, R, H, 1e-5f, true, stream);
     timed(KIND_LM_HEAD, 2.0 * V * H, [&] { lm_head_dispatch(vnrm, lm_head, vlogits, R, V, H, V, stream); });
-    if (ses.spec_sampled || ses.spec_scope == 1) {  // stop words, log-probabilities and the callback's tokens are the tail's business
-        VerifySampleParams q{};
-        VerifyCloseParams& cp = q.c;
-        cp.logits           = vlogits;
-        cp.R                = R;
-        cp.V                = V;
-        cp.step             = st;
-        cp.end_id           = cfg.end_id;
-        cp.max_input_len    = ses.S;
-        cp.total_len        = ses.total;
-        cp.draft            = spec_draft;
-        cp.output_ids       = step_ids;
-        cp.stop_words       = ses.sp.stop_words;
-        cp.stop_len         = ses.sp.stop_len;
-        cp.finished         = finished;
-        cp.seq_len          = seq_len;
-        cp.cum_log_probs    = ses.sp.return_cum_log_probs ? cum : nullptr;
-        cp.output_log_probs = ses.sp.return_cum_log_probs ? ses.sp.output_log_probs : nullptr;
-        cp.state            = state;
-        cp.h_flags          = h_flags;
-        cp.ws               = spec_close_ws;
-        if (ses.spec_sampled) {  // every row sampled with the draw the plain step of its position would take (either scope)
-            q.top_k             = ses.spec_top_k;
-            q.top_p_topk        = ses.spec_p_topk;
-            q.apply_temperature = ses.spec_apply_temp;
-            q.temperature       = ses.spec_temp;
-            q.random_seed       = ses.spec_seed;
-            q.draw_counter      = draws;
-            q.ws                = spec_sample_ws;
-            launch_verify_sample(q, stream);
-        }
-        else {
-            launch_verify_close(cp, stream);
-        }
+    // One close for every pass.  Stop words, log-probabilities and the callback's tokens are the tail's business; at scope 0
+    // speculation_wanted admitted the request only without them (and without optional_last_tokens), so these fields are NULL there
+    // -- the condition under which the close is the bare greedy acceptance: arg max, accepted prefix, cut after the first end_id.
+    VerifySampleParams q{};
+    VerifyCloseParams& cp = q.c;
+    cp.logits           = vlogits;
+    cp.R                = R;
+    cp.V                = V;
+    cp.step             = st;
+    cp.end_id           = cfg.end_id;
+    cp.max_input_len    = ses.S;
+    cp.total_len        = ses.total;
+    cp.draft            = spec_draft;
+    cp.output_ids       = step_ids;
+    cp.stop_words       = ses.sp.stop_words;
+    cp.stop_len         = ses.sp.stop_len;
+    cp.finished         = finished;
+    cp.seq_len          = seq_len;
+    cp.cum_log_probs    = ses.sp.return_cum_log_probs ? cum : nullptr;
+    cp.output_log_probs = ses.sp.return_cum_log_probs ? ses.sp.output_log_probs : nullptr;
+    cp.state            = state;
+    cp.h_flags          = h_flags;
+    cp.ws               = spec_close_ws;
+    if (ses.spec_sampled) {  // every row sampled with the draw the plain step of its position would take (either scope)
+        q.top_k             = ses.spec_top_k;
+        q.top_p_topk        = ses.spec_p_topk;
+        q.apply_temperature = ses.spec_apply_temp;
+        q.temperature       = ses.spec_temp;
+        q.random_seed       = ses.spec_seed;
+        q.draw_counter      = draws;
+        q.ws                = spec_sample_ws;
+        launch_verify_sample(q, stream);
     }
     else {
-        VerifyAcceptParams vp{};
-        vp.logits     = vlogits;
-        vp.R          = R;
-        vp.V          = V;
-        vp.step       = st;
-        vp.end_id     = cfg.end_id;
-        vp.draft      = spec_draft;
-        vp.output_ids = step_ids;
-        vp.finished   = finished;
-        vp.seq_len    = seq_len;
-        vp.state      = state;
-        vp.h_flags    = h_flags;
-        vp.argmax_ws  = spec_argmax;
-        launch_verify_accept(vp, stream);
+        launch_verify_close(cp, stream);
     }
     // what the next plain step expects of the step before it (k_greedy_decode's tail): the embedding row of the last token emitted
     // and the rotary table of its position

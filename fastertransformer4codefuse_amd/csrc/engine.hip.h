@@ -224,10 +224,11 @@ struct ftcf_gptneox {
     f16 *  vx = nullptr, *vnrm = nullptr, *vnrm2 = nullptr, *vqkv = nullptr, *vctx = nullptr, *vatt = nullptr, *vffn = nullptr, *vmid = nullptr;
     float *vlogits = nullptr, *vrot = nullptr, *spec_aws = nullptr, *spec_gws = nullptr;
     size_t spec_partial = 0;  // split-K partials of the pass's burst GEMMs (a workspace of their own: [partials][tickets])
-    int *  spec_draft = nullptr, *spec_ndraft = nullptr, *spec_argmax = nullptr;
-    float* spec_close_ws = nullptr;  // the slice partials of k_verify_close (scope 1)
+    int *  spec_draft = nullptr, *spec_ndraft = nullptr;
+    float* spec_close_ws = nullptr;  // the slice partials of k_verify_close (every greedy pass, at either scope)
     // which requests may speculate (ftcf_gptneox_set_speculative_scope): 0 the bare greedy request, 1 also one with stop words,
-    // log-probabilities, a streaming callback or optional_last_tokens.  Read by begin(): a request keeps the scope it began under.
+    // log-probabilities, a streaming callback or optional_last_tokens.  Read by begin() alone (speculation_wanted): a request that
+    // began is not touched by a later call.
     int    spec_scope = 0;
     // may a top-k sampled request speculate (ftcf_gptneox_set_speculative_sampling)?  Its passes close with the sampled tail
     // (launch_verify_sample) on the request's own draw counter and seed.  Read by begin(), like the scope.
@@ -478,7 +479,6 @@ struct ftcf_gptneox {
         spec_gws     = c.take<float>((spec_partial + gemm_smallm_ticket_bytes()) / 4);
         spec_draft   = c.take<int>(R);
         spec_ndraft  = c.take<int>(4);
-        spec_argmax  = c.take<int>(2 * R);
         spec_close_ws = c.take<float>(verify_close_workspace_bytes() / 4);
         spec_sample_ws = c.take<float>(verify_sample_workspace_bytes() / 4);
     }
@@ -1391,7 +1391,6 @@ struct ftcf_gptneox {
         // speculative decoding: on for this request; K, N; the draft count the last step's draft kernel left for the next one;
         // verify passes, drafts proposed / accepted so far
         bool              spec = false;
-        int               spec_scope = 0;  // the engine's scope when the request began: 1 closes a pass with k_verify_close
         int               spec_K = 0, spec_N = 0, spec_nd = 0;
         int               spec_steps = 0, spec_drafted = 0, spec_accepted = 0;
         // a top-k sampled request that speculates: its passes close with the sampled tail on what the plain steps sample with

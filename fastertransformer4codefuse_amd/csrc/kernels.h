@@ -415,7 +415,7 @@ enum HostFlag {
     FLAG_SPEC_NEXT_DRAFTS  = 4,  // the draft kernel's count for the next step
     FLAG_SPEC_ACCEPTED     = 5,  // drafts of the verify pass that became output tokens
     FLAG_COUNT             = 6,
-    // a verify pass closed by k_verify_close (speculative scope 1): the tokens it emitted and the sequence length behind each
+    // a verify pass (k_verify_close, k_verify_sample_close): the tokens it emitted and the sequence length behind each
     FLAG_SPEC_TOKENS       = 16,  // [VERIFY_MAX_ROWS]
     FLAG_SPEC_SEQ_LEN      = 32,  // [VERIFY_MAX_ROWS]
     FLAG_WORDS             = 48   // words of the engine's mailbox
@@ -564,33 +564,19 @@ void launch_ngram_draft(const int* tokens, int n, const int* d_n, int K, int N, 
                         int* draft, int* n_draft, int* h_n_draft, const int* d_stop, hipStream_t s);
 // the input rows of a verify pass: x[0] = wte[tokens[step - 1]], x[i] = wte[draft[i - 1]]
 void launch_verify_embed(f16* x, const f16* wte, const int* tokens, const int* draft, int step, int R, int H, hipStream_t s);
-// acceptance: a[i] = argmax of logits row i (value descending, index ascending on ties); m = longest prefix with
-// draft[i] == a[i]; emits a[0 .. m] cut after the first end_id, appends them at output_ids[step ...], advances seq_len[0] and
-// the device step, sets finished / all_finished, and leaves all_finished, the last step written, the tokens emitted and the
-// drafts accepted in h_flags (pinned, HostFlag: FLAG_ALL_FINISHED, FLAG_LAST_STEP, FLAG_SPEC_EMITTED, FLAG_SPEC_ACCEPTED;
-// FLAG_SPEC_NEXT_DRAFTS is the draft kernel's).  argmax_ws: 2 * R words.
-struct VerifyAcceptParams {
-    const float* logits;  // [R, V]
-    int          R, V, step, end_id;
-    const int*   draft;  // [R - 1]
-    int*         output_ids;
-    uint8_t*     finished;
-    int*         seq_len;
-    DecodeState* state;
-    int*         h_flags;
-    int*         argmax_ws;
-};
-void launch_verify_accept(const VerifyAcceptParams& p, hipStream_t s);
-// The same acceptance for a request with stop words, log-probabilities or a streaming callback (speculative scope 1; the
-// stand-alone ftcf_verify_accept of include/ftcf.h is the contract), in two launches: k_verify_slices reduces every row in
-// VERIFY_ACCEPT_SLICES vocabulary slices to {best, index, max, sum of exponentials}, k_verify_close merges them in slice order
-// and closes the step: for i = 0 .. m in order the token a[i] goes to output_ids[step + i], its log-probability
-// logf(exp(v - max) / (sum + 1e-6f)) is added to cum_log_probs[0] (sequential fp32 adds) and stored at
-// output_log_probs[step + i - max_input_len], then end_id, the stop words (decode_finish_body's rule at step + i, over the history
-// and the tokens just written) and the length criterion are tested; nothing is written behind the first token that finishes the
-// row.  One row of one sequence: output_ids is [total_len].  step >= max(1, max_input_len), step + R <= total_len.
-// state / h_flags (the engine's; the flags of launch_verify_accept plus FLAG_SPEC_TOKENS / FLAG_SPEC_SEQ_LEN) and emitted /
-// accepted / tokens [16] (device) may each be NULL.  ws: verify_close_workspace_bytes().
+// The acceptance of every greedy pass -- of a bare request (stop_words, cum_log_probs, output_log_probs NULL) as of one with stop
+// words, log-probabilities or a streaming callback; the stand-alone ftcf_verify_accept of include/ftcf.h is the contract -- in two
+// launches.  k_verify_slices reduces every row in VERIFY_ACCEPT_SLICES vocabulary slices to {best, index, max, sum of
+// exponentials}; k_verify_close merges them in slice order into a[i] = argmax of logits row i (value descending, index ascending
+// on ties), takes m = the longest prefix with draft[i] == a[i] and closes the step: for i = 0 .. m in order the token a[i] goes to
+// output_ids[step + i], its log-probability logf(exp(v - max) / (sum + 1e-6f)) is added to cum_log_probs[0] (sequential fp32 adds)
+// and stored at output_log_probs[step + i - max_input_len], then end_id, the stop words (stop_word_ends_at at step + i, over the
+// history and the tokens just written) and the length criterion are tested; nothing is written behind the first token that
+// finishes the row.  seq_len[0] and the device step advance by the tokens emitted, finished / all_finished are set.
+// One row of one sequence: output_ids is [total_len].  step >= max(1, max_input_len), step + R <= total_len.
+// state / h_flags (the engine's, pinned, HostFlag: FLAG_ALL_FINISHED, FLAG_LAST_STEP, FLAG_SPEC_EMITTED, FLAG_SPEC_ACCEPTED,
+// FLAG_SPEC_TOKENS / FLAG_SPEC_SEQ_LEN; FLAG_SPEC_NEXT_DRAFTS is the draft kernel's) and emitted / accepted / tokens [16] (device)
+// may each be NULL.  ws: verify_close_workspace_bytes().
 constexpr int VERIFY_ACCEPT_SLICES = 32;
 struct VerifyCloseParams {
     const float* logits;  // [R, V]

@@ -215,25 +215,14 @@ __global__ __launch_bounds__(256) void k_beam_batch(const BeamParams p, const fl
         const int* words = p.stop_words + (size_t)b * 2 * p.stop_len;
         const int* offs  = words + p.stop_len;
         for (int id = 0; id < p.stop_len; id++) {
-            if (offs[id] < 0) {
-                continue;
-            }
-            const int item_end = offs[id], item_start = id > 0 ? offs[id - 1] : 0, item_size = item_end - item_start;
-            bool      stop = false;
-            if (step + 1 >= item_size) {
-                stop       = true;
-                int parent = tid;
-                for (int t = item_size - 1; t >= 0; t--) {
-                    const int ts  = step - (item_size - 1) + t;
-                    const int tok = p.output_ids[(size_t)ts * BK + b * K + parent];
-                    if (tok != words[item_start + t]) {
-                        stop = false;
-                        break;
-                    }
-                    parent = p.parent_ids[(size_t)ts * BK + b * K + parent];
+            int  parent   = tid;  // the hypothesis's ancestor at the position asked for: one link back per position, from `step` down
+            auto token_at = [&](const int ts) {
+                if (ts < step) {
+                    parent = p.parent_ids[(size_t)(ts + 1) * BK + b * K + parent];
                 }
-            }
-            if (stop) {
+                return p.output_ids[(size_t)ts * BK + b * K + parent];
+            };
+            if (stop_word_ends_at(words, offs, id, step, token_at)) {
                 p.finished[bb] = 1;
             }
         }

@@ -692,23 +692,7 @@ __device__ __forceinline__ int decode_finish_body(const SamplingParams& p, const
             const int* words = p.stop_words + (size_t)b * 2 * p.stop_len;
             const int* offs  = words + p.stop_len;
             for (int id = 0; id < p.stop_len; id++) {
-                if (offs[id] < 0) {
-                    continue;
-                }
-                const int item_end = offs[id], item_start = id > 0 ? offs[id - 1] : 0;
-                const int item_size = item_end - item_start;
-                bool      stop      = false;
-                if (step + 1 >= item_size) {
-                    stop = true;
-                    for (int t = item_size - 1; t >= 0; t--) {
-                        const int prev = p.output_ids[(size_t)(step - (item_size - 1) + t) * p.B + b];
-                        if (prev != words[item_start + t]) {
-                            stop = false;
-                            break;
-                        }
-                    }
-                }
-                if (stop) {
+                if (stop_word_ends_at(words, offs, id, step, [&](const int pos) { return p.output_ids[(size_t)pos * p.B + b]; })) {
                     p.finished[b] = 1;
                 }
             }
@@ -813,29 +797,6 @@ __device__ __forceinline__ void decode_step_tail(const SamplingParams& p, const 
         }
     }
     decode_publish_host(p, step, all);
-}
-
-// Four waves' {best, max, sum of exponentials} of a row -> the workgroup's: v / i / m / s hold wave w's entry at [w * stride].
-// Returns the best; row_max / tot: the maximum and the sum rescaled to it, added with w ascending.
-__device__ __forceinline__ VI merge_waves(const float* v, const int* i, const float* m, const float* s, const int stride, float& row_max,
-                                          float& tot)
-{
-    VI r{v[0], i[0]};
-    row_max = m[0];
-#pragma unroll
-    for (int w = 1; w < 4; w++) {
-        if (better(v[w * stride], i[w * stride], r.v, r.i)) {
-            r.v = v[w * stride];
-            r.i = i[w * stride];
-        }
-        row_max = fmaxf(row_max, m[w * stride]);
-    }
-    tot = 0.f;
-#pragma unroll
-    for (int w = 0; w < 4; w++) {
-        tot += s[w * stride] * __expf(m[w * stride] - row_max);
-    }
-    return r;
 }
 
 // the ticket of a launch of `total` workgroups on state->pad, drawn by ONE thread: true for the last one, which re-arms the counter
@@ -1015,7 +976,7 @@ __device__ __forceinline__ void greedy_finish(const SamplingParams& p, const flo
         __syncthreads();
         if (threadIdx.x == 0) {
             float    row_max, tot;
-            const VI r = merge_waves(x_v[pb], x_i[pb], x_m[pb], x_s[pb], 1, row_max, tot);
+            const VI r = merge_waves<4>(x_v[pb], x_i[pb], x_m[pb], x_s[pb], 1, row_max, tot);
             commit(row, out_id, r, row_max, tot, st);
         }
     }
@@ -1306,7 +1267,7 @@ __global__ __launch_bounds__(256, 8) void k_lm_head_greedy(const f16* __restrict
 #pragma unroll
         for (int m = 0; m < M; m++) {
             float    mx, sum;
-            const VI r = merge_waves(&w_v[0][m], &w_i[0][m], &w_m[0][m], &w_s[0][m], M, mx, sum);
+            const VI r = merge_waves<4>(&w_v[0][m], &w_i[0][m], &w_m[0][m], &w_s[0][m], M, mx, sum);
             // granules {tag, value}, write-through (the reader sits on another XCD); a workgroup without a vocabulary row leaves
             // the neutral partial {-inf, no id, -FLT_MAX, 0}
             gu64*                    o  = (gu64*)(part + ((size_t)m * nb + blockIdx.x) * 4);

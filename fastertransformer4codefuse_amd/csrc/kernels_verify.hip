@@ -10,8 +10,9 @@
 //      the head's last ticket (the ORDER is fixed whoever merges: two launches give the same bits), one normalisation with
 //      the reference's + 1e-6, the context rounded once.
 //  * k_ngram_draft      : prompt-lookup drafting, one workgroup.
-//  * k_verify_embed / k_verify_argmax / k_verify_accept : the pass's input rows and the greedy acceptance rule.
-//  * k_verify_slices / k_verify_close : the acceptance rule of a request with stop words, log-probabilities or a callback.
+//  * k_verify_embed     : the pass's input rows.
+//  * k_verify_slices / k_verify_close : the acceptance rule of every greedy request, bare or with stop words, log-probabilities
+//      or a callback.
 //  * k_verify_topk_slices / k_verify_pick / k_verify_sample_close : the same for a top-k sampled request, token for token.
 //
 // Roofline: HBM (4 * len * dh * nh bytes per layer, once for all rows); the VALU work grows with R (R * dh fused
@@ -471,7 +472,7 @@ void launch_ngram_draft(const int* tokens, int n, const int* d_n, int K, int N, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// the pass's input rows and the acceptance rule
+// the pass's input rows
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_verify_embed(f16* x, const f16* __restrict__ wte, const int* __restrict__ tokens,
                                                       const int* __restrict__ draft, int step, int H)
@@ -491,92 +492,16 @@ void launch_verify_embed(f16* x, const f16* wte, const int* tokens, const int* d
     FTCF_HIP_CHECK(hipGetLastError());
 }
 
-// a[r] = argmax of row r: value descending, index ascending on ties (the rule of the greedy / top-k kernels)
-__global__ __launch_bounds__(256) void k_verify_argmax(const float* __restrict__ logits, int V, int* out)
-{
-    __shared__ float s_v[4];
-    __shared__ int   s_i[4];
-    const int    r = blockIdx.x, lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const float* l = logits + (size_t)r * V;
-    float        bv = -INFINITY;
-    int          bi = 0x7fffffff;
-    for (int i = threadIdx.x; i < V; i += 256) {
-        const float v = l[i];
-        if (v > bv || (v == bv && i < bi)) {
-            bv = v;
-            bi = i;
-        }
-    }
-    for (int o = 32; o >= 1; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const int   oi = __shfl_xor(bi, o, 64);
-        if (ov > bv || (ov == bv && oi < bi)) {
-            bv = ov;
-            bi = oi;
-        }
-    }
-    if (lane == 0) {
-        s_v[wid] = bv;
-        s_i[wid] = bi;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; w++) {
-            if (s_v[w] > bv || (s_v[w] == bv && s_i[w] < bi)) {
-                bv = s_v[w];
-                bi = s_i[w];
-            }
-        }
-        out[r] = bi < V ? bi : 0;
-    }
-}
-
-__global__ void k_verify_accept(const VerifyAcceptParams p)
-{
-    if (threadIdx.x != 0) {
-        return;
-    }
-    const int* a = p.argmax_ws;
-    int        m = 0;
-    while (m < p.R - 1 && p.draft[m] == a[m]) {
-        m++;
-    }
-    int e = 0, fin = 0;
-    for (int i = 0; i <= m && !fin; i++) {  // the accepted drafts and the model's own next token, cut after the first end_id
-        p.output_ids[p.step + i] = a[i];
-        e++;
-        fin = a[i] == p.end_id;
-    }
-    p.seq_len[0] += e;
-    p.finished[0]         = (uint8_t)fin;
-    p.state->all_finished = fin;
-    p.state->steps_done += e;
-    p.state->step = p.step + e;
-    p.h_flags[FLAG_LAST_STEP]     = p.step + e - 1;
-    p.h_flags[FLAG_SPEC_EMITTED]  = e;
-    p.h_flags[FLAG_SPEC_ACCEPTED] = m < e ? m : e;  // drafts that became output tokens
-    __threadfence_system();
-    p.h_flags[FLAG_ALL_FINISHED] = fin;
-}
-
-void launch_verify_accept(const VerifyAcceptParams& p, hipStream_t s)
-{
-    FTCF_CHECK_ARG(p.R >= 1 && p.R <= VERIFY_MAX_ROWS && p.V >= 1, "verify accept: bad arguments");
-    hipLaunchKernelGGL(k_verify_argmax, dim3(p.R), dim3(256), 0, s, p.logits, p.V, p.argmax_ws);
-    hipLaunchKernelGGL(k_verify_accept, dim3(1), dim3(64), 0, s, p);
-    FTCF_HIP_CHECK(hipGetLastError());
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
-// The decode tail of a verify pass whose request has stop words, log-probabilities or a streaming callback (speculative scope 1,
-// DESIGN.md section 4g), in two launches:
+// The decode tail of a verify pass of a greedy request -- bare, or with stop words, log-probabilities or a streaming callback
+//  -- in two launches:
 //  * k_verify_slices : grid (VS_SLICES, R).  A workgroup reduces its contiguous slice of its row to {best value, best index,
 //      slice max, sum of exp(v - slice max)} -- the partial of k_greedy_decode -- with VS_MAXE loads per thread in flight, chunk by
-//      chunk for a slice longer than 256 * VS_MAXE logits (any V).  Against k_verify_argmax (one workgroup per row: V / 256
-//      DEPENDENT loads per thread, 394 at V = 100864) a row is read by 32 workgroups at 13 independent loads per thread.
+//      chunk for a slice longer than 256 * VS_MAXE logits (any V).  Against one workgroup per row (V / 256 DEPENDENT loads per
+//      thread, 394 at V = 100864) a row is read by 32 workgroups at 13 independent loads per thread.
 //  * k_verify_close  : one workgroup.  Every row's partials are merged in slice order by one thread (a fixed order: two launches
 //      give identical bits), then the step is closed in one place: the accepted prefix, the tokens, their log-probabilities, the
-//      end token, the stop words (decode_finish_body's rule, kernels_sampling.hip), the length criterion, the state words and
+//      end token, the stop words (stop_word_ends_at, the rule of decode_finish_body), the length criterion, the state words and
 //      the pinned flags -- with the emitted tokens and the sequence length behind each, so that the host's callback copies nothing.
 // No workgroup waits for another: the launch boundary orders the partials.
 // ---------------------------------------------------------------------------------------------------------------------
@@ -634,19 +559,8 @@ __global__ __launch_bounds__(256) void k_verify_slices(const float* __restrict__
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        VI    b{redv[0], redi[0]};
-        float bm = redm[0];
-        for (int w = 1; w < 4; w++) {
-            if (better(redv[w], redi[w], b.v, b.i)) {
-                b.v = redv[w];
-                b.i = redi[w];
-            }
-            bm = fmaxf(bm, redm[w]);
-        }
-        float tot = 0.f;
-        for (int w = 0; w < 4; w++) {
-            tot += reds[w] * __expf(redm[w] - bm);
-        }
+        float    bm, tot;
+        const VI b = merge_waves<4>(redv, redi, redm, reds, 1, bm, tot);
         // write-through stores (agent scope: the closing workgroup may sit on another XCD)
         va_gu32* o = (va_gu32*)(part + ((size_t)r * VS_SLICES + blk) * 4);
         __hip_atomic_store(o + 0, __float_as_uint(n > 0 ? b.v : -INFINITY), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -656,9 +570,19 @@ __global__ __launch_bounds__(256) void k_verify_slices(const float* __restrict__
     }
 }
 
+// The LDS words of verify_close_stages that do not depend on the rows' tokens (VERIFY_MAX_ROWS of each): the drafts, -1 behind the
+// last, and the stop marks.  The caller's next barrier publishes them.
+__device__ __forceinline__ void verify_close_setup(const VerifyCloseParams& p, int* s_draft, int* s_stop)
+{
+    if ((int)threadIdx.x < VERIFY_MAX_ROWS) {
+        s_draft[threadIdx.x] = (int)threadIdx.x < p.R - 1 ? p.draft[threadIdx.x] : -1;
+        s_stop[threadIdx.x]  = 0;
+    }
+}
+
 // Stages 1 - 4 of a pass's close, shared by k_verify_close and k_verify_sample_close: s_a[r] / s_lp[r] are row r's token and its
-// log-probability, s_draft[r] the drafts (-1 behind the last), s_stop[] zero, all in LDS behind a barrier.  Returns the tokens
-// emitted (in thread 0; 0 in every other thread).
+// log-probability, s_draft[] / s_stop[] verify_close_setup's, all in LDS behind a barrier.  Returns the tokens emitted (in thread
+// 0; 0 in every other thread).
 __device__ __forceinline__ int verify_close_stages(const VerifyCloseParams& p, const bool lp_on, const int* s_a, const float* s_lp,
                                                    const int* s_draft, int* s_stop, int* s_m_slot)
 {
@@ -681,25 +605,7 @@ __device__ __forceinline__ int verify_close_stages(const VerifyCloseParams& p, c
         const int* offs  = words + p.stop_len;
         for (int w = threadIdx.x; w < (m + 1) * p.stop_len; w += 256) {
             const int i = w / p.stop_len, id = w % p.stop_len;
-            if (offs[id] < 0) {
-                continue;
-            }
-            const int item_end = offs[id], item_start = id > 0 ? offs[id - 1] : 0;
-            const int item_size = item_end - item_start;
-            const int step      = st + i;
-            bool      stop      = false;
-            if (step + 1 >= item_size) {
-                stop = true;
-                for (int t = item_size - 1; t >= 0; t--) {
-                    const int pos  = step - (item_size - 1) + t;
-                    const int prev = pos >= st ? s_a[pos - st] : p.output_ids[pos];
-                    if (prev != words[item_start + t]) {
-                        stop = false;
-                        break;
-                    }
-                }
-            }
-            if (stop) {
+            if (stop_word_ends_at(words, offs, id, st + i, [&](const int pos) { return pos >= st ? s_a[pos - st] : p.output_ids[pos]; })) {
                 atomicOr(&s_stop[i], 1);
             }
         }
@@ -774,13 +680,11 @@ __global__ __launch_bounds__(256) void k_verify_close(const VerifyCloseParams p,
         for (int i = threadIdx.x; i < R * VS_SLICES * 4; i += 256) {
             s_part[i] = __hip_atomic_load(q + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        if ((int)threadIdx.x < RM) {
-            s_draft[threadIdx.x] = (int)threadIdx.x < R - 1 ? p.draft[threadIdx.x] : -1;
-            s_stop[threadIdx.x]  = 0;
-        }
+        verify_close_setup(p, s_draft, s_stop);
     }
     __syncthreads();
-    // ---- a[r] and its log-probability: row r's partials in slice order, by one thread ----
+    // ---- a[r] and its log-probability: row r's partials in slice order, by one thread (merge_waves' order, written out: a
+    // slice's four words lie together as stored, the index among the floats, and are read as what they are) ----
     if ((int)threadIdx.x < R) {
         const unsigned* q = s_part + threadIdx.x * VS_SLICES * 4;
         VI    b{__uint_as_float(q[0]), (int)q[1]};
@@ -810,13 +714,20 @@ size_t verify_close_workspace_bytes()
     return (size_t)VERIFY_MAX_ROWS * VS_SLICES * 4 * sizeof(float);
 }
 
+// what either close asks of a pass's parameters (its own workspace apart); who: the prefix of its messages
+static void check_close_params(const VerifyCloseParams& p, const std::string& who)
+{
+    FTCF_CHECK_ARG(p.R >= 1 && p.R <= VERIFY_MAX_ROWS && p.V >= 1, who + ": 1 <= rows <= 16, vocabulary >= 1");
+    FTCF_CHECK_ARG(p.logits && p.output_ids && p.finished && p.seq_len && (p.R == 1 || p.draft), who + ": NULL tensor");
+    FTCF_CHECK_ARG(p.step >= 1 && p.max_input_len >= 0 && p.step >= p.max_input_len && p.step + p.R <= p.total_len,
+                   who + ": the rows' positions step .. step + R - 1 must lie in [max(1, max_input_len), total_len)");
+    FTCF_CHECK_ARG(!p.stop_words || p.stop_len >= 1, who + ": stop_words needs stop_len >= 1");
+}
+
 void launch_verify_close(const VerifyCloseParams& p, hipStream_t s)
 {
-    FTCF_CHECK_ARG(p.R >= 1 && p.R <= VERIFY_MAX_ROWS && p.V >= 1, "verify accept: 1 <= rows <= 16, vocabulary >= 1");
-    FTCF_CHECK_ARG(p.logits && p.output_ids && p.finished && p.seq_len && p.ws && (p.R == 1 || p.draft), "verify accept: NULL tensor");
-    FTCF_CHECK_ARG(p.step >= 1 && p.max_input_len >= 0 && p.step >= p.max_input_len && p.step + p.R <= p.total_len,
-                   "verify accept: the rows' positions step .. step + R - 1 must lie in [max(1, max_input_len), total_len)");
-    FTCF_CHECK_ARG(!p.stop_words || p.stop_len >= 1, "verify accept: stop_words needs stop_len >= 1");
+    check_close_params(p, "verify accept");
+    FTCF_CHECK_ARG(p.ws, "verify accept: NULL tensor");
     hipLaunchKernelGGL(k_verify_slices, dim3(VS_SLICES, p.R), dim3(256), 0, s, p.logits, p.V, p.ws);
     hipLaunchKernelGGL(k_verify_close, dim3(1), dim3(256), 0, s, p, (const float*)p.ws);
     FTCF_HIP_CHECK(hipGetLastError());
@@ -973,9 +884,8 @@ __global__ __launch_bounds__(256) void k_verify_sample_close(const VerifyClosePa
         const unsigned lp = __hip_atomic_load(q + RM + rc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         s_a[r]     = r < R ? (int)id : 0;
         s_lp[r]    = r < R ? __uint_as_float(lp) : 0.f;
-        s_draft[r] = r < R - 1 ? p.draft[r] : -1;
-        s_stop[r]  = 0;
     }
+    verify_close_setup(p, s_draft, s_stop);
     __syncthreads();
     const int e = verify_close_stages(p, lp_on, s_a, s_lp, s_draft, s_stop, &s_m);
     if (threadIdx.x == 0) {
@@ -991,14 +901,10 @@ size_t verify_sample_workspace_bytes()
 void launch_verify_sample(const VerifySampleParams& q, hipStream_t s)
 {
     const VerifyCloseParams& p = q.c;
-    FTCF_CHECK_ARG(p.R >= 1 && p.R <= VERIFY_MAX_ROWS && p.V >= 1, "verify sample: 1 <= rows <= 16, vocabulary >= 1");
+    check_close_params(p, "verify sample");
     FTCF_CHECK_ARG(q.top_k >= 1 && q.top_k <= VERIFY_SAMPLE_MAX_K && p.V <= VERIFY_SAMPLE_MAX_V,
                    "verify sample: 1 <= top_k <= 64, vocabulary <= 131072");
-    FTCF_CHECK_ARG(p.logits && p.output_ids && p.finished && p.seq_len && q.ws && q.draw_counter && (p.R == 1 || p.draft),
-                   "verify sample: NULL tensor");
-    FTCF_CHECK_ARG(p.step >= 1 && p.max_input_len >= 0 && p.step >= p.max_input_len && p.step + p.R <= p.total_len,
-                   "verify sample: the rows' positions step .. step + R - 1 must lie in [max(1, max_input_len), total_len)");
-    FTCF_CHECK_ARG(!p.stop_words || p.stop_len >= 1, "verify sample: stop_words needs stop_len >= 1");
+    FTCF_CHECK_ARG(q.ws && q.draw_counter, "verify sample: NULL tensor");
     const int lp_on = (p.cum_log_probs || p.output_log_probs) ? 1 : 0;
     hipLaunchKernelGGL(k_verify_topk_slices, dim3(VS_SLICES, p.R), dim3(256), 0, s, p.logits, p.V, q.top_k, lp_on, q.apply_temperature,
                        q.temperature, q.ws);

@@ -1,6 +1,7 @@
 // Device primitives shared by the dynamic decode (kernels_sampling.hip) and beam search (kernels_beam.hip): the {value, id}
-// arg-best with its tie rule, the workgroup max / sum through an LDS array, the optional-last-tokens mask -- and by the dynamic
-// decode and the sampled tail of a verify pass (kernels_verify.hip): the counter-based uniform number, a vocabulary slice in
+// arg-best with its tie rule, the workgroup max / sum through an LDS array, the optional-last-tokens mask -- by those two and the
+// close of a verify pass (kernels_verify.hip): the stop-word rule, the merge of a row's partials -- and by the dynamic
+// decode and the sampled tail of a verify pass: the counter-based uniform number, a vocabulary slice in
 // registers (load, soft-max statistics, the radix select of its k best), the merge of the slices' candidate sets and the top-k
 // layer's draw.
 #pragma once
@@ -77,6 +78,52 @@ __device__ __forceinline__ float block_sum_ordered(float v, float* red, const in
         tot += red[w];
     }
     return tot;
+}
+
+// N partials {best, max, sum of exponentials} of a row (a workgroup's waves') -> the workgroup's: v / i / m / s hold partial w's
+// entry at [w * stride].  Returns the best; row_max / tot: the maximum and the sum rescaled to it, added with w ascending.
+template<int N>
+__device__ __forceinline__ VI merge_waves(const float* v, const int* i, const float* m, const float* s, const int stride, float& row_max,
+                                          float& tot)
+{
+    VI r{v[0], i[0]};
+    row_max = m[0];
+#pragma unroll
+    for (int w = 1; w < N; w++) {
+        if (better(v[w * stride], i[w * stride], r.v, r.i)) {
+            r.v = v[w * stride];
+            r.i = i[w * stride];
+        }
+        row_max = fmaxf(row_max, m[w * stride]);
+    }
+    tot = 0.f;
+#pragma unroll
+    for (int w = 0; w < N; w++) {
+        tot += s[w * stride] * __expf(m[w * stride] - row_max);
+    }
+    return r;
+}
+
+// The stop-word rule (stop_criteria_kernels.cu:24-83): does word `id` of the list {words[stop_len], offs[stop_len]} end at position
+// `step`?  token_at(pos) yields the token at a position; it is called for pos = step, step - 1, ... in DESCENDING order up to the
+// first mismatch, so a caller may carry state from one position to the one before it (the beam step's parent chain).
+template<class TokenAt>
+__device__ __forceinline__ bool stop_word_ends_at(const int* words, const int* offs, const int id, const int step, TokenAt&& token_at)
+{
+    if (offs[id] < 0) {
+        return false;
+    }
+    const int item_end = offs[id], item_start = id > 0 ? offs[id - 1] : 0;
+    const int item_size = item_end - item_start;
+    if (step + 1 < item_size) {
+        return false;
+    }
+    for (int t = item_size - 1; t >= 0; t--) {
+        if (token_at(step - (item_size - 1) + t) != words[item_start + t]) {
+            return false;
+        }
+    }
+    return true;
 }
 
 // K15 select_optional_last_tokens (select_optional_last_tokens.cu:22-85): every logit of the row `l` whose token is not in

@@ -237,8 +237,8 @@ size_t ftcf_verify_attention_workspace(int R, int nh, int dh, int s_max);
  * draft is t[s + g, min(s + g + K, n)).  No match: zero drafts.  draft [K] and n_draft [1] are device int32.  1 <= K <= 15,
  * 1 <= N <= 8. */
 int ftcf_ngram_draft(const int* tokens, int n, int K, int N, int* draft, int* n_draft, void* stream);
-/* The decode tail of a verify pass for a request with stop words, log-probabilities or a streaming callback (the engine runs it
- * for every pass of a request that began under ftcf_gptneox_set_speculative_scope(h, 1)): two launches and nothing else.
+/* The decode tail of a verify pass of a greedy request, bare or with stop words, log-probabilities or a streaming callback (the
+ * engine runs it for every greedy pass, whatever ftcf_gptneox_set_speculative_scope says): two launches and nothing else.
  * logits [R, V] fp32 (device, not modified) are the pass's rows: row i is the model's distribution behind the token of position
  * step + i - 1, i.e. behind draft[i - 1] for i >= 1.  a[i] = the arg max of row i (value descending, index ascending on ties);
  * m = the longest prefix with draft[i] == a[i] (draft [R - 1] device int32; NULL with R = 1).  For i = 0 .. m in order:
@@ -713,9 +713,9 @@ int ftcf_gptneox_get_stats(ftcf_gptneox_t h, ftcf_forward_stats* stats);
 /* enable HIP-event timing around every weight-streaming launch of the decode loop (bench.py roofline leg) */
 int ftcf_gptneox_set_profiling(ftcf_gptneox_t h, int enabled);
 /* Which requests with speculative_tokens > 0 may speculate (a switch of the engine, not a request field: ftcf_forward_args keeps
- * its layout).  0, the default: the bare greedy request, as before the switch existed -- the same launches, bits and spec_active.
+ * its layout).  0, the default: the bare greedy request, as before the switch existed -- the same tokens, bits and spec_active.
  * 1: also a request with stop words, return_cum_log_probs, output_log_probs, a streaming callback or optional_last_tokens (see
- * speculative_tokens of ftcf_forward_args); every verify pass of such an engine closes with the two launches of
+ * speculative_tokens of ftcf_forward_args).  At either scope every greedy verify pass closes with the two launches of
  * ftcf_verify_accept.  Holds for requests begun after the call.  Any other value: FTCF_ERR_INVALID_ARG. */
 int ftcf_gptneox_set_speculative_scope(ftcf_gptneox_t h, int scope);
 /* Whether a TOP-K SAMPLED request with speculative_tokens > 0 may speculate (a switch of the engine like the scope, and

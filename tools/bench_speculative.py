@@ -10,10 +10,10 @@ plain step time.  Plain and speculative runs alternate inside the one process, a
     python tools/bench_speculative.py [--prompt-len 1024] [--out-len 512] [--rounds 3] [--ks 2,4,8] [--every 0,4,2,1]
 
 --scope adds the leg of the wider speculative scope (GptNeoXOp.set_speculative_scope(1)): the same workload as the harness sends
-it -- return_cum_log_probs, a stop-word list that never matches and a no-op callback -- whose passes close with k_verify_slices +
-k_verify_close instead of k_verify_argmax + k_verify_accept.  Per round the plain run, the scope 0 run and the scope 1 run follow
-each other in the one process; a row reports both legs' milliseconds per verify pass (best, and the spread over the rounds) and
-tokens/s (profiles/speculative_scope_bench.txt).
+it -- return_cum_log_probs, a stop-word list that never matches and a no-op callback.  The passes of both legs close with
+k_verify_slices + k_verify_close: the legs differ only in what the request carries.  Per round the plain run, the scope 0 run and
+the scope 1 run follow each other in the one process; a row reports both legs' milliseconds per verify pass (best, and the
+spread over the rounds) and tokens/s (profiles/speculative_scope_bench.txt).
 
 --sampled adds the leg of speculative SAMPLING (GptNeoXOp.set_speculative_sampling(1)): the request as the harness sends it with its
 top_k = 50, whose passes close with k_verify_topk_slices + k_verify_pick + k_verify_sample_close.  The drafts are the plain SAMPLED
